@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the rasterizer hot path on MI355X (contract: see the repo's DESIGN.md §Measurement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S2] [--dump-outputs DIR] [--full]
 
 A "step" is one training iteration of the hot path over one view of a synthetic scene: forward
 (geometry -> binning -> 16x16-tile blend) + backward (per-pixel backward -> geometry backward) through the
@@ -9,8 +9,16 @@ drop-in GaussianRasterizer, with fixed synthetic upstream gradients dL/dcolor, d
 inputs resident in HBM.  N > 1: one process per GPU, data-parallel over views, ONE RCCL all-reduce of the
 236 B/Gaussian parameter-gradient bucket per step (inside the timed region).
 
+A plain run sets up, runs W warm-up steps, times K steps (nothing else inside them), writes the last timed step's
+outputs when --dump-outputs DIR is given, and prints the headline line.  --full adds everything else below: the
+timed steps repeated in --blocks blocks with HIP events on the dominant kernel, per-stage times, the `sustained`
+repetition, the forward-only leg, rooflines and the secondary legs (other sizes, scenes, SH degrees, captured steps,
+CPU baseline).
+
 Rank 0 prints ONE JSON line:
   metric/value  train iterations (= views) per second, whole job
+  ms_per_step   milliseconds per timed step (K steps directly behind the W warm-up steps)
+--full only:
   render_mpix_per_sec   forward-only megapixels per second (the other half of BASELINE.json's metric)
   roofline      dominant kernel's algorithmic bytes / mean HIP-event duration vs the 8 TB/s HBM peak
   cpu_baseline  the pure-PyTorch CPU oracle timed on this box's host cores on a bounded sample (N=1 only)
@@ -19,6 +27,7 @@ Rank 0 prints ONE JSON line:
 from __future__ import annotations
 
 import argparse
+import contextlib
 import gc
 import json
 import math
@@ -168,6 +177,57 @@ def forward_only(setts, params, steps, warmup, timer):
         stages = timer.summary()
         stages.update(dominant)
     return dt, {"radii": fs[0], "num_rendered": fs[1]}, stages
+
+
+DUMP_BUDGET_BYTES = 64_000_000     # --dump-outputs: every .npy file of one run together
+
+
+def dump_outputs(dirname, last, params, seed=0):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy in float32 — per view the colour,
+    depth and alpha images and the radii, the gradients of means2D and of the five parameters.  A set larger than
+    DUMP_BUDGET_BYTES keeps a fixed seeded sample of Gaussians (rows of the per-Gaussian arrays; gaussian_index.npy) and,
+    only when the images alone take more than half the budget, of pixels as well (the images flattened to channels x
+    pixels, the same fraction of both; pixel_index.npy).  Indices are float64.  Same workload, same rows and pixels,
+    whichever build runs it."""
+    import numpy as np
+    outs, means2D = last
+    K = len(outs)
+    images, rows = {}, {}
+    for k, (c, radii, d, a) in enumerate(outs):
+        pre = f"view{k}_" if K > 1 else ""
+        images.update({pre + "color": c, pre + "depth": d, pre + "alpha": a})
+        rows[pre + "radii"] = radii
+        if means2D.grad is not None:
+            rows[pre + "grad_means2D"] = means2D.grad[k] if K > 1 else means2D.grad
+    for name, p in zip(("means3D", "shs", "opacities", "scales", "rotations"), params):
+        if p.grad is not None:
+            rows["grad_" + name] = p.grad
+    P = params[0].shape[0]
+    HW = outs[0][0].shape[-2] * outs[0][0].shape[-1]
+    row_bytes = sum(4 * t[0].numel() for t in rows.values())           # per Gaussian
+    px_bytes = sum(4 * t.shape[0] for t in images.values())            # per pixel
+    budget = DUMP_BUDGET_BYTES - 256 * (len(rows) + len(images) + 2)   # (.npy headers)
+    gen = torch.Generator().manual_seed(seed)
+    g_idx = px_idx = None
+    if P * row_bytes + HW * px_bytes > budget:
+        if HW * px_bytes <= budget // 2:
+            n_g = (budget - HW * px_bytes) // (row_bytes + 8)
+        else:
+            frac = budget / (P * (row_bytes + 8) + HW * (px_bytes + 8))
+            n_g = int(frac * P)
+            px_idx = torch.randperm(HW, generator=gen)[:int(frac * HW)].sort().values
+        g_idx = torch.randperm(P, generator=gen)[:n_g].sort().values
+    os.makedirs(dirname, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(dirname, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
+    for name, t in rows.items():
+        save(name, t if g_idx is None else t[g_idx.to(t.device)])
+    for name, t in images.items():
+        save(name, t if px_idx is None else t.reshape(t.shape[0], -1)[:, px_idx.to(t.device)])
+    for name, idx in (("gaussian_index", g_idx), ("pixel_index", px_idx)):
+        if idx is not None:
+            np.save(os.path.join(dirname, name + ".npy"), idx.numpy().astype(np.float64))
 
 
 _PMC = None
@@ -696,13 +756,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)      # 200 x 0.4 ms: long enough to average host hiccups out
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--blocks", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: blocks, stage times, sustained, forward-only, rooflines, "
+                         "secondary legs and the CPU baseline (a plain run times the K steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (images, radii, parameter "
+                         "gradients) as DIR/<name>.npy, float32, at most 64 MB in all")
+    ap.add_argument("--blocks", type=int, default=None,
                     help="the K timed steps are repeated this many times back to back: value_median / _min / _max (BASELINE.md: "
-                         "median of >= 5 runs); `value` is the first block")
+                         "median of >= 5 runs); `value` is the first block (default: 5 with --full, 1 otherwise)")
     ap.add_argument("--workload", default="S2", choices=sorted(syn.WORKLOADS))
     ap.add_argument("--sh-degree", type=int, default=3)
     ap.add_argument("--sustained-steps", type=int, default=1000,
-                    help="untimed steps before the `sustained` repetition of the K timed steps (0: skip it)")
+                    help="--full: untimed steps before the `sustained` repetition of the K timed steps (0: skip it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-s3", action="store_true")
     ap.add_argument("--no-full-iteration", action="store_true")
@@ -796,10 +862,14 @@ def main():
     # would cost more host time than some stages take on the GPU.
     timer = R.StageTimer()
     timed = R.StageTimer(only=("blend_backward", "grad_allreduce"))
-    R.set_stage_timer(timed)
+    # --full: HIP events on the dominant kernel inside the timed steps (its roofline line is measured live); a plain run
+    # times the steps alone
+    R.set_stage_timer(timed if args.full else None)
     EVENT_EVERY = 4 if args.steps >= 8 else 1
+    blocks = max(1, args.blocks if args.blocks is not None else (5 if args.full else 1))
 
     def train_step(step):
+        """One step; returns what its caller receives: [(color, radii, depth, alpha)] per view, and means2D (its .grad)."""
         for p in params:
             p.grad = None
         if multi is None:
@@ -807,6 +877,7 @@ def main():
             means2D = torch.zeros_like(means, requires_grad=True)
             c, radii, d, a = rasts[v](means3D=means, means2D=means2D, opacities=opac, shs=shs, scales=scales, rotations=rots)
             torch.autograd.backward([c, d, a], list(ups[v]))
+            outs = [(c, radii, d, a)]
         else:
             # K consecutive views of this rank in one node: forward x K, backward x K accumulating in the kernel
             vs = [(par.view_for(step, rank, world, 1 << 30) * K + k) % N_VIEWS for k in range(K)]
@@ -814,16 +885,15 @@ def main():
             means2D = torch.zeros((K,) + tuple(means.shape), device=dev, requires_grad=True)
             outs = multi(means3D=means, means2D=means2D, opacities=opac, shs=shs, scales=scales, rotations=rots)
             torch.autograd.backward([t for o in outs for t in (o[0], o[2], o[3])], [g for v in vs for g in ups[v]])
-            radii = outs[-1][1]
         if bucket is not None:
-            with timed("grad_allreduce"):
+            with (timed("grad_allreduce") if args.full else contextlib.nullcontext()):
                 bucket.reduce_grads(params)
-        return radii
+        return outs, means2D
 
     gc.collect()
     gc.disable()                 # a 0.3 ms step creates no reference cycles worth a collector pause inside the timed region
     for i in range(args.warmup):
-        train_step(i)
+        last = train_step(i)
     timed.reset()                # (nothing slow between the warm-up and the timed steps: an idle gap of a few ms lets the
     par.barrier()                #  GPU fall back to its low-power clocks, which a short run then pays for)
     torch.cuda.synchronize()
@@ -831,19 +901,60 @@ def main():
     # barrier + synchronize and reduced with MAX over ranks; `value` stays the FIRST block (the K steps directly behind the W
     # warm-up steps: comparable with every earlier round's line), `value_median / _min / _max` are over all blocks.
     block_dts = []
-    for b in range(max(1, args.blocks)):
+    for b in range(blocks):
         t0 = time.perf_counter()
         for i in range(args.steps):
             # the dominant kernel is timed live, with events on its own dispatch packet — on every EVENT_EVERY-th step: a dispatch
             # that carries a completion signal costs the queue ~7 us in front of it and ~5 us behind (rocprofv3 trace of this loop,
             # profiles/README.md round 5: 11.8 us of a 280 us step), which is the MEASUREMENT's time, not the path's
-            R.set_stage_timer(timed if (i % EVENT_EVERY == 0 and b == 0) else None)
-            radii = train_step(args.warmup + b * args.steps + i)
+            R.set_stage_timer(timed if (args.full and i % EVENT_EVERY == 0 and b == 0) else None)
+            last = train_step(args.warmup + b * args.steps + i)
         torch.cuda.synchronize()
         par.barrier()
         block_dts.append(par.max_over_ranks(time.perf_counter() - t0, dev))
     dt = block_dts[0]
     gc.enable()
+    radii = last[0][-1][1]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, params)
+
+    V = int((radii > 0).sum().item())
+    ms_per_step = dt / args.steps * 1e3
+    out = {
+        # one iteration of the reference = one view rendered and differentiated (train.py:143-170).  With K > 1 views per
+        # autograd node a "step" is K views behind ONE optimizer step: the metric is then named for what it counts.
+        "metric": "train_iters_per_sec" if K == 1 else "train_views_per_sec",
+        "value": round(world * K * args.steps / dt, 3), "unit": "iters/s" if K == 1 else "views/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "optimizer_steps_per_sec": round(args.steps / dt, 3),
+        "views_per_sec": round(world * K * args.steps / dt, 3),
+        "ms_per_view": round(ms_per_step / K, 4),
+        "value_is": "cold: the K timed steps directly after the W warm-up steps the caller asked for (device still raising "
+                    "its clocks when W is small)",
+        "full": args.full,
+        "config": {"workload": f"{args.workload}: {P} Gaussians, {W}x{H}, SH degree {deg}, fwd+bwd per view "
+                               f"({WORKLOAD_CONFIG.get(args.workload, 'no BASELINE config of this shape')})",
+                   "gaussians": P, "width": W, "height": H, "sh_degree": deg, "visible": V,
+                   "views": N_VIEWS, "parallelism": f"dp{world}-over-views" if world > 1 else "single",
+                   "ranks_seen": ranks_seen,
+                   "launched_by": ("bench.py's own launcher" if os.environ.get("SCG_BENCH_LAUNCHED") else
+                                   "external launcher (torchrun)" if world > 1 else "single process"),
+                   "grad_bucket_bytes": bucket.nbytes if bucket else 0,
+                   "views_per_step": K,
+                   "grad_bucket_bytes_per_view": (bucket.nbytes // K) if bucket else 0,
+                   "dist_backend": (args.dist_backend or "nccl") if bucket is not None else None,
+                   "exchange": "one all-reduce of the flat gradient arena per step (= per K views per rank), inside the timed region"
+                               if bucket is not None else None,
+                   "host": "scgaussian_amd.single_gpu_host_setup(): autograd backward on the calling thread"},
+    }
+    if not args.full:
+        if rank == 0:
+            json_out.write(json.dumps(out) + "\n")
+            json_out.flush()
+        par.shutdown()
+        return
+
     dominant_ms = timed.summary()
     # second pass, untimed: every stage
     R.set_stage_timer(timer)
@@ -897,19 +1008,26 @@ def main():
     if rank != 0:
         par.shutdown()
         return
-    V = int((radii > 0).sum().item())
     R_ = int(fs["num_rendered"])
     alg = algorithmic_bytes(P, V, R_, W, H, deg)
     kern = {k: v for k, v in stage_ms.items() if k in alg}
     dominant = max(kern, key=lambda k: kern[k][0])
-    ms_per_step = dt / args.steps * 1e3
-    out = {
-        # one iteration of the reference = one view rendered and differentiated (train.py:143-170).  With K > 1 views per
-        # autograd node a "step" is K views behind ONE optimizer step: the metric is then named for what it counts.
-        "metric": "train_iters_per_sec" if K == 1 else "train_views_per_sec",
-        "value": round(world * K * args.steps / dt, 3), "unit": "iters/s" if K == 1 else "views/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+    out["value_is"] += "; `sustained` = the same K steps on a warm device"
+    out["config"].update({
+        "num_rendered": R_,
+        "rccl_version": rccl_version(),
+        # "arena": all-reduce of the gradient arena in place; "mixed" (SH degree < 3): the 44 B / Gaussian of the
+        # other gradients in place + the packed ACTIVE SH coefficients; "packed": pack / all-reduce / unpack
+        "exchange_path": getattr(bucket, "last_path", None) if bucket is not None else None,
+        "rccl_requested": {"NCCL_ALGO": os.environ.get("NCCL_ALGO"), "NCCL_PROTO": os.environ.get("NCCL_PROTO"),
+                           "note": "what the ranks ASKED RCCL for (--rccl-algo / --rccl-proto or the caller's "
+                                   "environment); null = RCCL's tuner decides; --rccl-debug prints what it picked"},
+        "per_tile_sort": ("inside the forward blend (tile_blend_forward_kernel: its time and 12 B / instance are in "
+                          "blend_forward)" if sort_in_blend(R_, W, H) else "tile_sort_kernel (binning stage)"),
+        "tile_order": ("cost recorded by the previous render of the same camera (ScgFrame.tile_cost_in; the "
+                       "bench cycles through its views like a training loop)" if R.TILE_COST_HINT
+                       else "list length (rasterizer.TILE_COST_HINT = False)")})
+    out.update({
         "value_median": round(world * K * args.steps / sorted(block_dts)[len(block_dts) // 2], 3),
         "value_min": round(world * K * args.steps / max(block_dts), 3),
         "value_max": round(world * K * args.steps / min(block_dts), 3),
@@ -917,38 +1035,7 @@ def main():
                          "ms_per_step": [round(d_ / args.steps * 1e3, 4) for d_ in block_dts],
                          "note": "K-step blocks timed back to back (barrier + synchronize around each, MAX over ranks); `value` = "
                                  "block 0, the K steps directly behind the W warm-up steps"},
-        "optimizer_steps_per_sec": round(args.steps / dt, 3),
-        "views_per_sec": round(world * K * args.steps / dt, 3),
-        "value_is": ("cold: the K timed steps directly after the W warm-up steps the caller asked for (device still "
-                     "raising its clocks when W is small); `sustained` = the same K steps on a warm device"),
-        "config": {"workload": f"{args.workload}: {P} Gaussians, {W}x{H}, SH degree {deg}, fwd+bwd per view "
-                               f"({WORKLOAD_CONFIG.get(args.workload, 'no BASELINE config of this shape')})",
-                   "gaussians": P, "width": W, "height": H, "sh_degree": deg, "visible": V, "num_rendered": R_,
-                   "views": N_VIEWS, "parallelism": f"dp{world}-over-views" if world > 1 else "single",
-                   "ranks_seen": ranks_seen,
-                   "rccl_version": rccl_version(),
-                   "launched_by": ("bench.py's own launcher" if os.environ.get("SCG_BENCH_LAUNCHED") else
-                                   "external launcher (torchrun)" if world > 1 else "single process"),
-                   "grad_bucket_bytes": bucket.nbytes if bucket else 0,
-                   "views_per_step": K,
-                   "grad_bucket_bytes_per_view": (bucket.nbytes // K) if bucket else 0,
-                   "dist_backend": (args.dist_backend or "nccl") if bucket is not None else None,
-                   "exchange": "one all-reduce of the flat gradient arena per step (= per K views per rank), inside the timed region"
-                               if bucket is not None else None,
-                   # "arena": all-reduce of the gradient arena in place; "mixed" (SH degree < 3): the 44 B / Gaussian of the
-                   # other gradients in place + the packed ACTIVE SH coefficients; "packed": pack / all-reduce / unpack
-                   "exchange_path": getattr(bucket, "last_path", None) if bucket is not None else None,
-                   "rccl_requested": {"NCCL_ALGO": os.environ.get("NCCL_ALGO"), "NCCL_PROTO": os.environ.get("NCCL_PROTO"),
-                                      "note": "what the ranks ASKED RCCL for (--rccl-algo / --rccl-proto or the caller's "
-                                              "environment); null = RCCL's tuner decides; --rccl-debug prints what it picked"},
-                   "host": "scgaussian_amd.single_gpu_host_setup(): autograd backward on the calling thread",
-                   "per_tile_sort": ("inside the forward blend (tile_blend_forward_kernel: its time and 12 B / instance are in "
-                                     "blend_forward)" if sort_in_blend(R_, W, H) else "tile_sort_kernel (binning stage)"),
-                   "tile_order": ("cost recorded by the previous render of the same camera (ScgFrame.tile_cost_in; the "
-                                  "bench cycles through its views like a training loop)" if R.TILE_COST_HINT
-                                  else "list length (rasterizer.TILE_COST_HINT = False)")},
         "sustained": sustained,
-        "ms_per_view": round(ms_per_step / K, 4),
         "render_mpix_per_sec": round(world * args.steps * W * H / dt_f / 1e6, 2),
         "render_ms": round(dt_f / args.steps * 1e3, 4),
         # SURVEY §8d "unit of work": time per tile instance and per Gaussian, one view per rank
@@ -966,8 +1053,8 @@ def main():
         "roofline_sustained": (roofline_for(dominant, sustained_stage[dominant][0], alg[dominant], args.workload)
                                if sustained is not None and dominant in sustained_stage else None),
         "roofline_all": {k: roofline_for(k, kern[k][0], alg[k], args.workload) for k in kern},
-    }
-    # SURVEY §8e link budget next to the measured step, in EVERY line (N >= 1): what the exchange of this workload's gradient
+    })
+    # SURVEY §8e link budget next to the measured step, in EVERY --full line (N >= 1): what the exchange of this workload's gradient
     # arena (236 B per Gaussian at SH degree 3) would cost at 2 / 4 / 8 GPUs, and what K views per exchange buy
     arena_bytes = bucket.nbytes if bucket is not None else sum(int(p.numel()) * 4 for p in params)
     ar_ms = stage_ms.get("grad_allreduce", (0.0, 0))[0] if bucket is not None else 0.0

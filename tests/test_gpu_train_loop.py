@@ -199,7 +199,7 @@ def test_bench_launches_its_own_ranks_when_asked_for_more_than_one_gpu():
     they meet in one process group (gloo: both share this box's GPU — a code-path check, not a scaling number), rank 0 prints
     ONE line whose n_gpus is the size of the group the ranks actually saw."""
     res, line = _run_bench(["--gpus", "2", "--dist-backend", "gloo", "--workload", "S1", "--steps", "5", "--warmup", "2",
-                            "--sustained-steps", "0"])
+                            "--sustained-steps", "0", "--full"])
     assert res.returncode == 0, res.stderr[-3000:]
     assert line is not None and len([ln for ln in res.stdout.splitlines() if ln.startswith("{")]) == 1
     assert line["n_gpus"] == 2 and line["config"]["ranks_seen"] == 2
@@ -207,6 +207,46 @@ def test_bench_launches_its_own_ranks_when_asked_for_more_than_one_gpu():
     assert line["config"]["dist_backend"] == "gloo" and line["config"]["grad_bucket_bytes"] > 0
     assert line["stage_ms"].get("grad_allreduce", 0) > 0                 # the exchange ran inside the timed region
     assert line["value"] > 0
+
+
+def test_plain_bench_times_its_steps_and_dumps_what_the_last_step_returned(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline line of exactly --steps timed steps and none of the --full
+    fields; --dump-outputs writes the last timed step's outputs: the images and radii equal a render of that step's view."""
+    import numpy as np
+    import bench
+    from scgaussian_amd import rasterizer as R
+    steps, warmup = 7, 2
+    out = tmp_path / "dump"
+    res, line = _run_bench(["--gpus", "1", "--workload", "S1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--dump-outputs", str(out)], timeout=300)
+    assert res.returncode == 0, res.stderr[-3000:]
+    assert line["metric"] == "train_iters_per_sec" and line["unit"] == "iters/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["steps"] == steps and line["full"] is False
+    assert abs(line["value"] * line["ms_per_step"] - 1e3) < 1.0                     # one step = 1000 / value ms
+    assert not {"stage_ms", "sustained", "roofline", "value_blocks", "cpu_baseline", "s3_forward"} & set(line)
+
+    w = syn.WORKLOADS["S1"]
+    P, W, H = w["P"], w["width"], w["height"]
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= bench.DUMP_BUDGET_BYTES
+    assert {n: got[n].shape for n in ("color", "depth", "alpha", "radii", "grad_means2D", "grad_means3D", "grad_shs",
+                                      "grad_opacities", "grad_scales", "grad_rotations")} == {
+        "color": (3, H, W), "depth": (1, H, W), "alpha": (1, H, W), "radii": (P,), "grad_means2D": (P, 3),
+        "grad_means3D": (P, 3), "grad_shs": (P, 16, 3), "grad_opacities": (P, 1), "grad_scales": (P, 3),
+        "grad_rotations": (P, 4)}
+    assert all(np.isfinite(a).all() for a in got.values())
+
+    dev = torch.device("cuda", 0)
+    sc = syn.make_scene(P, W, H, seed=0).to(dev)
+    ps = [t.requires_grad_(True) for t in (sc.means3D, sc.shs, sc.opacities, sc.scales, sc.rotations)]
+    cam = bench.make_views(W, H)[(warmup + steps - 1) % bench.N_VIEWS]       # the view of the last timed step
+    rast = R.GaussianRasterizer(bench.settings_for(cam, 3, torch.zeros(3, device=dev), dev))
+    c, radii, d, a = rast(means3D=ps[0], means2D=torch.zeros_like(ps[0], requires_grad=True), opacities=ps[2], shs=ps[1],
+                          scales=ps[3], rotations=ps[4])
+    assert np.array_equal(got["radii"], radii.float().cpu().numpy())
+    for name, t in (("color", c), ("depth", d), ("alpha", a)):
+        np.testing.assert_allclose(got[name], t.detach().cpu().numpy(), rtol=1e-5, atol=1e-6, err_msg=name)
 
 
 def test_bench_refuses_an_rccl_launch_it_cannot_place_and_a_world_size_that_disagrees():

@@ -5,6 +5,7 @@
 #  kernels carry the same names and would be averaged into the headline workload's counters; the SH degrees the reference trains at
 #  get passes of their own: tools/pmc.sh <tag>/pmc_deg0 --sh-degree 0 --no-s3, summarised as S2_deg0 by pmc_summary.py ...@deg0)
 name=$1; shift
+set -- --full "$@"      # per-stage passes and the S3 render leg are bench.py --full legs
 R=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $R/gpurun_out/$name
 cd /tmp && export TMPDIR=/tmp

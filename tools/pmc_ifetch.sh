@@ -2,6 +2,7 @@
 # Extra PMC pass: instruction-fetch, branch, scalar-pipe and LDS-queue counters of the blend kernels (profiling aid).
 # Usage: tools/pmc_ifetch.sh <outdir-name> [bench args...]
 name=$1; shift
+set -- --full "$@"      # per-stage passes and the S3 render leg are bench.py --full legs
 R=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $R/gpurun_out/$name
 cd /tmp && export TMPDIR=/tmp
