@@ -4,8 +4,10 @@ raw parameterisation (ray-bound + background sets, logits, log-scales, un-normal
 scene/gaussian_model.py:452-509) rendered by `scgaussian_amd.render.render` (the model path: no getters, raw-parameter gradients in
 one arena), loss 0.8 L1 + 0.2 (1 - SSIM) (train.py:160-161, the fused kernels), and one CAPTURED step per training view
 (`graph_step.CapturedStep`: forward + loss + backward in a hipGraph; the optimizer steps outside it, in place).
+With --arena-adam the whole iteration is in the graph: forward + loss + backward + `optim.ArenaAdam.step()` (one launch for all
+parameters) + `optim.densification_stats` (the reference's max_radii2D / xyz_gradient_accum / denom update, train.py:191-192).
 
-    python examples/fit_captured.py [--iters 600] [--gaussians 10000] [--eager | --optimizer-in-graph]
+    python examples/fit_captured.py [--iters 600] [--gaussians 10000] [--eager | --optimizer-in-graph | --arena-adam]
 
 Prints loss / PSNR every 100 iterations and the time per iteration.  tests/test_gpu_graph_step.py runs a short form of both modes
 and holds their trajectories against each other."""
@@ -18,7 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import scgaussian_amd                                                                       # noqa: E402
-from scgaussian_amd import losses, synthetic as syn                                         # noqa: E402
+from scgaussian_amd import losses, optim, synthetic as syn                                  # noqa: E402
 from scgaussian_amd.graph_step import CapturedStep                                          # noqa: E402
 from scgaussian_amd.render import PipelineParams, render                                    # noqa: E402
 
@@ -27,8 +29,12 @@ def psnr(a, b):
     return float(-10.0 * torch.log10(((a - b) ** 2).mean()))
 
 
-def fit(iters=600, P=10_000, W=256, H=256, seed=0, captured=True, verbose=True, dev="cuda", optimizer_in_graph=False):
+def fit(iters=600, P=10_000, W=256, H=256, seed=0, captured=True, verbose=True, dev="cuda", optimizer_in_graph=False,
+        arena_adam=False):
+    """arena_adam: ArenaAdam + the densification statistics inside the captured step (implies optimizer_in_graph); the
+    statistics of the run are left in `fit.densification` = (max_radii2D, xyz_gradient_accum, denom)."""
     scgaussian_amd.single_gpu_host_setup()
+    optimizer_in_graph = optimizer_in_graph or arena_adam
     dev = torch.device(dev)
     gt = syn.make_scene(P, W, H, seed=seed, log_scale_mean=-3.3)
     truth = syn.make_raw_model(gt).to(dev)
@@ -59,10 +65,17 @@ def fit(iters=600, P=10_000, W=256, H=256, seed=0, captured=True, verbose=True, 
             groups.append({"params": [p], "lr": 1e-3})
         else:
             groups.append({"params": [p], "lr": 2e-3 if p is model.bg_xyz else 5e-3})
-    try:
-        opt = torch.optim.Adam(groups, eps=1e-15, fused=True, capturable=optimizer_in_graph)
-    except (RuntimeError, TypeError):
-        opt = torch.optim.Adam(groups, eps=1e-15, capturable=optimizer_in_graph)
+    if arena_adam:
+        opt = optim.ArenaAdam(groups, eps=1e-15)
+    else:
+        try:
+            opt = torch.optim.Adam(groups, eps=1e-15, fused=True, capturable=optimizer_in_graph)
+        except (RuntimeError, TypeError):
+            opt = torch.optim.Adam(groups, eps=1e-15, capturable=optimizer_in_graph)
+    P_all = model.zval.shape[0] + model.bg_xyz.shape[0]
+    max_radii2D = torch.zeros(P_all, device=dev)
+    xyz_gradient_accum = torch.zeros(P_all, 1, device=dev)
+    denom = torch.zeros(P_all, 1, device=dev)
     if optimizer_in_graph:
         # The optimizer steps INSIDE the captured graph (torch's capturable Adam: its step counters live on the device).  Its state
         # must exist before the capture (created inside it, the state would be re-zeroed by every replay): one step on zero
@@ -74,12 +87,16 @@ def fit(iters=600, P=10_000, W=256, H=256, seed=0, captured=True, verbose=True, 
             st["step"].zero_()
         for p in params:
             p.grad = None
+        if arena_adam:
+            opt.sync_hyperparameters()                           # the captured step reads its learning rates from the device
 
     def step_fn(v):
         def fn():
             pkg = render(cams[v], model, pipe, bg)
             loss = losses.image_loss(pkg["render"], targets[v], 0.2)
             loss.backward()
+            if arena_adam:
+                optim.densification_stats(max_radii2D, xyz_gradient_accum, denom, pkg["viewspace_points"].grad, pkg["radii"])
             return loss, pkg["radii"]
         return fn
     fns = [step_fn(v) for v in range(len(cams))]
@@ -123,10 +140,12 @@ def fit(iters=600, P=10_000, W=256, H=256, seed=0, captured=True, verbose=True, 
     if verbose:
         extra = "" if not captured else f"  ({sum(s.overflows for s in steps)} overflows, {sum(s.recaptures for s in steps)} recaptures)"
         mode = ("captured, optimizer inside the graph" if optimizer_in_graph else "captured") if captured else "eager"
+        mode += ", ArenaAdam + densification stats" if arena_adam else ""
         print(f"{mode}: {dt * 1e3:.4f} ms per iteration incl. the optimizer and the PSNR probes{extra}")
     if captured:
         for s in steps:
             s.close()
+    fit.densification = (max_radii2D, xyz_gradient_accum, denom)
     return history, dt
 
 
@@ -136,5 +155,6 @@ if __name__ == "__main__":
     ap.add_argument("--gaussians", type=int, default=10_000)
     ap.add_argument("--eager", action="store_true")
     ap.add_argument("--optimizer-in-graph", action="store_true", help="capturable Adam stepping inside the captured graph")
+    ap.add_argument("--arena-adam", action="store_true", help="ArenaAdam + densification statistics inside the captured graph")
     a = ap.parse_args()
-    fit(a.iters, a.gaussians, captured=not a.eager, optimizer_in_graph=a.optimizer_in_graph)
+    fit(a.iters, a.gaussians, captured=not a.eager, optimizer_in_graph=a.optimizer_in_graph, arena_adam=a.arena_adam)

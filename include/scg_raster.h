@@ -128,7 +128,8 @@ SCG_API const char* scg_last_error(void);
 SCG_API int32_t scg_abi_version(void);
 /* sizeof(ScgFrame) / sizeof(ScgWorkspaceLayout) / sizeof(ScgStageEvents) as this library was compiled: a binding that
  * declares the structs itself (ctypes, cgo, JNA) compares them with its own before the first call. */
-SCG_API size_t scg_struct_bytes(int32_t which /* 0 ScgFrame, 1 ScgWorkspaceLayout, 2 ScgStageEvents, 3 ScgModel, 4 ScgModelGrads */);
+SCG_API size_t scg_struct_bytes(int32_t which /* 0 ScgFrame, 1 ScgWorkspaceLayout, 2 ScgStageEvents, 3 ScgModel, 4 ScgModelGrads,
+                                                 5 ScgAdamSegment */);
 
 /* ---- stage 1: per-Gaussian geometry (replaces the preprocess step of upstream rasterize_gaussians;
  *      inputs as passed at reference gaussian_renderer/__init__.py:100-108) ---------------------------
@@ -432,6 +433,50 @@ SCG_API int scg_backward_model(const ScgFrame* frame, const ScgModel* model,
                                float* dsplats, int32_t dsplats_prezeroed,
                                const ScgModelGrads* grads, float* dL_dmeans2D,
                                int32_t flags /* SCG_BACKWARD_* */, const ScgStageEvents* stage_events, void* stream);
+
+/* ---- The training loop's gradient consumers (csrc/optim.hip) ---------------------------------------------------------------
+ * The optimizer step (reference train.py:203-208: two torch.optim.Adam, gaussian_model.py:486-515) and the densification
+ * statistics (train.py:191-192, gaussian_model.py:932-934), one launch each.  Additive to ABI 10. */
+
+#define SCG_ADAM_MAX_SEGMENTS 16
+#define SCG_ADAM_FORCE_FULL 1      /* ScgAdamSegment.flags: treat every column of a row segment as live (see `live` below) */
+
+/* One parameter tensor of one Adam step: torch's single-tensor Adam with weight_decay = 0, amsgrad = maximize = False, in torch's
+ * order of operations (m = lerp(m, g, 1-b1); v = b2 v + (1-b2) g g; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)).  All tensors
+ * are fp32, contiguous, `numel` elements; they are streamed as float4 when all four are 16-byte aligned.  `step` is ONE device
+ * float (torch's state['step']): every workgroup reads s and uses s+1, bc1 = 1 - b1^(s+1), bc2 = 1 - b2^(s+1) in double, and
+ * the launch leaves s+1 in it.  The hyper-parameters are doubles, as torch's Python floats are.
+ * row_len > 0 (features_rest: 45 floats per Gaussian) turns on the SH-tail skip: the launch keeps a watermark `live` per segment
+ * with the invariant "in every row, m and v are exact zeros at every column >= live".  Such an element is read as g alone and
+ * left untouched when g == 0 (torch's update of it is an exact no-op); otherwise it is updated from m = v = 0.  The launch
+ * re-derives the watermark from what it wrote (largest column with m or v != 0, + 1).  A caller that cannot vouch for the
+ * invariant (the moments were replaced or edited since the previous step) sets SCG_ADAM_FORCE_FULL. */
+typedef struct ScgAdamSegment {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    float* step;                  /* device, 1 float */
+    int64_t numel;
+    int32_t row_len;              /* 0: no tail skip */
+    int32_t flags;                /* SCG_ADAM_FORCE_FULL */
+    double lr, beta1, beta2, eps;
+} ScgAdamSegment;                 /* scg_struct_bytes(5) */
+
+/* Bytes of the workspace of scg_adam_step: a ticket word and the watermarks of SCG_ADAM_MAX_SEGMENTS segment slots (segment i of
+ * a call uses slot i).  The caller zeroes it ONCE when it allocates it and keeps it for all later steps of the same optimizer
+ * (the last workgroup of every launch leaves the ticket at zero).  0 for nseg outside 1..SCG_ADAM_MAX_SEGMENTS. */
+SCG_API size_t scg_adam_workspace_bytes(int32_t nseg);
+/* One launch for all `nseg` segments (the table is passed by value in the kernel's arguments).  lr_table: NULL = each segment's
+ * `lr`; otherwise nseg device doubles read by the kernel at run time (a step captured in a graph takes its learning rates from
+ * there).  Two launches on one workspace must not overlap (one stream). */
+SCG_API int scg_adam_step(const ScgAdamSegment* segments, int32_t nseg, const double* lr_table, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* What reference train.py:191-192 + gaussian_model.py:932-934 do with one render's outputs, in place, for every i with
+ * radii[i] > 0: accum[i] += sqrt(gx^2 + gy^2) with (gx, gy) = means2D_grad[i * grad_row_stride + 0..1]; denom[i] += 1;
+ * max_radii2D[i] = max(max_radii2D[i], (float)radii[i]).  accum, denom, max_radii2D: P floats each. */
+SCG_API int scg_densify_stats(int32_t P, const int32_t* radii, const float* means2D_grad, int64_t grad_row_stride,
+                              float* accum, float* denom, float* max_radii2D, void* stream);
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,17 @@ class ScgModelGrads(C.Structure):
     _fields_ = [("ray", ScgModelGradSet), ("bg", ScgModelGradSet)]
 
 
+ADAM_MAX_SEGMENTS = 16
+ADAM_FORCE_FULL = 1
+
+
+class ScgAdamSegment(C.Structure):
+    """One parameter tensor of an scg_adam_step launch (include/scg_raster.h ScgAdamSegment)."""
+    _fields_ = [(n, C.c_void_p) for n in ("param", "grad", "exp_avg", "exp_avg_sq", "step")] + [
+        ("numel", C.c_int64), ("row_len", C.c_int32), ("flags", C.c_int32),
+        ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/scg_raster.h
 _P = C.c_void_p
 SYMBOLS = {
@@ -96,6 +107,9 @@ SYMBOLS = {
     "scg_forward_model": (C.c_int, [C.POINTER(ScgFrame), C.POINTER(ScgModel), C.c_int64, _P, C.c_size_t] + [_P] * 4 + [_P, _P, _P, C.c_int32, _P, _P]),
     "scg_backward_model": (C.c_int, [C.POINTER(ScgFrame), C.POINTER(ScgModel), _P, C.c_int64, _P] + [_P] * 3 + [_P, C.c_int32]
                            + [C.POINTER(ScgModelGrads), _P, C.c_int32, _P, _P]),
+    "scg_adam_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "scg_adam_step": (C.c_int, [C.POINTER(ScgAdamSegment), C.c_int32, _P, _P, C.c_size_t, _P]),
+    "scg_densify_stats": (C.c_int, [C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -124,7 +138,7 @@ def open_library(path: str) -> C.CDLL:
         fn.argtypes = args
     if lib.scg_abi_version() != ABI_VERSION:
         raise ScgError(f"ABI version mismatch: library {lib.scg_abi_version()} != binding {ABI_VERSION}")
-    for which, struct in enumerate((ScgFrame, ScgWorkspaceLayout, ScgStageEvents, ScgModel, ScgModelGrads)):
+    for which, struct in enumerate((ScgFrame, ScgWorkspaceLayout, ScgStageEvents, ScgModel, ScgModelGrads, ScgAdamSegment)):
         if lib.scg_struct_bytes(which) != C.sizeof(struct):
             raise ScgError(f"struct layout mismatch: {struct.__name__} is {lib.scg_struct_bytes(which)} bytes in the library, "
                            f"{C.sizeof(struct)} in the binding")

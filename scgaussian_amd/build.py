@@ -4,6 +4,7 @@
 
 hipcc cross-compiles without a GPU.  The .so is git-ignored but travels to the GPU box with the
 gpurun snapshot.  geometry.hip is compiled with -ffp-contract=off (bit-exact tile assignment).
+optim.hip is too: Adam rounded where torch rounds it.
 """
 from __future__ import annotations
 
@@ -34,6 +35,7 @@ SOURCES = {
     "knn.hip": [],
     "loss.hip": [],
     "matchloss.hip": [],
+    "optim.hip": ["-ffp-contract=off"],           # Adam in torch's rounding order (no fused multiply-adds)
 }
 HEADERS = [os.path.join(CSRC, "scg_common.h"), os.path.join(CSRC, "tile_sort.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "scg_debug.h"), os.path.join(INCLUDE, "scg_raster.h"), os.path.join(INCLUDE, "scg_knn.h"), os.path.join(INCLUDE, "scg_loss.h"), os.path.join(INCLUDE, "scg_matchloss.h")]
 

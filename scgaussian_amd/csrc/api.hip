@@ -104,6 +104,7 @@ size_t scg_struct_bytes(int32_t which) {
         case 2: return sizeof(ScgStageEvents);
         case 3: return sizeof(ScgModel);
         case 4: return sizeof(ScgModelGrads);
+        case 5: return sizeof(ScgAdamSegment);
         default: return 0;
     }
 }
