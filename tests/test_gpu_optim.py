@@ -305,3 +305,81 @@ def test_densification_stats_match_the_reference():
     torch.cuda.synchronize()
     assert np.array_equal(den.cpu().numpy(), 2 * ref["densify_denom"])
     pu.assert_close(acc, 2 * ref["densify_accum"], "densify accum x2")
+
+
+# Densification statistics at the edges.  Reference: the reference's three statements (train.py:191-192, gaussian_model.py:932-934)
+#     max_radii2D[vis] = max(max_radii2D[vis], radii[vis]);  accum[vis] += norm(grad[vis, :2], dim=-1, keepdim=True);  denom[vis] += 1
+# with vis = radii > 0, evaluated in fp64 on the CPU and rounded to fp32.
+#   P        1, 255, 256, 257 (around the 256-thread workgroup), 100 003
+#   radii    positive, 0 and negative
+#   layout   (P,2), (P,3), a [:, :2] view of (P,4): row strides 2, 3, 4
+#   poison   NaN / Inf gradients in rows with radii <= 0 must not reach accum
+STATS_P = [1, 255, 256, 257, 100003]
+STATS_LAYOUTS = ["p2", "p3", "p4_view"]
+
+
+def _stats_inputs(P, layout, seed):
+    g = torch.Generator().manual_seed(seed)
+    radii = torch.randint(-3, 40, (P,), generator=g, dtype=torch.int32)
+    if P >= 3:
+        radii[0], radii[1], radii[-1] = 0, -1, 17                 # all three kinds present, the last row visible
+    else:
+        radii[:] = 5
+    cols = {"p2": 2, "p3": 3, "p4_view": 4}[layout]
+    grad = torch.randn(P, cols, generator=g) * 1e-3
+    hidden = radii <= 0
+    poison = torch.tensor([float("nan"), float("inf"), -float("inf")])
+    grad[hidden] = poison[torch.randint(0, 3, (int(hidden.sum()), cols), generator=g)]
+    acc = torch.rand(P, 1, generator=g) * 1e-2
+    den = torch.randint(0, 30, (P, 1), generator=g).float()
+    max_r = (torch.rand(P, generator=g) * 30).floor()
+    return radii, grad, acc, den, max_r
+
+
+def _stats_reference(radii, grad, acc, den, max_r):
+    vis = radii > 0
+    acc64, den64, max64 = acc.double().clone(), den.double().clone(), max_r.double().clone()
+    max64[vis] = torch.max(max64[vis], radii[vis].double())
+    acc64[vis] += torch.norm(grad.double()[vis, :2], dim=-1, keepdim=True)
+    den64[vis] += 1
+    return acc64.float(), den64.float(), max64.float()
+
+
+def _stats_run(radii, grad, acc, den, max_r, layout, no_grad=False, side_stream=False):
+    gd = grad.to(DEV)
+    gd = gd[:, :2] if layout == "p4_view" else gd
+    assert gd.stride(0) == {"p2": 2, "p3": 3, "p4_view": 4}[layout]
+    a, d, m, r = acc.to(DEV), den.to(DEV), max_r.to(DEV), radii.to(DEV)
+    torch.cuda.synchronize()
+    if side_stream:
+        st = torch.cuda.Stream()
+        with torch.cuda.stream(st):
+            O.densification_stats(m, a, d, gd, r)
+        st.synchronize()
+    elif no_grad:
+        with torch.no_grad():
+            O.densification_stats(m, a, d, gd, r)
+    else:
+        O.densification_stats(m, a, d, gd, r)
+    torch.cuda.synchronize()
+    return a.cpu(), d.cpu(), m.cpu()
+
+
+@pytest.mark.parametrize("layout", STATS_LAYOUTS)
+@pytest.mark.parametrize("P", STATS_P)
+def test_densification_stats_edges_against_fp64(P, layout):
+    inp = _stats_inputs(P, layout, seed=P + len(layout))
+    radii = inp[0]
+    want_a, want_d, want_m = _stats_reference(*inp)
+    a, d, m = _stats_run(*inp, layout)
+    assert torch.isfinite(a).all()                                # no poison from an invisible row
+    pu.assert_close(a, want_a, f"densify accum P={P} {layout}")
+    assert torch.equal(d, want_d) and torch.equal(m, want_m)
+    hidden = radii <= 0                                           # invisible rows are untouched, to the bit
+    assert torch.equal(a[hidden], inp[2][hidden]) and torch.equal(d[hidden], inp[3][hidden]) and torch.equal(m[hidden], inp[4][hidden])
+    if P >= 3:
+        assert bool(hidden.any()) and bool((radii < 0).any()) and bool((radii == 0).any())
+    # inside torch.no_grad() and on a side stream: the same numbers
+    for kw in (dict(no_grad=True), dict(side_stream=True)):
+        a2, d2, m2 = _stats_run(*inp, layout, **kw)
+        assert torch.equal(a2, a) and torch.equal(d2, d) and torch.equal(m2, m), kw
