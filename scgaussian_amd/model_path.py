@@ -19,14 +19,13 @@ contiguous span, which parallel.GradBucket all-reduces in place at every SH degr
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _grads, _lib
 from . import rasterizer as R
-from ._lib import ScgModel, ScgModelGrads, check, ptr
+from ._lib import ScgModel, ScgModelGrads, check
 
 # order of the operator's tensor arguments (behind means2D) = order of the gradients backward returns
 _RAY = ("zval", "rayo", "rayd", "features_dc", "features_rest", "opacity", "scaling", "rotation")
@@ -35,7 +34,6 @@ ARG_NAMES = _RAY + _BG
 # segments of the gradient arena: the two large SH tensors last (see the module docstring); rayo / rayd are constants
 _ARENA_ORDER = ("zval", "opacity", "scaling", "rotation", "features_dc", "bg_xyz", "bg_opacity", "bg_scaling", "bg_rotation",
                 "bg_features_dc", "features_rest", "bg_features_rest")
-_LAYOUTS = {}
 
 
 class _ModelArgs:
@@ -60,6 +58,15 @@ class _ModelArgs:
                 setattr(m.bg, f, t[n].data_ptr())
         self.c = m
         self.ref = C.byref(m)
+        # the gradient arena's segments (_grads.layout): the trainable tensors of the non-empty sets
+        self.grad_items = tuple((n, t[n].shape) for n in _ARENA_ORDER if t[n].shape[0])
+
+    def grad_outputs(self, into, d_means2D_out):
+        """What rasterizer._backward_view writes one view's gradients to: _grad_arena + the view's own dL/dmeans2D."""
+        out = dict(_grad_arena(self, into))
+        out["means2D"] = d_means2D_out if d_means2D_out is not None else \
+            torch.empty((self.P, 3), dtype=torch.float32, device=self.device)
+        return out
 
 
 def _usable(t: torch.Tensor, device, align16: bool) -> bool:
@@ -159,38 +166,20 @@ def model_for(pc, settings=None) -> Optional[_ModelArgs]:
 
 
 def _grad_arena(model: _ModelArgs, into):
-    """{name: gradient tensor} for the trainable tensors of the non-empty sets, all views of ONE flat arena (pooled: see
-    rasterizer._take_arena), + "_pooled" and "_c" (the ScgModelGrads struct).  `into`: an earlier call's result — reused."""
+    """{name: gradient tensor} for the trainable tensors of the non-empty sets, all views of ONE flat arena (pooled: _grads.py),
+    + "_pooled" and "_c" (the ScgModelGrads struct).  `into`: an earlier call's result — reused."""
     if into is not None:
         return into
-    key = (model.n_ray, model.n_bg)
-    lay = _LAYOUTS.get(key)
-    if lay is None:
-        if len(_LAYOUTS) > 64:
-            _LAYOUTS.clear()
-        names, sizes, shapes = [], [], []
-        by_name = dict(zip(ARG_NAMES, model.tensors))
-        for n in _ARENA_ORDER:
-            t = by_name[n]
-            if t.shape[0] == 0:
-                continue
-            names.append(n)
-            sizes.append((t.numel() + 3) // 4 * 4)               # 16-byte aligned segments
-            shapes.append(tuple(t.shape))
-        lay = _LAYOUTS[key] = (tuple(names), sizes, tuple(shapes), max(sum(sizes), 4))
-    names, sizes, shapes, total = lay
-    dev = model.device
-    arena, pooled = R._take_arena(("model", key, dev.index), total, dev)
-    out = {"_pooled": pooled}
-    views = arena.split_with_sizes(sizes) if total == sum(sizes) else arena[: sum(sizes)].split_with_sizes(sizes)
-    for n, v, shp, sz in zip(names, views, shapes, sizes):
-        out[n] = (v if sz == math.prod(shp) else v[:math.prod(shp)]).view(shp)
+    lay = _grads.layout(model.grad_items)
+    arena, pooled = _grads._take_arena("model", lay, lay[3], model.device, R.ARENA_POOL)
+    out = _grads.carve(arena, lay)
+    out["_pooled"] = pooled
     # the struct of raw pointers: a pooled arena's segments stay where they are — built once per arena
-    g = getattr(pooled, "cstruct", None) if pooled is not None else None
+    g = pooled.cstruct if pooled is not None else None
     if g is None:
         g = ScgModelGrads()
         base, off = arena.data_ptr(), 0
-        for n, sz in zip(names, sizes):
+        for n, sz in zip(lay[0], lay[1]):
             if n.startswith("bg_"):
                 setattr(g.bg, n[3:], base + 4 * off)
             else:
@@ -204,41 +193,10 @@ def _grad_arena(model: _ModelArgs, into):
 
 def backward_fused_model(model: _ModelArgs, radii, state, dL_dcolor, dL_ddepth, dL_dalpha, timer=None, into=None,
                          d_means2D_out=None):
-    """Stages 4-5 of the model path in one library call (scg_backward_model).  Returns {argument name: gradient} (views of one
-    arena) + "means2D"; `into` as in rasterizer.backward_fused (the kernel adds to an earlier view's gradients)."""
-    lib = _lib.load()
-    if not state.get("has_backward_state", True):
-        raise _lib.ScgError("this forward ran without backward state (SCG_FORWARD_NO_BACKWARD_STATE): it cannot be differentiated")
-    dev = model.device
-    fr = state["frame"]
-    if fr.hints is not None and fr.hints.bcost is not None:
-        fr.hints.bwritten = True
-    H, W = fr.H, fr.W
-    dL_dcolor = R._f32c(dL_dcolor, dev)
-    if dL_dcolor is None:
-        dL_dcolor = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
-    dL_ddepth = R._f32c(dL_ddepth, dev)
-    dL_dalpha = R._f32c(dL_dalpha, dev)
-    timer = timer or R._ACTIVE_TIMER
-    with R._on_device(dev):
-        stage_ev = timer.stage_events("backward") if isinstance(timer, R.StageTimer) else None
-        stream = R._stream(dev)
-        dsplats = state.get("dsplats_zeroed")
-        state["dsplats_zeroed"] = None
-        prezeroed = dsplats is not None
-        keep = None
-        if dsplats is None:
-            keep = torch.empty((model.P, R.DSPLAT_FLOATS), dtype=torch.float32, device=dev)
-            dsplats = keep.data_ptr()
-        out = _grad_arena(model, into)
-        d_means2D = d_means2D_out if d_means2D_out is not None else torch.empty((model.P, 3), dtype=torch.float32, device=dev)
-        flags = 1 if into is not None else R._sh_tail_promise(out.get("_pooled"), (fr.c.sh_degree + 1) ** 2)
-        check(lib.scg_backward_model(fr.ref, model.ref, radii.data_ptr(), state["cap"], state["ws"].data_ptr(),
-                                     dL_dcolor.data_ptr(), ptr(dL_ddepth), ptr(dL_dalpha), dsplats, int(prezeroed),
-                                     C.byref(out["_c"]), d_means2D.data_ptr(), flags, stage_ev, stream), "scg_backward_model")
-    out = dict(out)
-    out["means2D"] = d_means2D
-    return out
+    """Stages 4-5 of the model path in one library call (scg_backward_model, rasterizer._backward_view).  Returns {argument name:
+    gradient} (views of one arena) + "means2D"; `into` as in rasterizer.backward_fused (the kernel adds to an earlier view's
+    gradients)."""
+    return R._backward_view(state, model, radii, dL_dcolor, dL_ddepth, dL_dalpha, timer, into, d_means2D_out)
 
 
 class _RasterizeModel(torch.autograd.Function):
@@ -248,12 +206,7 @@ class _RasterizeModel(torch.autograd.Function):
         if model is None:
             model = _ModelArgs(dict(zip(ARG_NAMES, tensors)))
         needs_grad = any(ctx.needs_input_grad)
-        fused = R.forward_fused(raster_settings, None, None, None, None, None, None, None, needs_grad, model=model)
-        if fused is None:
-            raise _lib.ScgError("the model path needs the tile-first binning (scg_binning_accepts_bound): check "
-                                "model_path.supported(tensors, settings) first and render through the getters otherwise")
-        color, radii, depth, alpha, state = fused
-        state.pop("inputs")
+        color, radii, depth, alpha, _, state = R._forward_view(raster_settings, model, needs_grad)
         ctx.model = model
         ctx.fused_state = state
         ctx.raster_settings = raster_settings
@@ -266,7 +219,7 @@ class _RasterizeModel(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha):
         saved = ctx.saved_tensors                                # raises if a parameter was modified in place since forward
-        g = backward_fused_model(ctx.model, saved[-1], ctx.fused_state, grad_color, grad_depth, grad_alpha)
+        g = R._backward_view(ctx.fused_state, ctx.model, saved[-1], grad_color, grad_depth, grad_alpha)
         return (g["means2D"],) + tuple(g.get(n) for n in ARG_NAMES) + (None, None)
 
 
@@ -295,11 +248,7 @@ class _RasterizeModelViews(torch.autograd.Function):
         needs_grad = any(ctx.needs_input_grad)
         outs, states = [], []
         for st_ in settings_list:
-            fused = R.forward_fused(st_, None, None, None, None, None, None, None, needs_grad, model=model)
-            if fused is None:
-                raise _lib.ScgError("the model path needs the tile-first binning (scg_binning_accepts_bound) for every view")
-            color, radii, depth, alpha, state = fused
-            state.pop("inputs")
+            color, radii, depth, alpha, _, state = R._forward_view(st_, model, needs_grad)
             states.append(state)
             outs += [color, radii, depth, alpha]
         ctx.model, ctx.states, ctx.K = model, states, len(settings_list)
@@ -321,8 +270,8 @@ class _RasterizeModelViews(torch.autograd.Function):
             if g_color is None and g_depth is None and g_alpha is None:
                 d_means2D[k].zero_()
                 continue                                         # this view's outputs did not reach the loss
-            acc = backward_fused_model(model, radii_all[k], ctx.states[k], g_color, g_depth, g_alpha, into=acc,
-                                       d_means2D_out=d_means2D[k])
+            acc = R._backward_view(ctx.states[k], model, radii_all[k], g_color, g_depth, g_alpha, into=acc,
+                                   d_means2D_out=d_means2D[k])
         if acc is None:
             return (None,) * (len(ARG_NAMES) + 3)
         return (d_means2D,) + tuple(acc.get(n) for n in ARG_NAMES) + (None, None)

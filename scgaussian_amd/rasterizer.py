@@ -24,7 +24,6 @@ as it does with the reference's operator.
 from __future__ import annotations
 
 import contextlib
-import math
 import os
 import ctypes as C
 import threading
@@ -695,161 +694,98 @@ class _LazyViews(dict):
         return v
 
 
-# Order of the segments in the gradient arena.  The SH gradients come LAST of the usual five: the other four (11 floats per
-# Gaussian) are then one contiguous span, which parallel.GradBucket all-reduces in place when only the active SH coefficients
-# of a degree-limited step are exchanged (round 5).
-_GRAD_ORDER = ("means3D", "opacities", "scales", "rotations", "shs", "colors_precomp", "cov3D_precomp")
-_GRAD_INDEX = (0, 1, 4, 5, 2, 3, 6)            # position of each of those in the `inputs` 7-tuple
-_GRAD_LAYOUTS = {}
+# The gradient arena a backward writes into (segment layout, the pool that keeps arenas from step to step, the promise a kept
+# arena carries about its SH gradients): _grads.py.  _sh_tail_promise is the DECISION about that promise: the backward of both
+# paths looks it up here at call time (tests spy on it).
+from . import _grads                                                                                   # noqa: E402
+from ._grads import _GRAD_ORDER, _grad_outputs, _take_arena, grad_arena, sh_tail_flag as _sh_tail_promise      # noqa: E402,F401
+
+ARENA_POOL = True                        # module switch (tests / A-B runs): keep gradient arenas from step to step (_grads.py)
 
 
-# ---- gradient arenas that are KEPT from step to step ------------------------------------------------------------------------
-# A backward writes every parameter gradient into one flat fp32 arena and autograd keeps views of it as the .grad tensors.  The
-# arenas of a layout are pooled: one is handed out again once nobody outside the pool references its storage any more (the
-# previous step's .grad tensors are gone: optimizer.zero_grad(set_to_none=True), p.grad = None).  What that buys (round 6): the
-# arena REMEMBERS that its SH-coefficient gradients above the active degree hold zeros — written by the kernel the first time —
-# and the next backward is told to leave them alone (SCG_BACKWARD_SH_TAIL_ZERO): at degree 0 the geometry backward stores 12
-# instead of 192 bytes of SH gradient per Gaussian (the reference trains 1 000 iterations at degree 0 and 1 000 at degree 1,
-# train.py:129).  The promise holds while (a) nobody but the pool and this step's autograd references the storage and (b) no
-# torch operation wrote through any view of it since (the views share the arena's version counter: zero_grad(set_to_none=False),
-# an in-place all-reduce or clip bump it) — otherwise the kernel writes the zeros again.
-ARENA_POOL = True                        # module switch (tests / A-B runs)
-_ARENA_POOLS = {}                        # layout key -> [ _PooledArena ]
-_ARENA_POOL_DEPTH = 3                    # arenas kept per layout (a step holds one; gradient accumulation over two steps: two)
-_use_count = getattr(torch._C, "_storage_Use_Count", None)
-
-
-class _PooledArena:
-    __slots__ = ("arena", "storage", "version", "zero_from", "cstruct")
-
-    def __init__(self, total, dev):
-        self.arena = torch.empty((total,), dtype=torch.float32, device=dev)
-        self.storage = self.arena.untyped_storage()
-        self.version = -1
-        self.zero_from = None            # SH coefficients >= this index hold zeros (None: unknown)
-        self.cstruct = None              # model_path: the ScgModelGrads struct of this arena's segments
-
-    def free(self) -> bool:
-        return _use_count(self.storage._cdata) == 2          # the arena tensor and the wrapper above, nobody else
-
-
-def _take_arena(key, total, dev):
-    """(arena tensor, pooled record or None).  Not pooled: no use-count query in this torch, the switch is off, or a stream
-    capture is in progress (a captured step's buffers belong to its graph's memory pool and are replayed in place)."""
-    if not ARENA_POOL or _use_count is None or (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):
-        return torch.empty((total,), dtype=torch.float32, device=dev), None
-    pool = _ARENA_POOLS.get(key)
-    if pool is None:
-        if len(_ARENA_POOLS) > 32:
-            _ARENA_POOLS.clear()
-        pool = _ARENA_POOLS[key] = []
-    for pa in pool:
-        if pa.free():
-            return pa.arena, pa
-    pa = _PooledArena(total, dev)
-    if len(pool) < _ARENA_POOL_DEPTH:
-        pool.append(pa)
-    return pa.arena, pa
-
-
-def _sh_tail_promise(pa, n_active: int) -> int:
-    """SCG_BACKWARD_SH_TAIL_ZERO (2) when the pooled arena is known to hold zeros in every SH coefficient >= n_active; records
-    what this backward leaves behind (called once per backward, before the launch)."""
-    if pa is None:
-        return 0
-    ok = pa.zero_from is not None and pa.zero_from <= n_active and pa.version == pa.arena._version
-    pa.zero_from = n_active              # after this backward: written below n_active, zeros (kept or written) from there on
-    pa.version = pa.arena._version
-    return 2 if ok else 0
-
-
-
-def _grad_outputs(inputs, into, d_means2D_out, dev):
-    """Output tensors of a backward: every parameter gradient a view of ONE flat fp32 arena (16-byte aligned segments;
-    data-parallel training all-reduces the arena in place instead of packing / unpacking a bucket, parallel.GradBucket) —
-    or, when `into` is the result of an earlier backward over the same inputs, those very tensors (the kernel then ADDS
-    to them: views-per-step accumulation).  dL/dmeans2D belongs to the view: always a tensor of its own."""
-    d_means2D = d_means2D_out if d_means2D_out is not None else torch.empty_like(inputs[0])
-    if into is not None:
-        out = dict(into)
-        out["means2D"] = d_means2D
-        return out
-    # the layout (segment sizes, shapes) depends on the inputs' shapes only: looked up, not rebuilt per step
-    key = tuple(None if t is None else t.shape for t in inputs)
-    lay = _GRAD_LAYOUTS.get(key)
-    if lay is None:
-        if len(_GRAD_LAYOUTS) > 64:
-            _GRAD_LAYOUTS.clear()
-        names, sizes, shapes, exact = [], [], [], []
-        for n, i in zip(_GRAD_ORDER, _GRAD_INDEX):
-            t = inputs[i]
-            if t is not None:
-                names.append(n)
-                sizes.append((t.numel() + 3) // 4 * 4)
-                shapes.append(tuple(t.shape))
-                exact.append(sizes[-1] == t.numel())
-        lay = _GRAD_LAYOUTS[key] = (tuple(names), sizes, tuple(shapes), tuple(exact), max(sum(sizes), 4))
-    names, sizes, shapes, exact, total = lay
-    arena, pooled = _take_arena(("tensors", key, dev.index), total, dev)
-    out = dict.fromkeys(_GRAD_ORDER)
-    out["_pooled"] = pooled
-    if names:
-        for n, v, shp, ex in zip(names, arena.split_with_sizes(sizes) if total == sum(sizes) else
-                                 arena[: sum(sizes)].split_with_sizes(sizes), shapes, exact):
-            out[n] = (v if ex else v[: math.prod(shp)]).view(shp)
-    out["means2D"] = d_means2D
+def _backward_view(state, inputs, radii, dL_dcolor, dL_ddepth, dL_dalpha, timer: Optional[Callable] = None, into=None,
+                   d_means2D_out=None, want_dsplats: bool = False):
+    """One view's backward (stages 4-5) on the path its forward took, which `state` tells: a forward_stages result ("ptrs":
+    scg_blend_backward + scg_geometry_backward), a forward_fused state (scg_backward) or, with `inputs` a model_path._ModelArgs
+    in place of the 7-tuple of contiguous fp32 input tensors, the model path's (scg_backward_model).  Returns {name: gradient}
+    — views of one flat arena, _grads.py — + "means2D".  `into`: the dict an earlier view's call returned for the same inputs:
+    this view's parameter gradients are ADDED to it in the kernel.  `want_dsplats`: the gradient records as out["dsplats"] (the
+    staged path, where they are a tensor)."""
+    lib = _lib.load()
+    if not state.get("has_backward_state", True):
+        raise _lib.ScgError("this forward ran without backward state (prepare_backward=False -> scg_forward's "
+                            "SCG_FORWARD_NO_BACKWARD_STATE: final_T / n_contrib were not written): it cannot be differentiated")
+    model = None if isinstance(inputs, (tuple, list)) else inputs
+    dev, P = (inputs[0].device, inputs[0].shape[0]) if model is None else (model.device, model.P)
+    fr = state["frame"]
+    if fr.hints is not None and fr.hints.bcost is not None:
+        fr.hints.bwritten = True                             # (this backward records its quadrants' times: the next forward's hint)
+    dL_dcolor = _f32c(dL_dcolor, dev)
+    if dL_dcolor is None:
+        dL_dcolor = torch.zeros((3, fr.H, fr.W), dtype=torch.float32, device=dev)
+    dL_ddepth = _f32c(dL_ddepth, dev)
+    dL_dalpha = _f32c(dL_dalpha, dev)
+    timer = timer or _ACTIVE_TIMER
+    staged = "ptrs" in state
+    with _on_device(dev):
+        stage_ev = timer.stage_events("backward") if isinstance(timer, StageTimer) and not staged else None
+        stream = _stream(dev)
+        # the gradient records the forward blend cleared: usable once (a tensor on the staged path, a raw pointer into
+        # state["ws"] on the one-call paths); a second backward over one forward takes records of its own
+        dsplats = state.get("dsplats_zeroed")
+        state["dsplats_zeroed"] = None
+        prezeroed = dsplats is not None
+        if dsplats is None:
+            dsplats = torch.empty((P, DSPLAT_FLOATS), dtype=torch.float32, device=dev)
+        records = dsplats if isinstance(dsplats, int) else dsplats.data_ptr()
+        out = _grad_outputs(inputs, into, d_means2D_out, dev, ARENA_POOL) if model is None else \
+            model.grad_outputs(into, d_means2D_out)
+        # the pooled arena's promise about its SH tails: decided here, recorded once the library call has returned success
+        pa, n_active = out.get("_pooled"), (fr.c.sh_degree + 1) ** 2
+        flags = 1 if into is not None else _sh_tail_promise(pa, n_active)
+        try:
+            if model is not None:
+                check(lib.scg_backward_model(fr.ref, model.ref, radii.data_ptr(), state["cap"], state["ws"].data_ptr(),
+                                             dL_dcolor.data_ptr(), ptr(dL_ddepth), ptr(dL_dalpha), records, int(prezeroed),
+                                             C.byref(out["_c"]), out["means2D"].data_ptr(), flags, stage_ev, stream),
+                      "scg_backward_model")
+            else:
+                grads = (out["means3D"].data_ptr(), out["means2D"].data_ptr(), out["opacities"].data_ptr(), ptr(out["shs"]),
+                         ptr(out["colors_precomp"]), ptr(out["scales"]), ptr(out["rotations"]), ptr(out["cov3D_precomp"]))
+                in_ptrs = tuple(None if t is None else t.data_ptr() for t in inputs)
+                if staged:
+                    sp = state["ptrs"]
+                    with timer("blend_backward"):
+                        check(lib.scg_blend_backward(fr.ref, sp["ranges"], sp["point_list"], sp["splats"], sp["final_T"],
+                                                     sp["n_contrib"], ptr(dL_dcolor), ptr(dL_ddepth), ptr(dL_dalpha), records,
+                                                     int(prezeroed), stream), "scg_blend_backward")
+                    with timer("geometry_backward"):
+                        check(lib.scg_geometry_backward(fr.ref, *in_ptrs, radii.data_ptr(), sp["clamped"], records, *grads,
+                                                        flags, stream), "scg_geometry_backward")
+                else:
+                    check(lib.scg_backward(fr.ref, *in_ptrs, radii.data_ptr(), state["cap"], state["ws"].data_ptr(),
+                                           dL_dcolor.data_ptr(), ptr(dL_ddepth), ptr(dL_dalpha), records, int(prezeroed), *grads,
+                                           flags, stage_ev, stream), "scg_backward")
+        except BaseException:
+            _grads.invalidate_promise(pa)
+            raise
+        _grads.commit_promise(pa, n_active, into is not None)
+    if want_dsplats:
+        out["dsplats"] = dsplats
     return out
 
 
 def backward_stages(settings: GaussianRasterizationSettings, inputs, saved, dL_dcolor, dL_ddepth, dL_dalpha,
                     want_dsplats: bool = False, timer: Optional[Callable] = None, into=None, d_means2D_out=None):
-    """Blend backward + geometry backward through the C ABI.  `inputs` is the 7-tuple of contiguous fp32
+    """Blend backward + geometry backward through the C ABI (_backward_view).  `inputs` is the 7-tuple of contiguous fp32
     input tensors, `saved` the forward state: {"ptrs": raw device pointers of splats / clamped / point_list /
     ranges / final_T / n_contrib, "arenas": the allocations that own them, "radii": tensor} — a forward_stages
-    result can be passed as is.  `into`: the dict an earlier call returned for the same inputs — the parameter
-    gradients of this view are added to it in the kernel (scg_geometry_backward accumulate)."""
-    lib = _lib.load()
-    timer = timer or _ACTIVE_TIMER
-    means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp = inputs
-    dev = means3D.device
-    P = means3D.shape[0]
-    M = shs.shape[1] if shs is not None else 0
-    fr = saved.get("frame") if isinstance(saved, dict) else None
-    if fr is None:
-        fr = _frame_for(settings, P, M, dev)
-    if fr.hints is not None and fr.hints.bcost is not None:
-        fr.hints.bwritten = True
-    H, W = fr.H, fr.W
-    dL_dcolor = _f32c(dL_dcolor, dev)
-    if dL_dcolor is None:
-        dL_dcolor = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
-    dL_ddepth = _f32c(dL_ddepth, dev)
-    dL_dalpha = _f32c(dL_dalpha, dev)
-    with _on_device(dev):
-        stream = _stream(dev)
-        # the forward may have left a cleared gradient-record buffer behind (usable once)
-        dsplats = saved.pop("dsplats_zeroed", None) if isinstance(saved, dict) else None
-        prezeroed = dsplats is not None
-        if dsplats is None:
-            dsplats = torch.empty((P, DSPLAT_FLOATS), dtype=torch.float32, device=dev)
-        with timer("blend_backward"):
-            sp = saved["ptrs"]
-            check(lib.scg_blend_backward(fr.ref, sp["ranges"], sp["point_list"], sp["splats"], sp["final_T"],
-                                         sp["n_contrib"], ptr(dL_dcolor), ptr(dL_ddepth), ptr(dL_dalpha),
-                                         ptr(dsplats), int(prezeroed), stream), "scg_blend_backward")
-        out = _grad_outputs(inputs, into, d_means2D_out, dev)
-        flags = 1 if into is not None else _sh_tail_promise(out.get("_pooled"), (fr.c.sh_degree + 1) ** 2)
-        with timer("geometry_backward"):
-            check(lib.scg_geometry_backward(fr.ref, ptr(means3D), ptr(opacities), ptr(shs), ptr(colors_precomp),
-                                            ptr(scales), ptr(rotations), ptr(cov3D_precomp), ptr(saved["radii"]),
-                                            saved["ptrs"]["clamped"], ptr(dsplats), ptr(out["means3D"]),
-                                            ptr(out["means2D"]), ptr(out["opacities"]), ptr(out["shs"]),
-                                            ptr(out["colors_precomp"]), ptr(out["scales"]), ptr(out["rotations"]),
-                                            ptr(out["cov3D_precomp"]), flags, stream),
-                  "scg_geometry_backward")
-    if want_dsplats:
-        out["dsplats"] = dsplats
-    return out
+    result can be passed as is (its cleared gradient records are used up).  `into`, `want_dsplats`: see _backward_view."""
+    if saved.get("frame") is None:
+        shs = inputs[2]
+        saved["frame"] = _frame_for(settings, inputs[0].shape[0], shs.shape[1] if shs is not None else 0, inputs[0].device)
+    return _backward_view(saved, inputs, saved["radii"], dL_dcolor, dL_ddepth, dL_dalpha, timer, into, d_means2D_out,
+                          want_dsplats)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1065,70 +1001,28 @@ def forward_fused(settings: GaussianRasterizationSettings, means3D, opacities, s
 
 def backward_fused(inputs, radii, state, dL_dcolor, dL_ddepth, dL_dalpha, timer: Optional[Callable] = None, into=None,
                    d_means2D_out=None):
-    """Stages 4-5 in one library call; every parameter gradient is a view of ONE flat fp32 allocation (see
-    _grad_outputs).  Returns the same dict as backward_stages; `into` as there."""
-    lib = _lib.load()
-    if not state.get("has_backward_state", True):
-        raise _lib.ScgError("this forward ran without backward state (prepare_backward=False -> scg_forward's "
-                            "SCG_FORWARD_NO_BACKWARD_STATE: final_T / n_contrib were not written): it cannot be differentiated")
-    means3D = inputs[0]
-    dev = means3D.device
-    fr = state["frame"]
-    if fr.hints is not None and fr.hints.bcost is not None:
-        fr.hints.bwritten = True                             # (this backward records its quadrants' times: the next forward's hint)
-    H, W = fr.H, fr.W
-    dL_dcolor = _f32c(dL_dcolor, dev)
-    if dL_dcolor is None:
-        dL_dcolor = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
-    dL_ddepth = _f32c(dL_ddepth, dev)
-    dL_dalpha = _f32c(dL_dalpha, dev)
-    timer = timer or _ACTIVE_TIMER
-    with _on_device(dev):
-        stage_ev = timer.stage_events("backward") if isinstance(timer, StageTimer) else None
-        stream = _stream(dev)
-        dsplats = state.get("dsplats_zeroed")               # raw pointer into the forward's allocation (state["ws"])
-        state["dsplats_zeroed"] = None                      # usable once
-        prezeroed = dsplats is not None
-        keep = None
-        if dsplats is None:                                 # a second backward over one forward: records of its own
-            keep = torch.empty((means3D.shape[0], DSPLAT_FLOATS), dtype=torch.float32, device=dev)
-            dsplats = keep.data_ptr()
-        out = _grad_outputs(inputs, into, d_means2D_out, dev)
-        flags = 1 if into is not None else _sh_tail_promise(out.get("_pooled"), (fr.c.sh_degree + 1) ** 2)
-        check(lib.scg_backward(fr.ref, *(None if t is None else t.data_ptr() for t in inputs), radii.data_ptr(),
-                               state["cap"], state["ws"].data_ptr(), dL_dcolor.data_ptr(), ptr(dL_ddepth), ptr(dL_dalpha),
-                               dsplats, int(prezeroed), out["means3D"].data_ptr(), out["means2D"].data_ptr(),
-                               out["opacities"].data_ptr(), ptr(out["shs"]), ptr(out["colors_precomp"]), ptr(out["scales"]),
-                               ptr(out["rotations"]), ptr(out["cov3D_precomp"]), flags, stage_ev, stream),
-              "scg_backward")
-    return out
+    """Stages 4-5 over a forward_fused state in one library call (_backward_view); every parameter gradient is a view of ONE
+    flat fp32 allocation (_grads._grad_outputs).  Returns the same dict as backward_stages; `into` as there."""
+    return _backward_view(state, inputs, radii, dL_dcolor, dL_ddepth, dL_dalpha, timer, into, d_means2D_out)
 
 
-def grad_arena(params):
-    """The flat fp32 tensor that holds every `p.grad` of the latest rasterizer backward, when they all live in ONE
-    storage (backward_stages writes every parameter gradient into one allocation and autograd keeps those views as
-    `.grad` when it was None) and TILE a range of it; else None.  The range starts at the first of the given gradients
-    and ends behind the last: a subset of the parameters (only the opacities, say) yields only its own span, and a subset
-    with another parameter's gradient in between yields None — an all-reduce of the result never touches a gradient
-    that was not asked for.  Nothing is registered anywhere: the arena is rebuilt from the gradients' shared storage, so
-    it lives exactly as long as a gradient does."""
-    if not params or params[0].grad is None:
-        return None
-    st = params[0].grad.untyped_storage()
-    base = st.data_ptr()
-    begin, end, covered = None, 0, 0
-    for p in params:
-        g = p.grad
-        if g is None or g.dtype != torch.float32 or not g.is_contiguous() or g.untyped_storage().data_ptr() != base:
-            return None
-        off = g.storage_offset()
-        begin = off if begin is None else min(begin, off)
-        end = max(end, off + g.numel())
-        covered += g.numel()
-    # segments are padded to 16 bytes (<= 3 floats each): anything more between them is somebody else's memory
-    if end * 4 > st.nbytes() or (end - begin) - covered > 3 * len(params):
-        return None
-    return torch.empty((0,), dtype=torch.float32, device=params[0].grad.device).set_(st, begin, (end - begin,))
+def _forward_view(settings: GaussianRasterizationSettings, inputs, needs_grad: bool):
+    """One view's forward for the autograd Functions: the one-call path, else — on the tensor path — the staged one, which also
+    establishes the capacity.  `inputs`: the operator's (means3D, opacities, shs, colors_precomp, scales, rotations,
+    cov3D_precomp) or a model_path._ModelArgs.  Returns (color, radii, depth, alpha, the inputs as the kernels read them, the
+    state _backward_view takes)."""
+    model = None if isinstance(inputs, tuple) else inputs
+    fused = forward_fused(settings, *(inputs if model is None else (None,) * 7), needs_grad, model=model)
+    if fused is not None:
+        color, radii, depth, alpha, state = fused
+        return color, radii, depth, alpha, state.pop("inputs"), state
+    if model is not None:
+        raise _lib.ScgError("the model path needs the tile-first binning (scg_binning_accepts_bound): check "
+                            "model_path.supported(tensors, settings) first and render through the getters otherwise")
+    st = forward_stages(settings, *inputs, prepare_backward=needs_grad)
+    # raw pointers into the two arenas (kept alive by the reference to `arenas`)
+    state = {"ptrs": st["ptrs"], "arenas": st["arenas"], "dsplats_zeroed": st["dsplats_zeroed"], "frame": st["frame"]}
+    return st["color"], st["radii"], st["depth"], st["alpha"], st["inputs"], state
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -1137,20 +1031,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raster_settings):
         needs_grad = any(ctx.needs_input_grad)
         _require_cuda(means3D)
-        fused = forward_fused(raster_settings, means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp,
-                              needs_grad)
-        if fused is not None:
-            color, radii, depth, alpha, state = fused
-            inputs = state.pop("inputs")
-            ctx.fused_state = state
-        else:
-            st = forward_stages(raster_settings, means3D, opacities, sh, colors_precomp, scales, rotations,
-                                cov3Ds_precomp, prepare_backward=needs_grad)
-            color, radii, depth, alpha, inputs = st["color"], st["radii"], st["depth"], st["alpha"], st["inputs"]
-            ctx.fused_state = None
-            # raw pointers into the two arenas (kept alive by the reference to `arenas`)
-            ctx.saved_state = {"ptrs": st["ptrs"], "arenas": st["arenas"],
-                               "dsplats_zeroed": st["dsplats_zeroed"], "frame": st["frame"]}
+        color, radii, depth, alpha, inputs, ctx.state = _forward_view(
+            raster_settings, (means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp), needs_grad)
         ctx.raster_settings = raster_settings
         ctx.inputs_present = tuple(t is not None for t in inputs)
         ctx.shapes = (means3D.shape, means2D.shape, None if sh is None else sh.shape, opacities.shape)
@@ -1174,12 +1056,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         inputs = tuple(next(it) if present else None for present in ctx.inputs_present)
         radii = saved[-1]
         try:
-            if ctx.fused_state is not None:
-                g = backward_fused(inputs, radii, ctx.fused_state, grad_color, grad_depth, grad_alpha)
-            else:
-                state = dict(ctx.saved_state, radii=radii)
-                g = backward_stages(ctx.raster_settings, inputs, state, grad_color, grad_depth, grad_alpha)
-                ctx.saved_state["dsplats_zeroed"] = None     # usable once (a second backward memsets its own)
+            g = _backward_view(ctx.state, inputs, radii, grad_color, grad_depth, grad_alpha)
         except Exception:
             if ctx.raster_settings.debug:
                 names = ("means3D", "opacities", "shs", "colors_precomp", "scales", "rotations", "cov3D_precomp")
@@ -1282,19 +1159,10 @@ class _RasterizeViews(torch.autograd.Function):
         _require_cuda(means3D)
         outs, states, inputs = [], [], None
         for st_ in settings_list:
-            fused = forward_fused(st_, means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp, needs_grad)
-            if fused is not None:
-                color, radii, depth, alpha, state = fused
-                inputs = state.pop("inputs")
-                states.append(("fused", state))
-            else:
-                fs = forward_stages(st_, means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp,
-                                    prepare_backward=needs_grad)
-                color, radii, depth, alpha, inputs = fs["color"], fs["radii"], fs["depth"], fs["alpha"], fs["inputs"]
-                states.append(("staged", {"ptrs": fs["ptrs"], "arenas": fs["arenas"],
-                                          "dsplats_zeroed": fs["dsplats_zeroed"], "frame": fs["frame"]}))
+            color, radii, depth, alpha, inputs, state = _forward_view(
+                st_, (means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp), needs_grad)
+            states.append(state)
             outs += [color, radii, depth, alpha]
-        ctx.settings_list = tuple(settings_list)
         ctx.states = states
         ctx.inputs_present = tuple(t is not None for t in inputs)
         ctx.shapes = (means3D.shape, means2D.shape, None if sh is None else sh.shape, opacities.shape)
@@ -1306,7 +1174,7 @@ class _RasterizeViews(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        K = len(ctx.settings_list)
+        K = len(ctx.states)
         saved = ctx.saved_tensors
         it = iter(saved)
         inputs = tuple(next(it) if present else None for present in ctx.inputs_present)
@@ -1322,14 +1190,8 @@ class _RasterizeViews(torch.autograd.Function):
             if g_color is None and g_depth is None and g_alpha is None:
                 d_means2D[k].zero_()
                 continue                                             # this view's outputs did not reach the loss
-            kind, state = ctx.states[k]
-            if kind == "fused":
-                acc = backward_fused(inputs, radii_all[k], state, g_color, g_depth, g_alpha, into=acc,
-                                     d_means2D_out=d_means2D[k])
-            else:
-                acc = backward_stages(ctx.settings_list[k], inputs, dict(state, radii=radii_all[k]), g_color, g_depth,
-                                      g_alpha, into=acc, d_means2D_out=d_means2D[k])
-                state["dsplats_zeroed"] = None
+            acc = _backward_view(ctx.states[k], inputs, radii_all[k], g_color, g_depth, g_alpha, into=acc,
+                                 d_means2D_out=d_means2D[k])
         if acc is None:
             return (None,) * 9
 

@@ -244,3 +244,24 @@ def one_call_forward(st, scd):
                 point_list=words(plan.point_list, Rn, torch.int32).view(np.uint32),
                 ranges=words(plan.ranges, 2 * n_tiles, torch.int32).view(np.uint32).reshape(n_tiles, 2),
                 num_rendered=np.int64(Rn))
+
+
+def one_quadrant_scene(P, W, H, seed=0):
+    """syn.make_scene with every Gaussian's footprint inside ONE 8x8-pixel quadrant of syn.default_camera's W x H image (W, H
+    multiples of 8): centres on quadrant centres, projected sigma <= 0.7 px (log-scale mean -6 + the 0.3 px^2 low-pass filter), so
+    alpha falls below 1/255 within 2.3 px of the centre, 1.2 px short of the quadrant's edge.  The blend backward adds one
+    floating-point atomic per (Gaussian, quadrant) to the Gaussian's gradient record (DESIGN.md "Determinism"): with a single
+    contribution per record the sum has no order, and the gradients of such a scene are bit-reproducible run to run — what a
+    test needs that compares two runs with torch.equal."""
+    import math
+    from scgaussian_amd import synthetic as syn
+    assert W % 8 == 0 and H % 8 == 0
+    sc = syn.make_scene(P, W, H, seed=seed, log_scale_mean=-6.0)
+    g = torch.Generator().manual_seed(seed + 1)
+    qx, qy = torch.randint(0, W // 8, (P,), generator=g), torch.randint(0, H // 8, (P,), generator=g)
+    tany = math.tan(math.radians(50.0) / 2)
+    z = sc.means3D[:, 2]
+    # pixel 8 q + 3.5 in normalised device coordinates (pixel = ((ndc + 1) * size - 1) / 2)
+    sc.means3D[:, 0] = z * (tany * W / H) * ((16 * qx + 8) / W - 1)
+    sc.means3D[:, 1] = z * tany * ((16 * qy + 8) / H - 1)
+    return sc

@@ -265,6 +265,55 @@ def test_sh_tail_zero_promise_of_the_pooled_gradient_arena():
         assert float(leaves[1].grad[:, 1:].abs().max()) == 0 and float(leaves[1].grad[:, :1].abs().max()) > 0, it
 
 
+def test_model_views_of_mixed_sh_degree_leave_no_stale_tails_in_the_kept_gradient_arena():
+    """tests/test_gpu_views.py's test of the same name through rasterize_model_views: step A renders one camera at degree 0 then
+    1 (the second view ADDS non-zero features_rest gradients to the arena the first one wrote), step B both views at degree 0 on
+    that very arena: the kernel must be told to write the zeros again.
+
+    The last assertion compares step B with the pool on and off bit for bit: on pu.one_quadrant_scene, for the reason given
+    there (measured on make_scene's scene, pooled against unpooled: bg_xyz 3.7e-9 of 0.056, rotation 1.8e-11 of 8.9e-4, ... —
+    the blend backward's floating-point atomics, pool or no pool)."""
+    P, W, H, bg = 130, 64, 48, (0.1, 0.3, 0.2)
+    model = syn.make_raw_model(pu.one_quadrant_scene(P, W, H, seed=8), ray_fraction=0.6, seed=11)
+    md = _on_device(model, grad=True)
+    t = mp.tensors_of(md)
+    assert md.zval.shape[0] > 0 and md.bg_xyz.shape[0] > 0
+    cam = syn.default_camera(W, H)
+    ups = [tuple(g.to(DEV) for g in syn.make_upstream_grads(W, H, seed=20 + k)) for k in range(2)]
+    params = dict(zip(("zval", "features_dc", "features_rest", "opacity", "scaling", "rotation", "bg_xyz", "bg_features_dc",
+                       "bg_features_rest", "bg_opacity", "bg_scaling", "bg_rotation"), md.parameters()))
+    assert len(params) == 12
+
+    def step(degrees):
+        for p in params.values():
+            p.grad = None
+        m2s = torch.zeros(2, P, 3, device=DEV, requires_grad=True)
+        outs = mp.rasterize_model_views([pu.hip_settings(cam, d, bg) for d in degrees], m2s, **t)
+        torch.autograd.backward([o[i] for o in outs for i in (0, 2, 3)], [g for up in ups for g in up])
+        torch.cuda.synchronize()
+        return {k: p.grad for k, p in params.items()}
+    ga = step((0, 1))
+    for n in ("features_rest", "bg_features_rest"):
+        assert float(ga[n][:, :3].abs().max()) > 0 and float(ga[n][:, 3:].abs().max()) == 0, n
+    storage_a = ga["zval"].untyped_storage().data_ptr()
+    ga = None
+    gb = step((0, 0))
+    assert gb["zval"].untyped_storage().data_ptr() == storage_a             # the kept arena: the reuse was exercised
+    for n in ("features_rest", "bg_features_rest"):
+        assert float(gb[n].abs().max()) == 0, n
+        assert float(gb[n.replace("rest", "dc")].abs().max()) > 0, n
+    R.ARENA_POOL = False
+    try:
+        want = step((0, 0))
+    finally:
+        R.ARENA_POOL = True
+    assert want["zval"].untyped_storage().data_ptr() != storage_a
+    for k in params:
+        print(k, "max |pooled - unpooled|:", float((gb[k] - want[k]).abs().max()), "of", float(want[k].abs().max()))
+    for k in params:
+        assert torch.equal(gb[k], want[k]), k
+
+
 def test_render_remembers_the_validated_model_and_notices_a_densification():
     """render() keeps the validated _ModelArgs on the model object (model_path.model_for) while its tensors are the same objects
     at the same addresses; replaced tensors (what densify_and_prune does: new Parameters of another length,

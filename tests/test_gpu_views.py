@@ -198,3 +198,51 @@ def test_views_node_with_short_sh_records_and_low_active_degree(M, deg):
     if active < M:
         assert float(b["shs"].grad[:, active:].abs().max()) == 0.0
     assert float(b["shs"].grad[:, :active].abs().max()) > 0.0
+
+
+def test_views_of_mixed_sh_degree_leave_no_stale_tails_in_the_kept_gradient_arena():
+    """Step A: two views of one camera at degree 0 then 1 — the second ADDS non-zero gradients of coefficients 1-3 to the arena
+    the first one wrote.  Step B, on that very arena (kept by the pool), renders both views at degree 0: the pool must know
+    that the zeros begin at coefficient 4 now, not at 1, and have the kernel write coefficients 1-3 again.  130 Gaussians: two
+    full workgroups of the geometry backward (60 records each) and a partial one.
+
+    The last assertion compares step B with the pool on and off bit for bit.  A scene of make_scene's kind cannot carry it: the
+    blend backward sums per-Gaussian gradients with floating-point atomics, and such a step differs from ITSELF run to run with
+    the pool off (measured on an MI355X, six runs: 2-9 of the 390 means3D elements by one ulp, 3.7e-9 of 0.064; 2-6 SH elements,
+    7.3e-12 of 9.5e-5).  pu.one_quadrant_scene keeps every Gaussian inside one quadrant of the image: one atomic per gradient
+    record, no order to the sum."""
+    from scgaussian_amd import rasterizer as R
+    dev = torch.device("cuda")
+    P, W, H, bg = 130, 64, 48, (0.1, 0.3, 0.2)
+    sc, cam = pu.one_quadrant_scene(P, W, H, seed=8), syn.default_camera(W, H)
+    assert sc.shs.shape == (P, 16, 3)
+    lv = _leaves(sc, "sh_sr", cam, 3, dev)
+    assert len(lv) == 5
+    ups = [tuple(t.to(dev) for t in syn.make_upstream_grads(W, H, seed=20 + k)) for k in range(2)]
+
+    def step(degrees):
+        for p in lv.values():
+            p.grad = None
+        m2s = torch.zeros(2, P, 3, device=dev, requires_grad=True)
+        outs = R.GaussianRasterizerViews([pu.hip_settings(cam, d, bg) for d in degrees])(
+            means3D=lv["means3D"], means2D=m2s, opacities=lv["opacities"], **_kw(lv))
+        torch.autograd.backward([o[i] for o in outs for i in (0, 2, 3)], [g for up in ups for g in up])
+        torch.cuda.synchronize()
+        return {k: p.grad for k, p in lv.items()}
+    ga = step((0, 1))
+    assert float(ga["shs"][:, 1:4].abs().max()) > 0 and float(ga["shs"][:, 4:].abs().max()) == 0
+    storage_a = ga["shs"].untyped_storage().data_ptr()
+    ga = None
+    gb = step((0, 0))
+    assert gb["shs"].untyped_storage().data_ptr() == storage_a              # the kept arena: the reuse was exercised
+    assert float(gb["shs"][:, 1:].abs().max()) == 0 and float(gb["shs"][:, :1].abs().max()) > 0
+    R.ARENA_POOL = False
+    try:
+        want = step((0, 0))
+    finally:
+        R.ARENA_POOL = True
+    assert want["shs"].untyped_storage().data_ptr() != storage_a
+    for k in lv:
+        print(k, "max |pooled - unpooled|:", float((gb[k] - want[k]).abs().max()), "of", float(want[k].abs().max()))
+    for k in lv:
+        assert torch.equal(gb[k], want[k]), k

@@ -1,13 +1,15 @@
 """Host-side logic of the binding that needs no GPU (round 6): the capacity policy, what a settled count does to a camera's capacity,
 camera identity without a device read, the model path's attribute mapping and its refusal of models the kernels cannot take, the
-counters' summary per SH degree."""
+counters' summary per SH degree, the gradient arena's layout, pool and SH-tail promise (_grads.py)."""
 import os
 import sys
 import types
+import weakref
 
 import pytest
 import torch
 
+from scgaussian_amd import _grads as G
 from scgaussian_amd import model_path as mp
 from scgaussian_amd import rasterizer as R
 from scgaussian_amd import synthetic as syn
@@ -98,3 +100,114 @@ def test_counter_summary_keeps_the_degrees_apart(tmp_path, monkeypatch):
     assert d["S2_deg0"]["blend_backward"]["hbm_bytes"] == (2 * 400 + 10) * 1024
     assert d["S2"]["geometry_forward"]["hbm_bytes"] != d["S2_deg0"]["geometry_forward"]["hbm_bytes"]
     assert "kernel_source_sha256" in d["_stamp"]
+
+
+def _carries(grads, names):
+    """Parameters whose .grad are the given views (what autograd leaves behind after a backward)."""
+    params = []
+    for n in names:
+        p = torch.zeros(grads[n].shape, requires_grad=True)
+        p.grad = grads[n]
+        params.append(p)
+    return params
+
+
+def test_gradient_arena_layout_of_both_paths():
+    """One flat arena per backward: every gradient has its parameter's shape and starts on a 16-byte boundary, the large SH
+    segments come last, and grad_arena finds the one span again from the .grad tensors alone."""
+    P, cpu = 5, torch.device("cpu")
+    inputs = (torch.zeros(P, 3), torch.zeros(P, 1), torch.zeros(P, 16, 3), None, torch.zeros(P, 3), torch.zeros(P, 4), None)
+    out = R._grad_outputs(inputs, None, None, cpu, False)
+    names = ("means3D", "opacities", "scales", "rotations", "shs")
+    for n, i in zip(names, (0, 1, 4, 5, 2)):
+        assert out[n].shape == inputs[i].shape and out[n].storage_offset() % 4 == 0 and out[n].is_contiguous(), n
+    assert out["colors_precomp"] is None and out["cov3D_precomp"] is None and out["_pooled"] is None
+    assert out["means2D"].shape == (P, 3) and out["means2D"].untyped_storage().data_ptr() != out["shs"].untyped_storage().data_ptr()
+    # segments padded to 4 floats: 15 -> 16, 5 -> 8, 15 -> 16, 20, 240; the four small ones in front of the SH segment
+    assert [out[n].storage_offset() for n in names] == [0, 16, 24, 40, 60]
+    lay = G.layout(tuple((n, out[n].shape) for n in names))
+    assert G._take_arena("tensors", lay, lay[3], cpu, False)[0].numel() == 300
+    assert lay == (names, [16, 8, 16, 20, 240], ((P, 3), (P, 1), (P, 3), (P, 4), (P, 16, 3)), 300)
+    assert out["shs"].untyped_storage().nbytes() == 4 * 300
+    assert G.layout(tuple((n, out[n].shape) for n in names)) is lay                  # looked up, not rebuilt
+    assert G.layout(()) == ((), [], (), 4)
+    params = _carries(out, names)
+    assert R.grad_arena(params).numel() == 300 and R.grad_arena(params[:4]).numel() == 60
+    assert R.grad_arena(params).untyped_storage().data_ptr() == out["shs"].untyped_storage().data_ptr()
+    # the model path, a model without a background set: the non-empty tensors in _ARENA_ORDER, features_rest last
+    m = syn.make_raw_model(syn.make_scene(P, 64, 48), ray_fraction=1.0)
+    args = mp._ModelArgs(mp.tensors_of(m))
+    g = mp._grad_arena(args, None)
+    mnames = ("zval", "opacity", "scaling", "rotation", "features_dc", "features_rest")
+    assert tuple(n for n in g if not n.startswith("_")) == mnames and g["_c"] is not None
+    for n in mnames:
+        assert g[n].shape == getattr(m, n).shape and g[n].storage_offset() % 4 == 0, n
+    assert [g[n].storage_offset() for n in mnames] == [0, 8, 16, 32, 52, 68]
+    assert g["features_rest"].untyped_storage().nbytes() == 4 * (68 + P * 45 + 3)      # 225 floats in a 228-float segment
+    mparams = _carries(g, mnames)
+    assert R.grad_arena(mparams).numel() == 68 + P * 45 and R.grad_arena(mparams[:5]).numel() == 67
+
+
+def test_gradient_arena_pool_keeps_two_layouts_and_never_hands_out_an_arena_in_use():
+    cpu, path = torch.device("cpu"), "pool-test"
+
+    def take(key):
+        arena, pa = G._take_arena(path, key, 8, cpu)
+        assert pa is not None and pa.arena is arena
+        return pa, arena[:4]                                     # a view, as autograd keeps one as .grad
+    assert G._take_arena(path, "A", 8, cpu, False)[1] is None and (path, None) not in G._ARENA_POOLS      # the switch is off
+    a, view = take("A")
+    a2, view2 = take("A")                                        # the first one's view is alive: another arena
+    assert a2 is not a and a2.storage.data_ptr() != a.storage.data_ptr()
+    view = None
+    a3, view3 = take("A")                                        # released: handed out again, the one still in use is not
+    assert a3 is a
+    held = G._ARENA_POOLS[(path, None)]                          # [(layout, arenas)], least recently used first
+    assert held == [("A", [a, a2])]
+    gone = weakref.ref(a.arena)
+    a = a2 = a3 = view2 = view3 = None
+    b, view_b = take("B")
+    assert [k for k, _ in held] == ["A", "B"]
+    c, view_c = take("C")                                        # a third layout: the least recently used one's arenas go
+    assert held == [("B", [b]), ("C", [c])] and gone() is None
+    take("B")                                                    # use moves a layout to the recently-used end
+    take("D")
+    assert [k for k, _ in held] == ["B", "D"] and len(held[0][1]) == 2      # (b is still referenced by view_b: a second arena)
+    held_keeps = [take("D") for _ in range(5)]                   # the caller keeps these gradients: never the same arena twice,
+    assert len({pa.storage.data_ptr() for pa, _ in held_keeps}) == 5 and len(held[1][1]) == G._ARENA_POOL_DEPTH    # bounded
+    del G._ARENA_POOLS[(path, None)]
+
+
+def test_sh_tail_promise_is_decided_before_and_recorded_after_the_launch():
+    cpu = torch.device("cpu")
+    arena, pa = G._take_arena("promise-test", "L", 64, cpu)
+    try:
+        assert R._sh_tail_promise(None, 1) == 0                  # not pooled: nothing is known
+        assert R._sh_tail_promise(pa, 1) == 0                    # a fresh arena: the kernel writes the zeros
+        assert R._sh_tail_promise(pa, 1) == 0                    # ... deciding records nothing
+        G.commit_promise(pa, 4, False)
+        assert R._sh_tail_promise(pa, 4) == 2 and R._sh_tail_promise(pa, 9) == 2 and R._sh_tail_promise(pa, 16) == 2
+        assert R._sh_tail_promise(pa, 1) == 0                    # a lower degree: coefficients 1-3 hold old values
+        arena[:8].mul_(1.0)                                      # a torch write through a view: the promise is off
+        assert R._sh_tail_promise(pa, 4) == 0
+        G.commit_promise(pa, 4, False)
+        assert R._sh_tail_promise(pa, 4) == 2
+        # the failed-launch path: decided, the library call raised, no commit
+        assert R._sh_tail_promise(pa, 4) == 2
+        G.invalidate_promise(pa)
+        assert R._sh_tail_promise(pa, 4) == 0 and R._sh_tail_promise(pa, 16) == 0
+        G.commit_promise(pa, 16, True)                           # adding to an arena nobody knows anything about: still nothing
+        assert R._sh_tail_promise(pa, 16) == 0
+        # views of mixed degree in one step: the first WRITES at degree 0, the second ADDS at degree 1
+        G.commit_promise(pa, 1, False)
+        G.commit_promise(pa, 4, True)
+        assert R._sh_tail_promise(pa, 1) == 0 and R._sh_tail_promise(pa, 4) == 2
+        G.commit_promise(pa, 1, True)                            # a lower-degree view adds: the zeros stay where they begin
+        assert R._sh_tail_promise(pa, 1) == 0 and R._sh_tail_promise(pa, 4) == 2
+        arena[:8].mul_(1.0)
+        G.commit_promise(pa, 4, True)                            # a torch write between two views of a step: unknown from here on
+        assert R._sh_tail_promise(pa, 16) == 0
+        G.invalidate_promise(None)
+        G.commit_promise(None, 1, False)
+    finally:
+        del G._ARENA_POOLS[("promise-test", None)]

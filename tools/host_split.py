@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where the HOST time of a small training step goes: per library call (scg_forward, scg_wait_num_rendered, scg_backward — the
-C side: kernel launches, event record / wait) and per binding function (forward_fused, backward_fused), next to the whole step.
+C side: kernel launches, event record / wait) and per binding function (forward_fused, _backward_view), next to the whole step.
 Usage: python tools/host_split.py [S1]      (run with SCG_AUTOGRAD_SINGLE_THREAD=1 for the bench's host setup)"""
 import math
 import os
@@ -47,7 +47,7 @@ class Wrap:
 w = Wrap(lib)
 _lib.load = lambda: w
 fn = {}
-for name in ("forward_fused", "backward_fused", "_grad_outputs", "_frame_for"):
+for name in ("forward_fused", "_backward_view", "_grad_outputs", "_frame_for"):
     orig = getattr(R, name)
 
     def timed(*a, _o=orig, _n=name, **k):
