@@ -1,18 +1,25 @@
-"""The capacity policy and the counts of renders that were launched without a host read.  (Split out of rasterizer.py in round 6.)
+"""The capacity policy, the per-device state it lives in, and the counts of renders launched without a host read.
 
 A forward is launched with a CAPACITY — an upper bound of num_rendered, the number of (Gaussian, tile) instances — and learns the
 real count either at once (the default: the host waits for the geometry stage's partial sums) or LATER: with rasterizer.no_host_read()
 / inside a stream capture the binning stage leaves its count in a pinned word (ScgFrame.num_rendered_out) that is looked at the next
-time the camera is rendered.  This module owns those words and what a count that has arrived does to the camera's capacity;
-rasterizer.py decides when a forward runs in which mode.
+time the camera is rendered.  This module owns the per-device _SpecState and every access to its two capacity tables (lookup,
+lookup_shape, commit, commit_shape, forget: nothing outside this file touches `hint` / `cam_hint`), what a forward takes from the
+state (_PinnedSums, _Plan), and the pinned count words with what a count that has arrived does to the camera's capacity
+(_settle_word -> commit).  rasterizer.py decides in which mode a forward runs, launches it and repeats one that overflowed.
 """
 from __future__ import annotations
+
+import ctypes as C
+import threading
 
 import torch
 
 from . import _lib
+from ._lib import check
 
-_SPEC_STATE = {}                         # device index -> rasterizer._SpecState (capacities per shape and per camera, pending counts)
+_SPEC_STATE = {}                         # device index -> _SpecState
+_TABLE_MAX, _TABLE_TRIM = 1024, 128      # a capacity table beyond _TABLE_MAX entries loses its _TABLE_TRIM oldest
 
 
 def _capacity_for(R: int) -> int:
@@ -29,6 +36,158 @@ def _next_capacity(cur, R: int) -> int:
         return cur
     return _capacity_for(R)
 
+
+def first_sight_capacity(P: int) -> int:
+    """The bound of a render nothing is known about: too small is repaired by the overflow retry or the camera's next render."""
+    return _capacity_for(4 * P)
+
+
+def lookup(spec, P, W, H, cam, capturing=False, allow_first_sight=False):
+    """The capacity to launch camera `cam` (_camera_key) with; None: nothing is known, the staged path establishes it.
+    Remembered per CAMERA (views of one scene can differ by more than 2x in num_rendered: a bound shared by all of them would
+    shrink after the cheap view and overflow on the expensive one, every other step), keyed WITHOUT the Gaussian count:
+    densification changes P every ~100 iterations and must not put hundreds of cameras back on the shared fallback — after a
+    change of P the camera's last num_rendered is rescaled by the ratio of the counts.  A camera seen for the first time starts
+    from the latest bound of any camera of this shape, or (`allow_first_sight`: model path, no host read) from 4 P."""
+    ent = spec.cam_hint.get((W, H, cam))
+    if ent is not None:
+        cap, R_c, P_c = ent
+        if P_c != P:
+            cap = _capacity_for(int(R_c * (P / max(P_c, 1))) + 1)
+        if capturing:                                        # a captured step keeps its capacity for every replay: more head room
+            cap = max(cap, _capacity_for(int(R_c * (P / max(P_c, 1)) * 1.25) + 1))
+        return cap
+    cap = spec.hint.get((P, W, H))
+    return first_sight_capacity(P) if (cap is None and allow_first_sight) else cap
+
+
+def lookup_shape(spec, P, W, H):
+    """The latest bound of ANY camera of this shape (the staged forward's guess), or None."""
+    return spec.hint.get((P, W, H))
+
+
+def commit(spec, P, W, H, cam, cap, R):
+    """The next render of this camera, and of a new camera of this shape, starts from `cap` (derived from the count `R`).  The
+    camera's entry is re-inserted: the tables' order is the eviction order, the trim never takes the entry just written."""
+    spec.hint[(P, W, H)] = cap
+    ckey = (W, H, cam)
+    spec.cam_hint.pop(ckey, None)
+    spec.cam_hint[ckey] = (cap, R, P)
+    for table in (spec.hint, spec.cam_hint):
+        if len(table) > _TABLE_MAX:
+            for k in list(table)[:_TABLE_TRIM]:
+                del table[k]
+
+
+def commit_shape(spec, P, W, H, R):
+    """The staged forward's update: it knows the exact count and no camera."""
+    spec.hint[(P, W, H)] = _next_capacity(spec.hint.get((P, W, H)), R)
+
+
+def forget(spec, P, W, H, cam):
+    """The bound this camera needs no longer fits the tile-first binning: its next render takes the staged path."""
+    spec.cam_hint.pop((W, H, cam), None)
+    spec.hint.pop((P, W, H), None)
+
+
+class _SpecState:
+    """Per-device state of the speculative launch: the two capacity tables (read and written by the policy functions above
+    only), pinned host memory for the partial sums of num_rendered, the workspace plans, the pending count words."""
+
+    def __init__(self, device):
+        self.hint = {}                   # (P, W, H) -> capacity: the latest bound of ANY camera of this shape
+        self.cam_hint = {}               # (W, H, camera) -> (capacity, num_rendered, P it was taken at)
+        # pinned host scratch of the forwards IN FLIGHT on this device: one _PinnedSums per forward, taken from / returned to a
+        # free list (round 5: the operator is re-entrant — two threads, each on its own stream, may be inside a forward at the
+        # same time, as with the upstream extension; one shared scratch made the second one raise)
+        self.free = []
+        self.pool_lock = threading.Lock()
+        self.plans = {}                  # (P, W, H, capacity) -> _Plan
+        self.pending = {}                # (W, H, camera) -> [_CountWord]: no-host-read renders whose count nobody has looked at yet
+
+    def take(self, nbytes: int) -> "_PinnedSums":
+        """Pinned host memory used as the geometry stage's scratch for ONE forward: the kernel writes its per-workgroup
+        partial sums of num_rendered straight to the host, so the speculative path needs neither a total kernel nor a D2H
+        copy.  give_back() when the count has been read."""
+        with self.pool_lock:
+            ps = self.free.pop() if self.free else None
+        if ps is None or ps.nbytes < nbytes:
+            ps = _PinnedSums(nbytes)
+        return ps
+
+    def give_back(self, ps: "_PinnedSums"):
+        with self.pool_lock:
+            if len(self.free) < 8:
+                self.free.append(ps)
+
+    def plan(self, lib, P, W, H, cap):
+        key = (P, W, H, cap)
+        pl = self.plans.get(key)
+        if pl is None:
+            if len(self.plans) > 64:
+                self.plans.clear()
+            pl = self.plans[key] = _Plan(lib, P, W, H, cap)
+        return pl
+
+
+class _PinnedSums:
+    """The pinned words one forward's geometry kernel writes its partial sums of num_rendered to, and the events of the paths
+    that wait on one (the staged path; the one-call path with EVENTLESS_WAIT off)."""
+    __slots__ = ("t", "np", "ptr", "nbytes", "event", "raw_event")
+
+    def __init__(self, nbytes: int):
+        self.t = torch.zeros(((nbytes + 3) // 4 + 1024,), dtype=torch.int32).pin_memory()
+        self.np = self.t.numpy()
+        self.ptr = self.t.data_ptr()
+        self.nbytes = self.t.numel() * 4
+        self.event = None                # torch.cuda.Event of the staged path
+        self.raw_event = None            # hipEvent_t (timing disabled) of the one-call path
+
+    def torch_event(self):
+        if self.event is None:
+            self.event = torch.cuda.Event()
+        return self.event
+
+    def event_handle(self):
+        if self.raw_event is None:
+            h = C.c_void_p()
+            check(_lib.load().scg_event_create(C.byref(h), 0), "scg_event_create")
+            self.raw_event = h.value
+        return self.raw_event
+
+
+class _Plan:
+    """Workspace layout of one (P, W, H, capacity): byte offsets reported by the library, looked up once."""
+
+    __slots__ = ("total", "final_T", "n_contrib", "point_list", "ranges", "splats", "rects", "depth_keys", "clamped",
+                 "partial_bytes", "accepts", "fused", "_shape")
+
+    def __init__(self, lib, P, W, H, cap):
+        L = _lib.ScgWorkspaceLayout()
+        check(lib.scg_workspace_layout(P, cap, W, H, C.byref(L)), "scg_workspace_layout")
+        self.total = int(L.total)
+        for k in ("final_T", "n_contrib", "point_list", "ranges", "splats", "rects", "depth_keys", "clamped"):
+            setattr(self, k, int(getattr(L, k)))
+        self.partial_bytes = int(L.partial_words) * 4
+        self.accepts = lib.scg_binning_accepts_bound(cap, W, H, _lib.BINNING_AUTO) == 1
+        # ScgFrame.long_lists_out is written by the forward blend that sorts its own tiles; a frame whose sort is a kernel of
+        # its own (the library's A/B bit, FUSED_SORT = False) leaves the words alone (fused[options]: which one runs)
+        self.fused = {}
+        self._shape = (cap, W, H)
+
+    def sorts_in_blend(self, lib, options: int) -> bool:
+        v = self.fused.get(options)
+        if v is None:
+            v = self.fused[options] = lib.scg_forward_sorts_in_blend(*self._shape, options) == 1
+        return v
+
+
+def _spec_state(device) -> _SpecState:
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    st = _SPEC_STATE.get(key)
+    if st is None:
+        st = _SPEC_STATE[key] = _SpecState(device)
+    return st
 
 
 _COUNT_ARMED = 0xFFFFFFFF                # "the binning stage of this render has not written its count yet"
@@ -85,10 +244,7 @@ def _settle_word(spec, w: _CountWord, R: int):
     W, H, cam = w.key
     ent = spec.cam_hint.get(w.key)
     cur = ent[0] if (ent is not None and ent[2] == w.P) else w.cap
-    nxt = _next_capacity(max(cur, w.cap) if R <= w.cap else None, R)
-    spec.hint[(w.P, W, H)] = nxt
-    spec.cam_hint.pop(w.key, None)
-    spec.cam_hint[w.key] = (nxt, R, w.P)
+    commit(spec, w.P, W, H, cam, _next_capacity(max(cur, w.cap) if R <= w.cap else None, R), R)
 
 
 def _settle_camera(spec, key):

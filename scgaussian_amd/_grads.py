@@ -24,6 +24,8 @@ import math
 
 import torch
 
+from ._lib import BACKWARD_SH_TAIL_ZERO
+
 # Order of the segments in the tensor path's arena.  The SH gradients come LAST of the usual five: the other four (11 floats per
 # Gaussian) are then one contiguous span, which parallel.GradBucket all-reduces in place when only the active SH coefficients
 # of a degree-limited step are exchanged (round 5).
@@ -104,11 +106,11 @@ def _take_arena(path, key, total, dev, pool=True):
 
 
 def sh_tail_flag(pa, n_active: int) -> int:
-    """SCG_BACKWARD_SH_TAIL_ZERO (2) when the pooled arena is known to hold zeros in every SH coefficient >= n_active, else 0.
+    """SCG_BACKWARD_SH_TAIL_ZERO when the pooled arena is known to hold zeros in every SH coefficient >= n_active, else 0.
     Decides only: what the backward leaves behind is recorded by commit_promise once the launch has succeeded."""
-    if pa is None:
+    if pa is None or pa.zero_from is None or pa.zero_from > n_active or pa.version != pa.arena._version:
         return 0
-    return 2 if (pa.zero_from is not None and pa.zero_from <= n_active and pa.version == pa.arena._version) else 0
+    return BACKWARD_SH_TAIL_ZERO
 
 
 def commit_promise(pa, n_active: int, accumulated: bool):

@@ -15,6 +15,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SCG_LIB_PATH") or os.path.join(_HERE, "libscg_raster.so")
 
 ABI_VERSION = 10
+# The headers' option / flag enumerators under their own names minus "SCG_" (include/scg_raster.h; DEBUG_*: csrc/scg_debug.h, the
+# library's A/B bits of scg_forward's `options`).  tests/test_abi_cpu.py holds names and values against the headers' text.
+FORWARD_NO_BACKWARD_STATE, FORWARD_SKIP_RARE_SORT, FORWARD_RARE_8WAVE, FORWARD_SPLIT_LONG_LISTS = 4, 8, 16, 32
+FORWARD_ARM_PARTIAL_SUMS = 64
+DEBUG_SEPARATE_SORT, DEBUG_SEPARATE_HIST = 1, 2
+BACKWARD_ACCUMULATE, BACKWARD_SH_TAIL_ZERO = 1, 2
+BINNING_AUTO, BINNING_GLOBAL_SORT = 0, 1
 
 
 class ScgFrame(C.Structure):

@@ -23,7 +23,7 @@ from typing import Optional
 
 import torch
 
-from . import _grads, _lib
+from . import _counts, _grads, _lib
 from . import rasterizer as R
 from ._lib import ScgModel, ScgModelGrads, check
 
@@ -97,12 +97,7 @@ def supported(tensors: dict, settings=None) -> bool:
                 continue
             if tuple(t.shape) != shp or not _usable(t, dev, n.endswith(("features_dc", "features_rest", "rotation"))):
                 return False
-        if settings is not None:
-            lib = _lib.load()
-            if lib.scg_binning_accepts_bound(R._capacity_for(4 * (nr + nb)), int(settings.image_width),
-                                             int(settings.image_height), 0) != 1:
-                return False
-        return True
+        return settings is None or _accepts(nr + nb, settings)
     except (KeyError, AttributeError, IndexError):
         return False
 
@@ -116,7 +111,8 @@ def _accepts(P: int, settings) -> bool:
     if v is None:
         if len(_ACCEPTS) > 256:
             _ACCEPTS.clear()
-        v = _ACCEPTS[key] = _lib.load().scg_binning_accepts_bound(R._capacity_for(4 * P), key[1], key[2], 0) == 1
+        v = _ACCEPTS[key] = _lib.load().scg_binning_accepts_bound(_counts.first_sight_capacity(P), key[1], key[2],
+                                                                  _lib.BINNING_AUTO) == 1
     return v
 
 

@@ -12,6 +12,11 @@ gaussian_renderer/__init__.py:15 and uses at :38-53 and :100-108:
 PyTorch is plumbing here (device memory, the current stream, autograd graph edges); every stage of the
 computation runs in hand-written HIP kernels behind include/scg_raster.h.  There is no fallback path.
 
+What lives where: this module owns the operator, the frames with their per-camera launch hints, and the forwards and the backward
+as sequences of library calls (forward_fused: mode, capacity look-up, _launch_forward per attempt, overflow retry).  The capacity
+policy with its tables, pinned partial sums, workspace plans and count words: _counts.py; the gradient arena: _grads.py; camera
+identity: _cameras.py; the option and flag bits handed to the library: _lib.py's constants, named as in the headers.
+
 Concurrency: the operator is re-entrant per device and stream, like the upstream extension — every forward takes its own
 pinned scratch (the partial sums of num_rendered) from a per-device pool, so two threads, each on its own stream, may be
 inside a forward at the same time (round 5; before, the second one raised).  The host-side hint tables (capacities, tile
@@ -24,16 +29,16 @@ as it does with the reference's operator.
 from __future__ import annotations
 
 import contextlib
-import os
 import ctypes as C
-import threading
 from typing import Callable, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
 
-from . import _lib
-from ._lib import ScgFrame, check, ptr
+from . import _counts, _lib
+from ._lib import (BACKWARD_ACCUMULATE, BINNING_AUTO, DEBUG_SEPARATE_HIST, DEBUG_SEPARATE_SORT, FORWARD_ARM_PARTIAL_SUMS,
+                   FORWARD_NO_BACKWARD_STATE, FORWARD_RARE_8WAVE, FORWARD_SKIP_RARE_SORT, FORWARD_SPLIT_LONG_LISTS, ScgFrame, check,
+                   ptr)
 
 SPLAT_FLOATS = 12
 DSPLAT_FLOATS = 16         # gradient record of a Gaussian: one 64-byte line (scg_raster.h SCG_DSPLAT_FLOATS)
@@ -69,6 +74,13 @@ def _f32c(t: Optional[torch.Tensor], device) -> Optional[torch.Tensor]:
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
+
+
+def _kernel_inputs(dev, *tensors):
+    """The operator's seven inputs (means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp) as the kernels read
+    them (_f32c; None for an absent or empty one) + M, the SH coefficients per Gaussian."""
+    inputs = tuple([_f32c(t, dev) for t in tensors])
+    return inputs, (inputs[2].shape[1] if inputs[2] is not None else 0)
 
 
 class _Frame:
@@ -228,11 +240,11 @@ def _rare_options(words) -> int:
     if words is None or words[0] < 0:
         return 0                                             # nothing known yet: the rare-size kernel as in the staged calls
     if words[0] == 0:
-        return 8 if SKIP_IDLE_RARE_SORT else 0               # SCG_FORWARD_SKIP_RARE_SORT
+        return FORWARD_SKIP_RARE_SORT if SKIP_IDLE_RARE_SORT else 0
     # very long lists (beyond 16 384 entries): split everything beyond 4 096 by depth + 8-wave work-list sort; without them the
     # 16-wave rare-size kernel finishes its handful of lists in one round (measured: 30 %-clustered scene 64.6 vs 73.3 us)
     if RARE_8WAVE and SPLIT_LONG_LISTS and words[1] > 0:
-        return 16 | 32
+        return FORWARD_RARE_8WAVE | FORWARD_SPLIT_LONG_LISTS
     return 0
 
 
@@ -426,100 +438,11 @@ class _Arena:
         return self.buf[self.offsets[i]: self.offsets[i] + nbytes].view(dtype).view(shape)
 
 
-class _SpecState:
-    """Per-device state of the speculative launch: pinned host memory for the partial sums of num_rendered, an event,
-    and the capacity (upper bound of num_rendered) in use per (P, W, H)."""
-
-    def __init__(self, device):
-        self.hint = {}                   # (P, W, H) -> capacity: the latest bound of ANY camera of this shape
-        self.cam_hint = {}               # (W, H, camera) -> (capacity, num_rendered, P it was taken at)
-        # pinned host scratch of the forwards IN FLIGHT on this device: one _PinnedSums per forward, taken from / returned to a
-        # free list (round 5: the operator is re-entrant — two threads, each on its own stream, may be inside a forward at the
-        # same time, as with the upstream extension; one shared scratch made the second one raise)
-        self.free = []
-        self.pool_lock = threading.Lock()
-        self.plans = {}                  # (P, W, H, capacity) -> _Plan
-        self.pending = {}                # (W, H, camera) -> [_CountWord]: no-host-read renders whose count nobody has looked at yet
-
-    def take(self, nbytes: int) -> "_PinnedSums":
-        """Pinned host memory used as the geometry stage's scratch for ONE forward: the kernel writes its per-workgroup
-        partial sums of num_rendered straight to the host, so the speculative path needs neither a total kernel nor a D2H
-        copy.  give_back() when the count has been read."""
-        with self.pool_lock:
-            ps = self.free.pop() if self.free else None
-        if ps is None or ps.nbytes < nbytes:
-            ps = _PinnedSums(nbytes)
-        return ps
-
-    def give_back(self, ps: "_PinnedSums"):
-        with self.pool_lock:
-            if len(self.free) < 8:
-                self.free.append(ps)
-
-    def plan(self, lib, P, W, H, cap):
-        key = (P, W, H, cap)
-        pl = self.plans.get(key)
-        if pl is None:
-            if len(self.plans) > 64:
-                self.plans.clear()
-            pl = self.plans[key] = _Plan(lib, P, W, H, cap)
-        return pl
-
-
-
-class _PinnedSums:
-    """The pinned words one forward's geometry kernel writes its partial sums of num_rendered to, and the events of the paths
-    that wait on one (the staged path; the one-call path with EVENTLESS_WAIT off)."""
-    __slots__ = ("t", "np", "ptr", "nbytes", "event", "raw_event")
-
-    def __init__(self, nbytes: int):
-        self.t = torch.zeros(((nbytes + 3) // 4 + 1024,), dtype=torch.int32).pin_memory()
-        self.np = self.t.numpy()
-        self.ptr = self.t.data_ptr()
-        self.nbytes = self.t.numel() * 4
-        self.event = None                # torch.cuda.Event of the staged path
-        self.raw_event = None            # hipEvent_t (timing disabled) of the one-call path
-
-    def torch_event(self):
-        if self.event is None:
-            self.event = torch.cuda.Event()
-        return self.event
-
-    def event_handle(self):
-        if self.raw_event is None:
-            h = C.c_void_p()
-            check(_lib.load().scg_event_create(C.byref(h), 0), "scg_event_create")
-            self.raw_event = h.value
-        return self.raw_event
-
-
-class _Plan:
-    """Workspace layout of one (P, W, H, capacity): byte offsets reported by the library, looked up once."""
-
-    __slots__ = ("total", "final_T", "n_contrib", "point_list", "ranges", "splats", "rects", "depth_keys", "clamped",
-                 "partial_bytes", "accepts", "fused", "_shape")
-
-    def __init__(self, lib, P, W, H, cap):
-        L = _lib.ScgWorkspaceLayout()
-        check(lib.scg_workspace_layout(P, cap, W, H, C.byref(L)), "scg_workspace_layout")
-        self.total = int(L.total)
-        for k in ("final_T", "n_contrib", "point_list", "ranges", "splats", "rects", "depth_keys", "clamped"):
-            setattr(self, k, int(getattr(L, k)))
-        self.partial_bytes = int(L.partial_words) * 4
-        self.accepts = lib.scg_binning_accepts_bound(cap, W, H, 0) == 1
-        # ScgFrame.long_lists_out is written by the forward blend that sorts its own tiles; a frame whose sort is a kernel of
-        # its own (the library's A/B bit, FUSED_SORT = False) leaves the words alone (fused[options]: which one runs)
-        self.fused = {}
-        self._shape = (cap, W, H)
-
-    def sorts_in_blend(self, lib, options: int) -> bool:
-        v = self.fused.get(options)
-        if v is None:
-            v = self.fused[options] = lib.scg_forward_sorts_in_blend(*self._shape, options) == 1
-        return v
-
-
-from ._counts import _SPEC_STATE, _capacity_for, _next_capacity          # noqa: E402 - the capacity policy: _counts.py
+# the capacity policy with the per-device state it lives in, the pinned count words of renders launched without a host read and
+# what a settled count does to a camera's capacity, the counters: _counts.py
+from ._counts import (_ANON_CAPTURED, _COUNT_ARMED, _COUNT_FREE, _COUNT_SLOTS, _OVERFLOW, _QUARANTINE, _SPEC_STATE,      # noqa: E402,F401
+                      _CountWord, _capacity_for, _count_pool, _count_word, _next_capacity, _settle_camera, _settle_word,
+                      _spec_state, overflow_stats, settle_counts)
 # what the speculation cost so far (speculation_stats(); bench.py `moving_scene`): forwards on the one-call path, how many of them
 # had to be repeated because num_rendered exceeded the capacity, forwards that took the staged path (first sight of a shape, images
 # beyond the tile-first binning), and how many one-call forwards had a launch-order hint of their camera's previous render
@@ -546,17 +469,9 @@ FUSED_HIST = True
 EVENTLESS_WAIT = True
 
 
-def _spec_state(device) -> _SpecState:
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    st = _SPEC_STATE.get(key)
-    if st is None:
-        st = _SPEC_STATE[key] = _SpecState(device)
-    return st
-
-
 def forward_stages(settings: GaussianRasterizationSettings, means3D, opacities, shs=None, colors_precomp=None,
                    scales=None, rotations=None, cov3D_precomp=None, want_keys: bool = False,
-                   timer: Optional[Callable] = None, binning_algo: int = 0, capacity_hint: Optional[int] = None,
+                   timer: Optional[Callable] = None, binning_algo: int = BINNING_AUTO, capacity_hint: Optional[int] = None,
                    prepare_backward: bool = False):
     """Run the forward stages through the C ABI and return every intermediate (used by the autograd
     function and, with want_keys=True, by the parity tests).
@@ -567,26 +482,14 @@ def forward_stages(settings: GaussianRasterizationSettings, means3D, opacities, 
     the launches.  A guess that was too small (rare) re-runs stages 2-3 with the exact size.  `capacity_hint`
     overrides the guess (tests)."""
     _require_cuda(means3D)
-    spec = _spec_state(means3D.device)
-    return _forward_stages_locked(spec, settings, means3D, opacities, shs, colors_precomp, scales, rotations,
-                                  cov3D_precomp, want_keys, timer, binning_algo, capacity_hint, prepare_backward)
-
-
-def _forward_stages_locked(spec, settings, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp,
-                           want_keys, timer, binning_algo, capacity_hint, prepare_backward):
     lib = _lib.load()
     _SPEC_STATS["staged_forwards"] += 1
     timer = timer or _ACTIVE_TIMER
     dev = means3D.device
-    means3D = _f32c(means3D, dev)
+    spec = _spec_state(dev)
+    inputs, M = _kernel_inputs(dev, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp)
+    means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp = inputs
     P = 0 if means3D is None else means3D.shape[0]
-    opacities = _f32c(opacities, dev)
-    shs = _f32c(shs, dev)
-    colors_precomp = _f32c(colors_precomp, dev)
-    scales = _f32c(scales, dev)
-    rotations = _f32c(rotations, dev)
-    cov3D_precomp = _f32c(cov3D_precomp, dev)
-    M = shs.shape[1] if shs is not None else 0
     fr = _frame_for(settings, P, M, dev, forward=True)
     H, W = fr.H, fr.W
     with _on_device(dev):
@@ -595,8 +498,7 @@ def _forward_stages_locked(spec, settings, means3D, opacities, shs, colors_preco
         gscratch = lib.scg_geometry_scratch_bytes(P)
         ga = _Arena([P * SPLAT_FLOATS * 4, P * 8, P * 4, P, gscratch, 4], dev)
         radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        key = (P, W, H)
-        guess = capacity_hint if capacity_hint is not None else spec.hint.get(key)
+        guess = capacity_hint if capacity_hint is not None else _counts.lookup_shape(spec, P, W, H)
         speculative = (SPECULATIVE_LAUNCH or capacity_hint is not None) and guess is not None and P > 0 and \
             not want_keys and \
             lib.scg_binning_accepts_bound(int(guess), W, H, binning_algo) == 1
@@ -645,7 +547,7 @@ def _forward_stages_locked(spec, settings, means3D, opacities, shs, colors_preco
                               arenas=(ga, ba), capacity=cap, n_tiles=fr.n_tiles, hw=(H, W), P=P, frame=fr,
                               ptrs=dict(splats=ga.ptr(0), clamped=ga.ptr(3), point_list=ba.ptr(0), ranges=ba.ptr(1),
                                         final_T=ba.ptr(2), n_contrib=ba.ptr(3)),
-                              inputs=(means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp)),
+                              inputs=inputs),
                          want_keys)
         if speculative:
             pinned.torch_event().synchronize()
@@ -659,7 +561,7 @@ def _forward_stages_locked(spec, settings, means3D, opacities, shs, colors_preco
                 out["ptrs"].update(point_list=ba.ptr(0), ranges=ba.ptr(1), final_T=ba.ptr(2), n_contrib=ba.ptr(3))
             out["num_rendered"] = R
         if capacity_hint is None:
-            spec.hint[key] = _next_capacity(spec.hint.get(key), R)
+            _counts.commit_shape(spec, P, W, H, R)
     return out
 
 
@@ -742,7 +644,7 @@ def _backward_view(state, inputs, radii, dL_dcolor, dL_ddepth, dL_dalpha, timer:
             model.grad_outputs(into, d_means2D_out)
         # the pooled arena's promise about its SH tails: decided here, recorded once the library call has returned success
         pa, n_active = out.get("_pooled"), (fr.c.sh_degree + 1) ** 2
-        flags = 1 if into is not None else _sh_tail_promise(pa, n_active)
+        flags = BACKWARD_ACCUMULATE if into is not None else _sh_tail_promise(pa, n_active)
         try:
             if model is not None:
                 check(lib.scg_backward_model(fr.ref, model.ref, radii.data_ptr(), state["cap"], state["ws"].data_ptr(),
@@ -816,51 +718,70 @@ def no_host_read(enabled: bool = True):
         NO_HOST_READ = prev
 
 
-# the pinned count words, what a settled count does to a camera's capacity, the counters: _counts.py
-from ._counts import (_ANON_CAPTURED, _COUNT_ARMED, _COUNT_FREE, _COUNT_SLOTS, _OVERFLOW, _QUARANTINE, _CountWord,   # noqa: E402,F401
-                      _count_pool, _count_word, _settle_camera, _settle_word, overflow_stats, settle_counts)
-
-
 # ---------------------------------------------------------------------------------------------------------------------
 # the fast path: ONE C-ABI call per direction (include/scg_raster.h scg_forward / scg_backward)
 # ---------------------------------------------------------------------------------------------------------------------
+def _launch_forward(lib, fr, P, dev, model, in_ptrs, plan, cap, outs, pinned, ev, ckey, prepare_backward, stage_ev, stream):
+    """ONE attempt of forward_fused at capacity `cap`: the workspace, the option word, where the count goes, the library call.
+    `outs`: the addresses of radii, colour, depth, alpha; `pinned`: this forward's pinned partial sums — None for a forward that
+    does not read the host, whose count arrives in a count word of camera `ckey`.  Returns (workspace, address of the cleared
+    gradient records or None, count word or None)."""
+    # the gradient records of the coming backward (cleared by the forward blend) live behind the workspace in the same
+    # allocation: one torch.empty less per step (they are only ever addressed by raw pointer); without a host read the geometry
+    # kernel's partial sums of num_rendered go to device memory behind the records: nobody reads them — the count comes from
+    # the binning stage, ScgFrame.num_rendered_out
+    ds_bytes = (P * DSPLAT_FLOATS * 4 + 64) if prepare_backward else 0
+    ws = torch.empty((plan.total + ds_bytes + (plan.partial_bytes + 256 if pinned is None else 0),), dtype=torch.uint8, device=dev)
+    wp = ws.data_ptr()
+    dsplats = ((wp + plan.total + 63) & ~63) if prepare_backward else None       # 64-byte aligned records
+    # num_rendered without an event (ABI 9): the pinned words are armed by scg_forward and watched by scg_wait_num_rendered — no
+    # barrier packet behind the geometry kernel, no event wake-up
+    options = (0 if FUSED_SORT else DEBUG_SEPARATE_SORT) | (0 if FUSED_HIST else DEBUG_SEPARATE_HIST) | \
+        (0 if prepare_backward else FORWARD_NO_BACKWARD_STATE) | _rare_options(fr.long_np) | \
+        (FORWARD_ARM_PARTIAL_SUMS if (ev is None and pinned is not None) else 0)
+    if fr.long_np is not None and fr.long_np[0] >= 0 and not plan.sorts_in_blend(lib, options):
+        # nobody writes the words in this frame: what an earlier, sparser frame of the camera left there is stale
+        fr.long_np[:] = -1
+        options &= ~(FORWARD_SKIP_RARE_SORT | FORWARD_RARE_8WAVE | FORWARD_SPLIT_LONG_LISTS)
+    if pinned is None:
+        cw = _count_word(cap, P, ckey, dev.index)
+        fr.c.num_rendered_out = cw.ptr
+        sums = (wp + plan.total + ds_bytes + 255) & ~255
+    else:
+        cw = fr.c.num_rendered_out = None
+        sums = pinned.ptr
+    try:
+        if model is None:
+            check(lib.scg_forward(fr.ref, *in_ptrs, cap, wp, plan.total, *outs, sums, ev, dsplats, options, stage_ev, stream),
+                  "scg_forward")
+        else:
+            check(lib.scg_forward_model(fr.ref, model.ref, cap, wp, plan.total, *outs, sums, ev, dsplats, options, stage_ev,
+                                        stream), "scg_forward_model")
+    finally:
+        fr.c.num_rendered_out = None
+    return ws, dsplats, cw
+
+
 def forward_fused(settings: GaussianRasterizationSettings, means3D, opacities, shs, colors_precomp, scales, rotations,
                   cov3D_precomp, prepare_backward: bool, timer: Optional[Callable] = None, model=None):
     """Stages 1-3 in one library call, laid out in one workspace allocation, enqueued without a host read: the capacity
-    (upper bound of num_rendered) comes from the previous calls of this problem shape.  Returns None when the fast path
-    does not apply (no capacity known yet, image too large for the tile-first binning): the caller then takes the
-    staged path, which also establishes the capacity.  Otherwise (color, radii, depth, alpha, state).
+    (upper bound of num_rendered) comes from the previous calls of this camera or problem shape (_counts.lookup).  Returns None
+    when the fast path does not apply (no capacity known yet, image too large for the tile-first binning): the caller then takes
+    the staged path, which also establishes the capacity.  Otherwise (color, radii, depth, alpha, state).
     `model` (model_path._ModelArgs): the reference model's raw parameter tensors in place of the seven activated inputs
     (scg_forward_model); a model's first render starts from a generous bound instead of the staged path."""
     dev = means3D.device if model is None else model.device
     spec = _spec_state(dev)
     P = means3D.shape[0] if model is None else model.P
     H, W = int(settings.image_height), int(settings.image_width)
-    # the capacity is remembered per CAMERA (views of one scene can differ by more than 2x in num_rendered: a bound
-    # shared by all of them would shrink after the cheap view and overflow on the expensive one, every other step); a
-    # camera seen for the first time starts from the latest bound of any camera of this shape
-    # (the camera = the content of its view matrix, _camera_key: an address can be recycled for another camera)
-    cam = _camera_key(settings.viewmatrix)
+    cam = _camera_key(settings.viewmatrix)   # the content of the view matrix: an address can be recycled for another camera
     ckey = (W, H, cam)
     # a forward that must not read the host: asked for (NO_HOST_READ) or inside a stream capture (a host read cannot be captured)
     capturing = torch.cuda.is_current_stream_capturing()
     no_read = NO_HOST_READ or capturing
     if spec.pending:
         _settle_camera(spec, ckey)                           # counts of this camera's earlier no-host-read renders that have arrived
-    # ... keyed WITHOUT the Gaussian count: densification changes P every ~100 iterations, and a per-camera entry that
-    # died with every change of P would leave hundreds of cameras on the shared fallback again.  The entry remembers the
-    # count it was taken at; after a change of P the camera's last num_rendered is rescaled by the ratio of the counts.
-    ent = spec.cam_hint.get(ckey)
-    if ent is not None:
-        cap_c, R_c, P_c = ent
-        cap = cap_c if P_c == P else _capacity_for(int(R_c * (P / max(P_c, 1))) + 1)
-        if capturing:                                        # a captured step keeps its capacity for every replay: more head room
-            cap = max(cap, _capacity_for(int(R_c * (P / max(P_c, 1)) * 1.25) + 1))
-    else:
-        cap = spec.hint.get((P, W, H))
-    if cap is None and (model is not None or no_read):
-        cap = _capacity_for(4 * P)                           # (too small: the retry below repeats the call with room for the count;
-    #                                                           without a host read the camera's next render has room)
+    cap = _counts.lookup(spec, P, W, H, cam, capturing, model is not None or no_read)
     if cap is None or P == 0 or not SPECULATIVE_LAUNCH:
         if capturing:
             raise _lib.ScgError("a rasterizer forward inside a stream capture needs the one-call path (P > 0, SPECULATIVE_LAUNCH)")
@@ -875,16 +796,10 @@ def forward_fused(settings: GaussianRasterizationSettings, means3D, opacities, s
     pinned = None if no_read else spec.take(plan.partial_bytes)   # this forward's pinned words (returned once num_rendered is read)
     try:
         if model is None:
-            means3D = _f32c(means3D, dev)
-            opacities = _f32c(opacities, dev)
-            shs = _f32c(shs, dev)
-            colors_precomp = _f32c(colors_precomp, dev)
-            scales = _f32c(scales, dev)
-            rotations = _f32c(rotations, dev)
-            cov3D_precomp = _f32c(cov3D_precomp, dev)
-            M = shs.shape[1] if shs is not None else 0
+            inputs, M = _kernel_inputs(dev, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp)
+            in_ptrs = tuple(None if t is None else t.data_ptr() for t in inputs)
         else:
-            M = 16
+            inputs, M, in_ptrs = model.tensors, 16, None
         fr = _frame_for(settings, P, M, dev, forward=True)
         _SPEC_STATS["one_call_forwards"] += 1
         if fr.c.tile_cost_in:
@@ -895,54 +810,14 @@ def forward_fused(settings: GaussianRasterizationSettings, means3D, opacities, s
         with _on_device(dev):
             stage_ev = timer.stage_events("forward") if isinstance(timer, StageTimer) else None
             stream = _stream(dev)
-            # num_rendered without an event (ABI 9): the pinned words are armed by scg_forward and watched by
-            # scg_wait_num_rendered — no barrier packet behind the geometry kernel, no event wake-up
-            ev = None if EVENTLESS_WAIT else pinned.event_handle()
+            ev = None if (EVENTLESS_WAIT or no_read) else pinned.event_handle()
             img = torch.empty((5, H, W), dtype=torch.float32, device=dev)          # colour | depth | alpha
             radii = torch.empty((P,), dtype=torch.int32, device=dev)
-            # the gradient records of the coming backward (cleared by the forward blend) live behind the workspace in the same
-            # allocation: one torch.empty less per step (they are only ever addressed by raw pointer)
-            ds_bytes = (P * DSPLAT_FLOATS * 4 + 64) if prepare_backward else 0
-            ip = img.data_ptr()
-            hw4 = H * W * 4
-            if model is None:
-                inputs = (means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp)
-                in_ptrs = tuple(None if t is None else t.data_ptr() for t in inputs)
-            else:
-                inputs = model.tensors
-            cw = None
+            ip, hw4 = img.data_ptr(), H * W * 4
+            outs = (radii.data_ptr(), ip, ip + 3 * hw4, ip + 4 * hw4)
             while True:
-                # (without a host read the geometry kernel's partial sums of num_rendered go to device memory behind the records:
-                # nobody reads them — the count comes from the binning stage, ScgFrame.num_rendered_out)
-                ws = torch.empty((plan.total + ds_bytes + (plan.partial_bytes + 256 if no_read else 0),), dtype=torch.uint8,
-                                 device=dev)
-                wp = ws.data_ptr()
-                dsplats = ((wp + plan.total + 63) & ~63) if prepare_backward else None       # 64-byte aligned records
-                options = (0 if FUSED_SORT else 1) | (0 if FUSED_HIST else 2) | (0 if prepare_backward else 4) | \
-                    _rare_options(fr.long_np) | (64 if (ev is None and not no_read) else 0)
-                if fr.long_np is not None and fr.long_np[0] >= 0 and not plan.sorts_in_blend(lib, options):
-                    # nobody writes the words in this frame: what an earlier, sparser frame of the camera left there is stale
-                    fr.long_np[:] = -1
-                    options &= ~(8 | 16 | 32)
-                if no_read:
-                    cw = _count_word(cap, P, ckey, dev.index)
-                    fr.c.num_rendered_out = cw.ptr
-                    sums, ev = (wp + plan.total + ds_bytes + 255) & ~255, None
-                else:
-                    fr.c.num_rendered_out = None
-                    sums = pinned.ptr
-                try:
-                    if model is None:
-                        check(lib.scg_forward(fr.ref, *in_ptrs, cap, wp, plan.total, radii.data_ptr(), ip,
-                                              ip + 3 * hw4, ip + 4 * hw4, sums, ev,
-                                              dsplats, options, stage_ev,
-                                              stream), "scg_forward")
-                    else:
-                        check(lib.scg_forward_model(fr.ref, model.ref, cap, wp, plan.total, radii.data_ptr(), ip,
-                                                    ip + 3 * hw4, ip + 4 * hw4, sums, ev, dsplats, options, stage_ev,
-                                                    stream), "scg_forward_model")
-                finally:
-                    fr.c.num_rendered_out = None
+                ws, dsplats, cw = _launch_forward(lib, fr, P, dev, model, in_ptrs, plan, cap, outs, pinned, ev, ckey,
+                                                  prepare_backward, stage_ev, stream)
                 if no_read:
                     # launched, not waited for: the count is looked at when this camera is rendered next (or by settle_counts /
                     # the captured step that owns the word)
@@ -958,6 +833,7 @@ def forward_fused(settings: GaussianRasterizationSettings, means3D, opacities, s
                 if R < 0:
                     check(int(R), "scg_wait_num_rendered")
                 if R <= cap:
+                    _counts.commit(spec, P, W, H, cam, _next_capacity(cap, R), R)
                     break
                 # the bound was too small (rare: the scene grew by > 12 % since this camera's last render): lists were
                 # clipped, run again with room for the real count
@@ -965,20 +841,10 @@ def forward_fused(settings: GaussianRasterizationSettings, means3D, opacities, s
                 cap = _capacity_for(R)
                 plan = spec.plan(lib, P, W, H, cap)
                 if not plan.accepts:                 # the larger bound no longer fits the tile-first binning:
-                    spec.cam_hint.pop((W, H, cam), None)         # the staged path (global sort) takes over
-                    spec.hint.pop((P, W, H), None)
+                    _counts.forget(spec, P, W, H, cam)           # the staged path (global sort) takes over
                     spec.give_back(pinned)
                     return None
                 stage_ev = None
-            if R is not None:
-                nxt = _next_capacity(cap, R)
-                spec.hint[(P, W, H)] = nxt
-                spec.cam_hint.pop((W, H, cam), None)             # (re-inserted: the dict's order is the eviction order)
-                spec.cam_hint[(W, H, cam)] = (nxt, R, P)
-            for table in (spec.hint, spec.cam_hint):             # bounded: the OLDEST entries go, never the ones just written
-                if len(table) > 1024:
-                    for k in list(table)[:128]:
-                        del table[k]
         # "num_rendered": None for a forward that did not read the host ("count_word": where its count arrives)
         state = {"ws": ws, "cap": cap, "plan": plan, "frame": fr, "dsplats_zeroed": dsplats, "num_rendered": R,
                  "inputs": inputs, "has_backward_state": bool(prepare_backward), "count_word": cw}

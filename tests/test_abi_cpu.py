@@ -46,16 +46,36 @@ def test_library_exports_every_declared_symbol():
     assert lib.scg_struct_bytes(99) == 0
 
 
+def test_option_and_flag_bits_of_the_binding_are_the_headers():
+    """Every SCG_FORWARD_* / SCG_BACKWARD_* / SCG_DEBUG_* / SCG_BINNING_* enumerator of include/scg_raster.h and
+    csrc/scg_debug.h has a constant of the same name (minus SCG_) and value in _lib, and _lib has none the headers lack."""
+    declared = {}
+    for hdr in (os.path.join(ROOT, "include", "scg_raster.h"), os.path.join(ROOT, "scgaussian_amd", "csrc", "scg_debug.h")):
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(hdr).read(), flags=re.S)
+        for body in re.findall(r"\benum\s*\{(.*?)\}", text, flags=re.S):
+            for name, value in re.findall(r"\bSCG_((?:FORWARD|BACKWARD|DEBUG|BINNING)_[A-Z0-9_]+)\s*=\s*(\w+)", body):
+                assert name not in declared, name
+                declared[name] = int(value, 0)
+    assert len(declared) >= 11 and declared["FORWARD_ARM_PARTIAL_SUMS"] == 64 and declared["BINNING_AUTO"] == 0
+    bound = {k: v for k, v in vars(_lib).items() if re.fullmatch(r"(FORWARD|BACKWARD|DEBUG|BINNING)_[A-Z0-9_]+", k)}
+    assert bound == declared, sorted(set(bound.items()) ^ set(declared.items()))
+    # the bits of one option word do not collide: scg_forward's `options` carries the FORWARD_* and the DEBUG_* bits together
+    word = [v for k, v in declared.items() if k.startswith(("FORWARD_", "DEBUG_"))]
+    assert all(v > 0 and v & (v - 1) == 0 for v in word) and len(set(word)) == len(word)
+
+
 def test_scratch_size_queries_are_monotone():
     lib = _lib.load()
     assert lib.scg_geometry_scratch_bytes(1) > 0
     assert lib.scg_geometry_scratch_bytes(1_000_000) >= 1_000_000 // 256 * 4
-    a = lib.scg_binning_scratch_bytes(500, 1000, 256, 256, 0)
-    b = lib.scg_binning_scratch_bytes(500_000, 1_000_000, 1920, 1080, 0)
-    c = lib.scg_binning_scratch_bytes(500_000, 1_000_000, 1920, 1080, 1)      # global 64-bit sort: 20 B / instance
+    auto, global_sort = _lib.BINNING_AUTO, _lib.BINNING_GLOBAL_SORT
+    a = lib.scg_binning_scratch_bytes(500, 1000, 256, 256, auto)
+    b = lib.scg_binning_scratch_bytes(500_000, 1_000_000, 1920, 1080, auto)
+    c = lib.scg_binning_scratch_bytes(500_000, 1_000_000, 1920, 1080, global_sort)      # global 64-bit sort: 20 B / instance
     assert 0 < a < b and c >= 1_000_000 * 20
     # the tile-first path never materialises the R 64-bit key/value pairs twice: smaller scratch than the global sort
-    assert lib.scg_binning_scratch_bytes(500_000, 4_000_000, 1920, 1080, 0) < lib.scg_binning_scratch_bytes(500_000, 4_000_000, 1920, 1080, 1)
+    assert lib.scg_binning_scratch_bytes(500_000, 4_000_000, 1920, 1080, auto) < \
+        lib.scg_binning_scratch_bytes(500_000, 4_000_000, 1920, 1080, global_sort)
     assert lib.scg_sort_scratch_bytes(10) > 0 and lib.scg_scan_scratch_bytes(10) > 0
 
 

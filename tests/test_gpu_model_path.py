@@ -414,3 +414,37 @@ def test_a_model_whose_background_set_is_the_references_empty_initialisation():
     finally:
         rmod.MODEL_FAST_PATH = True
     assert pu.nrm_err(out["render"].detach(), slow["render"]) < 1e-4 and int((out["radii"] != slow["radii"]).sum()) <= 2
+
+
+def test_model_forward_repeats_a_launch_whose_capacity_was_too_small():
+    """The overflow retry through scg_forward_model: the camera's bound is forced to the smallest one the policy hands out, below
+    the scene's num_rendered — the forward notices, launches once more with room for the count and returns the same bits."""
+    P, W, H = 2_000, 128, 96
+    sc, model = _model(P, W, H, 0.6, seed=5)
+    t = mp.tensors_of(_on_device(model))
+    assert t["zval"].shape[0] > 0 and t["bg_xyz"].shape[0] > 0
+    cam = syn.default_camera(W, H)
+    smallest = R._capacity_for(0)
+    for scale in (1.0, 2.0, 4.0, 8.0):                          # (larger splats until the scene needs more than that bound)
+        st = pu.hip_settings(cam, 3, (0.2, 0.1, 0.3), scale)
+        assert mp.supported(t, st)
+        first = R.forward_fused(st, None, None, None, None, None, None, None, True, model=mp._ModelArgs(t))
+        assert first is not None
+        count = int(first[4]["num_rendered"])
+        if count > smallest:
+            break
+    assert count > smallest, (count, smallest)
+    spec, ckey = R._spec_state(t["zval"].device), (W, H, R._camera_key(st.viewmatrix))
+    assert spec.cam_hint[ckey][0] >= count and spec.cam_hint[ckey][1:] == (count, P)
+    spec.cam_hint[ckey] = (smallest, count, P)
+    before = R.speculation_stats()
+    again = R.forward_fused(st, None, None, None, None, None, None, None, True, model=mp._ModelArgs(t))
+    torch.cuda.synchronize()
+    after = R.speculation_stats()
+    assert after["overflow_retries"] == before["overflow_retries"] + 1
+    assert after["one_call_forwards"] == before["one_call_forwards"] + 1
+    assert int(again[4]["num_rendered"]) == count and again[4]["cap"] >= count
+    for a, b, name in zip(first[:4], again[:4], ("color", "radii", "depth", "alpha")):
+        assert torch.equal(a, b), name
+    assert float(first[0].abs().max()) > 0 and int((first[1] > 0).sum()) > 0
+    assert spec.cam_hint[ckey][0] >= count and spec.cam_hint[ckey][1:] == (count, P) and list(spec.cam_hint)[-1] == ckey

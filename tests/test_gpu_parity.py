@@ -13,6 +13,8 @@ import torch
 
 import parity_utils as pu
 from scgaussian_amd import synthetic as syn
+from scgaussian_amd._lib import (BINNING_AUTO, BINNING_GLOBAL_SORT, FORWARD_RARE_8WAVE, FORWARD_SKIP_RARE_SORT,
+                                 FORWARD_SPLIT_LONG_LISTS)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +32,7 @@ def _tiles_touched(fs) -> np.ndarray:
     return ((r[:, 1] & 0xFFFF) * (r[:, 1] >> 16)).astype(np.int64)
 
 
-def _stages(sc, cam, deg, bg, mod=1.0, mode="sh_sr", algo=0):
+def _stages(sc, cam, deg, bg, mod=1.0, mode="sh_sr", algo=BINNING_AUTO):
     from scgaussian_amd import rasterizer as R
     st = pu.hip_settings(cam, deg, bg, mod)
     lv = {k: v.to(_dev()) for k, v in pu.run_oracle_inputs(sc, cam, deg, mod, mode).items()}
@@ -68,7 +70,7 @@ def test_forward_matches_oracle(cfg):
     assert fs["num_rendered"] == b["num_rendered"]
     assert np.array_equal(np.cumsum(_tiles_touched(fs)).astype(np.uint32), b["point_offsets"])
     assert np.array_equal(pu.as_u32(fs["rects"]).astype(np.int64)[:, 0] & 0xFFFF, pre["rect"].numpy()[:, 0] * (o["radii"] > 0).numpy())
-    for algo_fs in (fs, _stages(sc, cam, deg, bg, mod, algo=1)):      # depth-first binning and global 64-bit sort
+    for algo_fs in (fs, _stages(sc, cam, deg, bg, mod, algo=BINNING_GLOBAL_SORT)):      # depth-first binning and global 64-bit sort
         assert np.array_equal(algo_fs["keys_sorted"].cpu().numpy().view(np.uint64), b["keys_sorted"])
         assert np.array_equal(pu.as_u32(algo_fs["point_list"]), b["point_list"])
         assert np.array_equal(pu.as_u32(algo_fs["ranges"]), b["ranges"])
@@ -273,7 +275,7 @@ def test_single_and_huge_gaussians():
         assert np.array_equal(pu.as_u32(fs["ranges"]), b["ranges"])
         if 0 in sel:
             assert b["num_rendered"] >= ((W + 15) // 16) * ((H + 15) // 16)     # covers every tile
-        fs1 = _stages(sc, cam, 3, (0.1, 0.1, 0.1), algo=1)
+        fs1 = _stages(sc, cam, 3, (0.1, 0.1, 0.1), algo=BINNING_GLOBAL_SORT)
         assert np.array_equal(pu.as_u32(fs1["point_list"]), b["point_list"])
         h = pu.run_hip(sc, cam, 3, (0.1, 0.1, 0.1), grads=grads)
         assert pu.nrm_err(h["color"], o["color"]) < TOL
@@ -357,7 +359,7 @@ def test_full_size_properties(name):
     a, T = fs["alpha"][0], fs["final_T"]
     assert float((a + T - 1).abs().max()) < 1e-5
     assert float(a.min()) >= 0.0 and float(a.max()) <= 1.0 + 1e-6
-    fs2 = _stages(sc, cam, 3, (0.0, 0.0, 0.0), algo=1)        # the global 64-bit sort gives the identical list
+    fs2 = _stages(sc, cam, 3, (0.0, 0.0, 0.0), algo=BINNING_GLOBAL_SORT)        # the global 64-bit sort gives the identical list
     assert torch.equal(fs["point_list"], fs2["point_list"]) and torch.equal(fs["ranges"], fs2["ranges"])
     assert torch.equal(fs["keys_sorted"], fs2["keys_sorted"])
     assert torch.equal(fs["color"], fs2["color"]) and torch.equal(fs["depth"], fs2["depth"])
@@ -464,7 +466,7 @@ def test_tile_sort_handles_long_lists_and_depth_ties():
         sc = syn.Scene(means, torch.full((P, 3), 0.004), torch.tensor([[1.0, 0, 0, 0]]).repeat(P, 1),
                        torch.full((P, 1), 0.02), torch.rand(P, 16, 3, generator=g) * 0.1)
         outs = []
-        for algo in (0, 1):
+        for algo in (BINNING_AUTO, BINNING_GLOBAL_SORT):
             fs = _stages(sc, cam, 0, (0.0, 0.0, 0.0), algo=algo)
             outs.append(fs)
         a, b = outs
@@ -489,7 +491,7 @@ def test_tile_sort_handles_long_lists_and_depth_ties():
         means = torch.cat([xy * z[:, None], z[:, None]], 1)
         sc = syn.Scene(means, torch.full((P, 3), 0.004), torch.tensor([[1.0, 0, 0, 0]]).repeat(P, 1),
                        torch.full((P, 1), 0.02), torch.rand(P, 16, 3, generator=g) * 0.1)
-        a, b = (_stages(sc, cam, 0, (0.0, 0.0, 0.0), algo=algo) for algo in (0, 1))
+        a, b = (_stages(sc, cam, 0, (0.0, 0.0, 0.0), algo=algo) for algo in (BINNING_AUTO, BINNING_GLOBAL_SORT))
         assert a["num_rendered"] == b["num_rendered"] >= P
         assert torch.equal(a["point_list"], b["point_list"])
         assert torch.equal(a["keys_sorted"], b["keys_sorted"])
@@ -670,13 +672,13 @@ def test_huge_image_falls_back_to_global_sort_and_million_gaussians():
     satisfies the list invariants."""
     from scgaussian_amd import _lib
     lib = _lib.load()
-    assert lib.scg_binning_accepts_bound(1000, 7680, 4320, 0) == 0
-    assert lib.scg_binning_accepts_bound(1000, 1920, 1080, 0) == 1
+    assert lib.scg_binning_accepts_bound(1000, 7680, 4320, BINNING_AUTO) == 0
+    assert lib.scg_binning_accepts_bound(1000, 1920, 1080, BINNING_AUTO) == 1
     W, H, P = 7680, 4320, 3000
     sc = syn.make_scene(P, W, H, seed=9, log_scale_mean=-2.5)
     cam = syn.default_camera(W, H)
-    a = _stages(sc, cam, 1, (0.0, 0.0, 0.0), algo=0)
-    b = _stages(sc, cam, 1, (0.0, 0.0, 0.0), algo=1)
+    a = _stages(sc, cam, 1, (0.0, 0.0, 0.0), algo=BINNING_AUTO)
+    b = _stages(sc, cam, 1, (0.0, 0.0, 0.0), algo=BINNING_GLOBAL_SORT)
     assert a["num_rendered"] == b["num_rendered"] > P
     assert torch.equal(a["point_list"], b["point_list"]) and torch.equal(a["ranges"], b["ranges"])
     assert torch.equal(a["color"], b["color"])
@@ -1097,13 +1099,13 @@ def test_skipped_rare_sort_launch_and_the_forward_blends_fallback_for_a_long_lis
         wide = scene(2.5, False)                                # lists of a few hundred entries at most
         R.forward_stages(st, wide.means3D, wide.opacities, shs=wide.shs, scales=wide.scales, rotations=wide.rotations)
         out, pl, fr = one_call(wide)                            # first one-call render of the frame: word unknown (-1 -> launch)
-        assert check(wide, out, pl) <= 1536 and int(fr.long_np[0]) == 0 and R._rare_options(fr.long_np) == 8
+        assert check(wide, out, pl) <= 1536 and int(fr.long_np[0]) == 0 and R._rare_options(fr.long_np) == FORWARD_SKIP_RARE_SORT
         out, pl, fr2 = one_call(wide)                           # second: the launch is skipped (word == 0)
         assert fr2 is fr and check(wide, out, pl) <= 1536 and int(fr.long_np[0]) == 0
         # another background tensor (reference train.py:141 random_background): another frame, the camera's hints carry over
         st_bg = st._replace(bg=torch.tensor([0.5, 0.5, 0.5], device=wide.means3D.device))
         fr_bg = R._frame_for(st_bg, P, 16, wide.means3D.device, forward=True)
-        assert fr_bg is not fr and fr_bg.hints is fr.hints and R._rare_options(fr_bg.long_np) == 8
+        assert fr_bg is not fr and fr_bg.hints is fr.hints and R._rare_options(fr_bg.long_np) == FORWARD_SKIP_RARE_SORT
         for tied in (False, True):                              # ... and now the promise is wrong: lists of thousands of entries
             fr.long_np[0] = 0
             dense = scene(0.05, tied)
@@ -1118,13 +1120,14 @@ def test_skipped_rare_sort_launch_and_the_forward_blends_fallback_for_a_long_lis
             assert longest > 16384, longest
             # the next render of this camera knows: lists beyond the blend's own sort, and very long ones among them
             assert int(fr.long_np[0]) > 0 and int(fr.long_np[1]) > 0
-            assert R._rare_options(fr.long_np) == (16 | 32)     # -> split by depth + 8-wave work-list sort
+            # -> split by depth + 8-wave work-list sort
+            assert R._rare_options(fr.long_np) == (FORWARD_RARE_8WAVE | FORWARD_SPLIT_LONG_LISTS)
             out, pl, _ = one_call(dense)
             assert check(dense, out, pl) == longest
             # ... and with a bound that is too small for this scene while the split path is on: the lists are clipped (the split
             # and the 8-wave sort work on clipped ranges, nothing is written out of bounds), the binding sees num_rendered
             # and renders again with room for it
-            assert R._rare_options(fr.long_np) == (16 | 32)
+            assert R._rare_options(fr.long_np) == (FORWARD_RARE_8WAVE | FORWARD_SPLIT_LONG_LISTS)
             sp.cam_hint[(W, H, R._camera_key(st.viewmatrix))] = (30_000, 30_000, P)
             out, pl, _ = one_call(dense)
             assert out[4]["cap"] >= out[4]["num_rendered"] > 30_000

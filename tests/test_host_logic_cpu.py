@@ -9,6 +9,7 @@ import weakref
 import pytest
 import torch
 
+from scgaussian_amd import _counts as C
 from scgaussian_amd import _grads as G
 from scgaussian_amd import model_path as mp
 from scgaussian_amd import rasterizer as R
@@ -43,6 +44,79 @@ def test_a_settled_count_moves_the_cameras_capacity():
     R._settle_word(spec, w, 150_000)                             # clipped: counted, room for the count next time
     assert R._OVERFLOW["overflows"] == before["overflows"] + 1
     assert spec.cam_hint[key][0] >= 150_000 + 150_000 // 8 and spec.cam_hint[key][1:] == (150_000, 5000)
+
+
+def _capacity_by_hand(count):
+    """The policy's head-room formula written out: 12.5 % + 4 096 on top of the count, rounded up to 1/16 of its magnitude."""
+    need = int(count * 1.125) + 4096
+    grain = 1 << max(12, need.bit_length() - 4)
+    return -(-need // grain) * grain
+
+
+def test_capacity_lookup_order_camera_then_shape_then_first_sight():
+    spec = types.SimpleNamespace(hint={}, cam_hint={}, pending={})
+    W, H, cam = 640, 480, b"camera"
+    assert R._capacity_for(160_001) == _capacity_by_hand(160_001) == 196_608
+    # nothing known: the staged path — or the 4 P bound where a first sight may launch (model path, no host read)
+    assert C.lookup(spec, 5000, W, H, cam) is None and C.lookup(spec, 5000, W, H, cam, True) is None
+    assert C.lookup(spec, 5000, W, H, cam, False, True) == C.first_sight_capacity(5000) == _capacity_by_hand(20_000) == 28_672
+    # an unknown camera falls back to the shape's entry (whatever the mode), and only at this Gaussian count
+    spec.hint[(5000, W, H)] = 77_777
+    assert C.lookup(spec, 5000, W, H, cam) == C.lookup(spec, 5000, W, H, cam, True, True) == C.lookup_shape(spec, 5000, W, H) == 77_777
+    assert C.lookup(spec, 5001, W, H, cam) is None and C.lookup_shape(spec, 5001, W, H) is None
+    # a known camera at the same P: its stored capacity, before the shape's
+    spec.cam_hint[(W, H, cam)] = (100_000, 80_000, 5000)
+    assert C.lookup(spec, 5000, W, H, cam) == 100_000
+    assert C.lookup(spec, 5000, W, H, b"another") == 77_777 and C.lookup(spec, 5000, W + 16, H, cam) is None
+    # at a changed P: the last count rescaled by the ratio of the Gaussian counts (no shape entry at that P is needed)
+    assert C.lookup(spec, 10_000, W, H, cam) == _capacity_by_hand(int(80_000 * 10_000 / 5000) + 1) == 196_608
+    assert C.lookup(spec, 2500, W, H, cam) == _capacity_by_hand(int(80_000 * 2500 / 5000) + 1) == 49_152
+    # capturing: at least the 1.25x form, never below what the camera already has
+    assert C.lookup(spec, 5000, W, H, cam, True) == _capacity_by_hand(int(80_000 * 5000 / 5000 * 1.25) + 1) == 122_880
+    assert C.lookup(spec, 10_000, W, H, cam, True) == _capacity_by_hand(int(80_000 * 10_000 / 5000 * 1.25) + 1) == 229_376
+    spec.cam_hint[(W, H, cam)] = (400_000, 80_000, 5000)
+    assert C.lookup(spec, 5000, W, H, cam, True) == 400_000
+    assert spec.hint == {(5000, W, H): 77_777} and spec.cam_hint == {(W, H, cam): (400_000, 80_000, 5000)}      # a look-up writes nothing
+
+
+def test_capacity_commit_orders_and_bounds_both_tables():
+    spec = types.SimpleNamespace(hint={}, cam_hint={}, pending={})
+    W, H = 640, 480
+    for i in range(3):
+        C.commit(spec, 5000, W, H, i, 100_000 + i, 80_000 + i)
+    assert list(spec.cam_hint) == [(W, H, 0), (W, H, 1), (W, H, 2)] and spec.hint == {(5000, W, H): 100_002}
+    C.commit(spec, 6000, W, H, 0, 120_000, 90_000)               # the camera's entry moves to the recently-used end
+    assert list(spec.cam_hint) == [(W, H, 1), (W, H, 2), (W, H, 0)] and spec.cam_hint[(W, H, 0)] == (120_000, 90_000, 6000)
+    assert spec.hint == {(5000, W, H): 100_002, (6000, W, H): 120_000}
+    C.forget(spec, 6000, W, H, 0)                                # the bound no longer fits the tile-first binning: both entries go
+    assert list(spec.cam_hint) == [(W, H, 1), (W, H, 2)] and spec.hint == {(5000, W, H): 100_002}
+    C.forget(spec, 6000, W, H, 0)                                # (nothing there: nothing happens)
+    # 1 024 entries are kept as they are; with 1 025 present the 128 oldest go — never the one just written, although it was the oldest
+    spec.cam_hint = {(W, H, i): (1, 1, 5000) for i in range(1024)}
+    spec.hint = {(i, W, H): 1 for i in range(1023)}
+    C.commit(spec, 5000, W, H, 0, 2, 2)
+    assert len(spec.cam_hint) == 1024 and len(spec.hint) == 1024 and list(spec.cam_hint)[0] == (W, H, 1)
+    spec.cam_hint[(W, H, 1024)] = (1, 1, 5000)
+    C.commit(spec, 5001, W, H, 1, 3, 3)
+    assert list(spec.cam_hint) == [(W, H, i) for i in range(130, 1024)] + [(W, H, 0), (W, H, 1024), (W, H, 1)]
+    assert spec.cam_hint[(W, H, 1)] == (3, 3, 5001) and spec.cam_hint[(W, H, 0)] == (2, 2, 5000)
+    assert list(spec.hint) == [(i, W, H) for i in range(128, 1023)] + [(5000, W, H), (5001, W, H)] and spec.hint[(5001, W, H)] == 3
+    # a settled count writes through the same function: the camera's entry ends up last, the tables stay bounded
+    w = R._CountWord()
+    w.slot, w.np, w.ptr, w.cap, w.P, w.key, w.device_index, w.captured = 0, None, 0, 100_000, 5000, (W, H, 500), 0, False
+    spec.cam_hint.update({(W, H, i): (1, 1, 5000) for i in range(2000, 2128)})
+    assert len(spec.cam_hint) == 1025
+    R._settle_word(spec, w, 80_000)
+    assert len(spec.cam_hint) == 897 and list(spec.cam_hint)[-1] == (W, H, 500) and list(spec.cam_hint)[0] == (W, H, 258)
+    assert spec.cam_hint[(W, H, 500)] == (100_000, 80_000, 5000) and spec.hint[(5000, W, H)] == 100_000
+    # the staged forward's update knows a count and no camera: first the head-room formula, then kept while the count fits
+    spec = types.SimpleNamespace(hint={}, cam_hint={}, pending={})
+    C.commit_shape(spec, 5000, W, H, 160_001)
+    assert spec.hint == {(5000, W, H): 196_608} and spec.cam_hint == {}
+    C.commit_shape(spec, 5000, W, H, 170_000)
+    assert spec.hint == {(5000, W, H): 196_608}
+    C.commit_shape(spec, 5000, W, H, 196_608)
+    assert spec.hint == {(5000, W, H): _capacity_by_hand(196_608)} and spec.hint[(5000, W, H)] > 196_608 * 9 // 8
 
 
 def test_camera_identity_without_a_device_read():
