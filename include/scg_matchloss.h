@@ -40,6 +40,53 @@ SCG_API int scg_match_loss_pair(const float* depth, int32_t H, int32_t W, const 
                         const float* intr1, const float* w2c1, const float* uv1, int32_t M, float width, float height,
                         float* loss, float* grad_depth, void* stream);
 
+/* ---- The ray-depth init stage (train.py:49-95 of the reference) ------------------------------------------------------------
+ *
+ * 2 000 Adam iterations on the per-match ray depths z_val against GaussianModel.get_matchloss_from_base
+ * (scene/gaussian_model.py:175-239), keeping for every match the depth at which its own loss term was smallest.  Once the
+ * number of valid matches of a view pair is known every match is independent of every other, so one thread carries one match
+ * through n_steps consecutive iterations in registers: loss term, gradient, best-state rule, one Adam step.
+ *
+ * One flat arena over all ORDERED view pairs (a -> b), N = sum of their match counts.  Per element:
+ *   rays_o (N,3), rays_d (N,3)   the ray of the match in view a
+ *   uv_t (N,2)                   the matched pixel in the target view b (8-byte aligned)
+ *   wgt (N)                      1 / (valid matches of the pair) where mask_a * mask_b > 0, else 0 (all 0 for a pair without
+ *                                a valid match: its elements get no gradient and never move)
+ * State, fp32 (N) each: z, exp_avg, exp_avg_sq, best_z, min_loss.
+ * Per ordered pair one ScgInitSegment of a DEVICE table (any number of them; every element lies in exactly one). */
+typedef struct ScgInitSegment {
+    int32_t offset;              /* first element */
+    int32_t count;               /* matches of this ordered pair */
+    float width, height;         /* the normalisation (the reference takes them from the earlier view of the pair) */
+    float intr[9];               /* intrinsics of the target view b, row-major */
+    float w2c[12];               /* first three rows of its world-to-camera matrix, row-major */
+} ScgInitSegment;
+
+#define SCG_INIT_STAGE_MAX_STEPS 4096
+
+/* Per element and iteration (global index it = first_iter + k, k < n_steps):
+ *   (X,Y,Z) = K_b (R_b (o + d z) + t_b);  px = X / (Z + 1e-8);  py = Y / (Z + 1e-8)
+ *   ml = 0.5 (|px - u| / width + |py - v| / height)           the unmasked loss_state entry
+ *   g  = loss_scale * wgt * d ml / d z                         (sign(0) = 0)
+ *   it == 0: min_loss = ml, and best_z = z AFTER this iteration's step (the reference's best state aliases the parameter
+ *            through the first step); it == 1: min_loss = min_loss < ml ? min_loss : ml, best_z untouched;
+ *   it >= 2: best_z = min_loss < ml ? best_z : z (before the step), then min_loss as for it == 1.  A NaN on either side takes
+ *            the current value, as torch.where does.
+ *   one Adam step (torch's single-tensor order, betas (beta1, beta2), eps, learning rate lr, step count it + 1).
+ * n_steps >= 1 (run): inputs are read once, the five state arrays are written once.  partials, when not NULL, receives for every
+ *   iteration k and workgroup w the sum of wgt * ml over the workgroup's elements, at partials[k * W + w], in a fixed order (no
+ *   atomics: bitwise reproducible); the sum of row k is the reference's match loss of that iteration (without the NaN of a
+ *   pair that has no valid match: the caller knows its counts).  loss_state and grad are not used.
+ * n_steps == 0 (evaluate): writes loss_state (N) = ml and grad (N) = g where not NULL, and one row of partials; changes no state
+ *   (exp_avg, exp_avg_sq, best_z and min_loss may be NULL).
+ * partials_bytes must be at least scg_init_stage_partials_bytes(N, n_steps) = max(n_steps, 1) * W * 4. */
+SCG_API size_t scg_init_stage_partials_bytes(int32_t N, int32_t n_steps);   /* 0 for arguments out of range */
+SCG_API int scg_init_stage_run(const ScgInitSegment* segments, int32_t nseg, int32_t N, const float* rays_o,
+                       const float* rays_d, const float* uv_t, const float* wgt, float* z, float* exp_avg,
+                       float* exp_avg_sq, float* best_z, float* min_loss, int32_t first_iter, int32_t n_steps, double lr,
+                       double beta1, double beta2, double eps, float loss_scale, float* loss_state, float* grad,
+                       float* partials, size_t partials_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,15 @@ class ScgAdamSegment(C.Structure):
         ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
 
 
+INIT_STAGE_MAX_STEPS = 4096
+
+
+class ScgInitSegment(C.Structure):
+    """One ordered view pair of the init stage's device table (include/scg_matchloss.h ScgInitSegment)."""
+    _fields_ = [("offset", C.c_int32), ("count", C.c_int32), ("width", C.c_float), ("height", C.c_float),
+                ("intr", C.c_float * 9), ("w2c", C.c_float * 12)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/scg_raster.h
 _P = C.c_void_p
 SYMBOLS = {
@@ -99,6 +108,9 @@ SYMBOLS = {
     "scg_image_loss_forward_combined": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, C.c_size_t, _P]),
     "scg_image_loss_backward_combined": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, _P, _P]),
     "scg_match_loss_pair": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 9 + [C.c_int32, C.c_float, C.c_float, _P, _P, _P]),
+    "scg_init_stage_partials_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "scg_init_stage_run": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 4 + [_P] * 5 + [C.c_int32, C.c_int32] + [C.c_double] * 4
+                           + [C.c_float, _P, _P, _P, C.c_size_t, _P]),
     "scg_knn3_scratch_bytes": (C.c_size_t, [C.c_int64]),
     "scg_knn3_mean_dist2_ws": (C.c_int, [_P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "scg_geometry_backward": (C.c_int, [C.POINTER(ScgFrame)] + [_P] * 7 + [_P] * 3 + [_P] * 8 + [C.c_int32, _P]),
@@ -145,7 +157,8 @@ def open_library(path: str) -> C.CDLL:
         fn.argtypes = args
     if lib.scg_abi_version() != ABI_VERSION:
         raise ScgError(f"ABI version mismatch: library {lib.scg_abi_version()} != binding {ABI_VERSION}")
-    for which, struct in enumerate((ScgFrame, ScgWorkspaceLayout, ScgStageEvents, ScgModel, ScgModelGrads, ScgAdamSegment)):
+    for which, struct in enumerate((ScgFrame, ScgWorkspaceLayout, ScgStageEvents, ScgModel, ScgModelGrads, ScgAdamSegment,
+                                    ScgInitSegment)):
         if lib.scg_struct_bytes(which) != C.sizeof(struct):
             raise ScgError(f"struct layout mismatch: {struct.__name__} is {lib.scg_struct_bytes(which)} bytes in the library, "
                            f"{C.sizeof(struct)} in the binding")

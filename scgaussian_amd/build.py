@@ -4,7 +4,7 @@
 
 hipcc cross-compiles without a GPU.  The .so is git-ignored but travels to the GPU box with the
 gpurun snapshot.  geometry.hip is compiled with -ffp-contract=off (bit-exact tile assignment).
-optim.hip is too: Adam rounded where torch rounds it.
+optim.hip and initstage.hip are too: Adam rounded where torch rounds it.
 """
 from __future__ import annotations
 
@@ -36,8 +36,9 @@ SOURCES = {
     "loss.hip": [],
     "matchloss.hip": [],
     "optim.hip": ["-ffp-contract=off"],           # Adam in torch's rounding order (no fused multiply-adds)
+    "initstage.hip": ["-ffp-contract=off"],       # the init stage's Adam: the same arithmetic (csrc/adam_math.h)
 }
-HEADERS = [os.path.join(CSRC, "scg_common.h"), os.path.join(CSRC, "tile_sort.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "scg_debug.h"), os.path.join(INCLUDE, "scg_raster.h"), os.path.join(INCLUDE, "scg_knn.h"), os.path.join(INCLUDE, "scg_loss.h"), os.path.join(INCLUDE, "scg_matchloss.h")]
+HEADERS = [os.path.join(CSRC, "scg_common.h"), os.path.join(CSRC, "tile_sort.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "scg_debug.h"), os.path.join(CSRC, "adam_math.h"), os.path.join(INCLUDE, "scg_raster.h"), os.path.join(INCLUDE, "scg_knn.h"), os.path.join(INCLUDE, "scg_loss.h"), os.path.join(INCLUDE, "scg_matchloss.h")]
 
 
 def _hipcc() -> str:

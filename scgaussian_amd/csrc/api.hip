@@ -7,6 +7,7 @@
 
 #include "scg_common.h"
 #include "scg_debug.h"
+#include "../../include/scg_matchloss.h"
 
 #include <atomic>
 #include <chrono>
@@ -105,6 +106,7 @@ size_t scg_struct_bytes(int32_t which) {
         case 3: return sizeof(ScgModel);
         case 4: return sizeof(ScgModelGrads);
         case 5: return sizeof(ScgAdamSegment);
+        case 6: return sizeof(ScgInitSegment);
         default: return 0;
     }
 }

@@ -20,6 +20,7 @@
 // densify_stats_kernel: the densification statistics of one render (train.py:191-192, gaussian_model.py:932-934), one thread per
 // Gaussian, no atomics (each Gaussian's three words belong to its thread).
 #include "scg_common.h"
+#include "adam_math.h"
 
 namespace scg {
 
@@ -53,18 +54,7 @@ struct AdamArgs {
     uint32_t* ws;
 };
 
-struct AdamCoef {
-    float w1, b2f, w2, eps, bc2s, nss;    // nss = -(lr / bc1) as fp32
-};
-
-// torch's order: exp_avg.lerp_(g, 1-b1); exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2);
-// denom = exp_avg_sq.sqrt() / sqrt(bc2) + eps; param.addcdiv_(exp_avg, denom, -lr/bc1)
-__device__ __forceinline__ void adam_update(float& p, float& m, float& v, float g, const AdamCoef& c) {
-    m = m + c.w1 * (g - m);                       // lerp with a weight < 0.5
-    v = v * c.b2f + c.w2 * g * g;
-    const float denom = sqrtf(v) / c.bc2s + c.eps;
-    p = p + c.nss * (m / denom);
-}
+// (AdamCoef, adam_bias_coefs and adam_update: adam_math.h, shared with the init stage)
 
 __device__ __forceinline__ uint32_t live_col(float m, float v, uint32_t col) {
     return (m != 0.f || v != 0.f) ? col + 1 : 0u;
@@ -109,14 +99,10 @@ __global__ __launch_bounds__(kAdamBlock) void adam_step_kernel(AdamArgs a) {
         const AdamSegDev& sg = a.seg[s];
         // the step this launch takes, as torch forms it: step_t += 1 (fp32), then Python floats (double)
         const float step1 = sg.step[0] + 1.0f;
-        const double t = (double)step1;
-        const double bc1 = 1.0 - pow(sg.b1, t);
-        const double bc2 = 1.0 - pow(sg.b2, t);
         const double lr = a.lr_table ? a.lr_table[s] : sg.lr;
         AdamCoef c;
         c.w1 = sg.w1; c.b2f = sg.b2f; c.w2 = sg.w2; c.eps = sg.eps;
-        c.bc2s = (float)sqrt(bc2);
-        c.nss = (float)(-(lr / bc1));
+        adam_bias_coefs(sg.b1, sg.b2, lr, (double)step1, c.bc2s, c.nss);
         const int64_t e0 = (int64_t)(b - sg.first_block) * kAdamChunk;
         const int64_t e1 = min(e0 + (int64_t)kAdamChunk, sg.numel);
         rows = sg.row_len > 0;
