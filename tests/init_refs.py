@@ -1,4 +1,5 @@
-"""The reference's init stage as a plain torch loop, and the scenes of tests/golden/ref_init.npz as view_gs dictionaries.
+"""The reference's init stage as a plain torch loop, and the scenes of tests/golden/ref_init.npz and ref_init_edges.npz as view_gs
+dictionaries.
 
 `matchloss_from_base` restates GaussianModel.get_matchloss_from_base (scene/gaussian_model.py:175-239) and `torch_init_loop` the
 loop around it (train.py:57-95) in this project's words; tests/test_init_stage_cpu.py holds both to the arrays the reference's
@@ -19,18 +20,56 @@ def fixture():
     return np.load(os.path.join(GOLDEN, "ref_init.npz"))
 
 
+def fixture_edges():
+    return np.load(os.path.join(GOLDEN, "ref_init_edges.npz"))
+
+
+_IN_KEYS = ("uv", "rays_o", "rays_d", "cam_rays_d", "blender_mask", "z_val")
+
+
 def load_scene(fx, tag: str, device="cpu", dtype=torch.float32):
-    """view_gs of scene `tag` ("A" or "B") with fresh z_val leaves."""
-    cams = np.load(os.path.join(GOLDEN, "ref_model.npz"))
-    W, H = (int(v) for v in fx["wh"])
+    """view_gs of scene `tag` with fresh z_val leaves, the views in the fixture's dictionary order.  Scenes "A" and "B"
+    (ref_init.npz) share one size and take the cameras of ref_model.npz; a scene that carries <tag>_wh / <tag>_intr / <tag>_w2c
+    (one row per view, in that order: "C" and "D" of ref_init_edges.npz) has its own, and its inputs flat in arena order."""
     t = lambda a: torch.from_numpy(np.asarray(a)).to(dtype).to(device)                     # noqa: E731
-    vg = {f"view{i}": {"width": W, "height": H, "intr": t(cams["cam_intr"][i]), "w2c": t(cams["cam_w2c"][i]), "match_infos": {}}
-          for i in fx[f"{tag}_views"]}
-    for a, b in fx[f"{tag}_pairs"]:
-        mi = {k: t(fx[f"{tag}_in_{a}{b}_{k}"]) for k in ("uv", "rays_o", "rays_d", "cam_rays_d", "blender_mask", "z_val")}
+    views = [int(i) for i in fx[f"{tag}_views"]]
+    if f"{tag}_wh" in fx.files:
+        wh, intr, w2c = fx[f"{tag}_wh"], fx[f"{tag}_intr"], fx[f"{tag}_w2c"]
+        vg = {f"view{i}": {"width": int(wh[n][0]), "height": int(wh[n][1]), "intr": t(intr[n]), "w2c": t(w2c[n]), "match_infos": {}}
+              for n, i in enumerate(views)}
+    else:
+        cams = np.load(os.path.join(GOLDEN, "ref_model.npz"))
+        W, H = (int(v) for v in fx["wh"])
+        vg = {f"view{i}": {"width": W, "height": H, "intr": t(cams["cam_intr"][i]), "w2c": t(cams["cam_w2c"][i]), "match_infos": {}}
+              for i in views}
+    off = 0
+    for n, (a, b) in enumerate(fx[f"{tag}_pairs"]):
+        if f"{tag}_counts" in fx.files:
+            M = int(fx[f"{tag}_counts"][n])
+            mi = {k: t(fx[f"{tag}_in_{k}"][off:off + M]) for k in _IN_KEYS}
+            off += M
+        else:
+            mi = {k: t(fx[f"{tag}_in_{a}{b}_{k}"]) for k in _IN_KEYS}
         mi["z_val"] = mi["z_val"].clone().requires_grad_(True)
         vg[f"view{a}"]["match_infos"][f"view{b}"] = mi
     return vg
+
+
+def z_of(vg):
+    """{a: {b: z_val}}: the depths of view_gs in the nested shape `flat` takes."""
+    return {a: {b: mi["z_val"] for b, mi in v["match_infos"].items()} for a, v in vg.items()}
+
+
+def held(what, got, r64, r32, grad=False):
+    """max|got - r64| <= max(4 * e32, floor) (loss_refs.held_to): e32 = max|r32 - r64|, floor = GRAD_FLOOR * max|r64| for a gradient,
+    FLOOR * max(1, max|r64|) for every other array."""
+    import loss_refs
+    as64 = lambda a: np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, dtype=np.float64)          # noqa: E731
+    got, r64, r32 = as64(got), as64(r64), as64(r32)
+    assert got.shape == r64.shape == r32.shape, (what, got.shape, r64.shape, r32.shape)
+    scale = float(np.abs(r64).max())
+    floor = GRAD_FLOOR * scale if grad else FLOOR * max(1.0, scale)
+    loss_refs.held_to(f"init {what}", float(np.abs(got - r64).max()), float(np.abs(r32 - r64).max()), floor, r64.size)
 
 
 def arena(vg):

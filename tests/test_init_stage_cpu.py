@@ -1,5 +1,5 @@
-"""The init stage without a GPU: the fixture the reference's own code produced (tests/golden/ref_init.npz), the plain torch
-restatement held to it, the packing of view_gs into the arena, the splitting of a schedule into launches (against a fake
+"""The init stage without a GPU: the fixtures the reference's own code produced (tests/golden/ref_init.npz, ref_init_edges.npz), the
+plain torch restatement held to them, the packing of view_gs into the arena, the splitting of a schedule into launches (against a fake
 library) and the argument validation of the C entry points."""
 import ctypes as C
 
@@ -15,6 +15,11 @@ from scgaussian_amd import init_stage as IS
 @pytest.fixture(scope="module")
 def fx():
     return ir.fixture()
+
+
+@pytest.fixture(scope="module")
+def fe():
+    return ir.fixture_edges()
 
 
 def _close(a32, a64, floor):
@@ -72,6 +77,98 @@ def test_plain_torch_restatement_reproduces_the_reference_records(fx):
     assert np.abs(ir.flat(vg, out["best"]).numpy() - fx["A_f64_final_best"]).max() <= 1e-9
     assert np.abs(ir.flat(vg, out["min_loss"]).numpy() - fx["A_f64_final_min"]).max() <= 1e-9
     assert np.abs(np.array([float(v) for v in out["losses"]]) - fx["A_f64_losses"]).max() <= 1e-10
+
+
+VALUE_KEYS = ("losses", "it0_loss", "it0_loss_state", "final_z", "final_best", "final_min", "after1_z", "after1_best", "after1_min",
+              "after2_z", "after2_best", "after2_min", "loaded_z")
+
+
+def test_edge_fixture_holds_what_it_was_built_for(fe):
+    # scene C: three sizes, three intrinsics, a dictionary order that is not the name order, pairs of 63, 64 and 2
+    assert list(fe["C_views"]) == [2, 0, 1] and [tuple(p) for p in fe["C_pairs"]] == [(2, 0), (2, 1), (0, 2), (0, 1), (1, 2), (1, 0)]
+    assert list(fe["C_counts"]) == [63, 64, 63, 2, 64, 2] and int(fe["C_iters"]) == 12 and list(fe["C_halve_at"]) == [6]
+    assert [tuple(r) for r in fe["C_wh"]] == [(64, 96), (96, 64), (80, 48)]
+    assert len({fe["C_intr"][n].tobytes() for n in range(3)}) == 3 and len({fe["C_w2c"][n].tobytes() for n in range(3)}) == 3
+    # scene D: seven views, 42 segments of 1, 2, 3 and 5 matches, 64 < N < 128, a segment across element 64
+    counts = fe["D_counts"]
+    offs = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    assert len(fe["D_views"]) == 7 and len(counts) == 42 and set(counts) == {1, 2, 3, 5} and 64 < counts.sum() < 128
+    assert list(fe["D_views"]) != sorted(fe["D_views"]) and int(fe["D_iters"]) == 12 and len(fe["D_halve_at"]) == 0
+    assert bool(((offs < 64) & (offs + counts > 64)).any())
+    for tag in "CD":
+        N = int(fe[f"{tag}_counts"].sum())
+        for k in VALUE_KEYS:
+            assert fe[f"{tag}_f32_{k}"].dtype == np.float32 and fe[f"{tag}_f64_{k}"].dtype == np.float64
+            assert _close(fe[f"{tag}_f32_{k}"], fe[f"{tag}_f64_{k}"], ir.FLOOR), (tag, k)
+        g64 = fe[f"{tag}_f64_it0_grad"]
+        assert g64.shape == (N,) and fe[f"{tag}_f64_losses"].shape == (12,) and fe[f"{tag}_in_rays_o"].shape == (N, 3)
+        assert float(np.abs(fe[f"{tag}_f32_it0_grad"] - g64).max()) <= ir.GRAD_FLOOR * float(np.abs(g64).max())
+        vg = ir.load_scene(fe, tag)
+        assert list(vg) == [f"view{i}" for i in fe[f"{tag}_views"]]
+        masked = sum(int(((vg[a]["match_infos"][b]["blender_mask"] * vg[b]["match_infos"][a]["blender_mask"]) <= 0).sum())
+                     for a, b in ir.arena(vg))
+        assert int((g64 == 0).sum()) == masked and 0 < masked < N
+        for p in ("f32", "f64"):
+            assert np.array_equal(fe[f"{tag}_{p}_after2_best"], fe[f"{tag}_{p}_after1_z"])
+            assert np.array_equal(fe[f"{tag}_{p}_after1_min"], fe[f"{tag}_{p}_it0_loss_state"])
+            assert np.array_equal(fe[f"{tag}_{p}_loaded_z"], fe[f"{tag}_{p}_final_best"])
+
+
+@pytest.mark.parametrize("tag", ["C", "D"])
+def test_plain_torch_restatement_reproduces_the_edge_records(fe, tag):
+    """Unequal views: the size of the EARLIER view in dictionary order, the camera of the TARGET view.  In fp64 the restatement is
+    the record up to the order of its matrix products; in fp32 it is held to the fp64 record as the kernel is: max(4 * e32, floor),
+    e32 = the reference's own fp32 record against its fp64 one."""
+    iters, halve_at = int(fe[f"{tag}_iters"]), tuple(int(h) for h in fe[f"{tag}_halve_at"])
+    rec = lambda p, k: fe[f"{tag}_{p}_{k}"]                                                  # noqa: E731
+    grad_of = lambda vg: ir.flat(vg, {a: {b: mi["z_val"].grad for b, mi in v["match_infos"].items()} for a, v in vg.items()})   # noqa: E731
+    for dtype in (torch.float64, torch.float32):
+        vg = ir.load_scene(fe, tag, dtype=dtype)
+        loss, state = ir.matchloss_from_base(vg)
+        (5 * loss).backward()
+        it0 = {"it0_loss": np.array(5 * float(loss.detach())), "it0_loss_state": ir.flat(vg, state), "it0_grad": grad_of(vg)}
+        vg = ir.load_scene(fe, tag, dtype=dtype)
+        out = ir.torch_init_loop(vg, iters, halve_at)
+        run = {"final_z": ir.flat(vg, ir.z_of(vg)), "final_best": ir.flat(vg, out["best"]), "final_min": ir.flat(vg, out["min_loss"]),
+               "losses": np.array([float(v) for v in out["losses"]])}
+        if dtype == torch.float64:
+            assert abs(float(it0["it0_loss"]) - float(rec("f64", "it0_loss"))) <= 1e-12
+            assert np.abs(it0["it0_loss_state"].numpy() - rec("f64", "it0_loss_state")).max() <= 1e-12
+            assert np.abs(it0["it0_grad"].numpy() - rec("f64", "it0_grad")).max() <= 1e-12 * np.abs(rec("f64", "it0_grad")).max()
+            for k in ("final_z", "final_best", "final_min"):
+                assert np.abs(run[k].numpy() - rec("f64", k)).max() <= 1e-9, k
+            assert np.abs(run["losses"] - rec("f64", "losses")).max() <= 1e-10
+        else:
+            for k, v in {**it0, **run}.items():
+                ir.held(f"cpu fp32 restatement {tag} {k}", v, rec("f64", k), rec("f32", k), grad=(k == "it0_grad"))
+
+
+def test_arena_packing_of_unequal_views(fe):
+    """Scene C: width and height come from the earlier view in DICTIONARY order (view2 before view0 before view1), K and w2c from
+    the target view."""
+    vg = ir.load_scene(fe, "C")
+    st = IS.InitStage.from_view_gs(vg)
+    assert [(a, b) for a, b, _o, _m in st.segments] == ir.arena(vg) and st.N == 258
+    table = np.frombuffer(st.table.numpy().tobytes(), dtype=IS._SEG_DTYPE)
+    first = {("view2", "view0"): "view2", ("view0", "view2"): "view2", ("view2", "view1"): "view2", ("view1", "view2"): "view2",
+             ("view0", "view1"): "view0", ("view1", "view0"): "view0"}
+    sizes = {"view2": (64, 96), "view0": (96, 64), "view1": (80, 48)}
+    for rec, (a, b, off, M) in zip(table, st.segments):
+        assert (int(rec["offset"]), int(rec["count"])) == (off, M)
+        assert (float(rec["width"]), float(rec["height"])) == sizes[first[a, b]], (a, b)
+        assert np.array_equal(rec["intr"], vg[b]["intr"].numpy().reshape(9)) and not np.array_equal(rec["intr"], vg[a]["intr"].numpy().reshape(9))
+        assert np.array_equal(rec["w2c"], vg[b]["w2c"].numpy()[:3].reshape(12))
+
+
+def test_partials_bytes_at_the_launch_limits():
+    lib = _lib.load()
+    for N in (1, 64, 65):
+        for n in (0, 1, 64, 65, 4096):
+            assert lib.scg_init_stage_partials_bytes(N, n) == max(n, 1) * ((N + 63) // 64) * 4, (N, n)
+        assert lib.scg_init_stage_partials_bytes(N, 4097) == 0 and lib.scg_init_stage_partials_bytes(N, -1) == 0
+    for n in (0, 1, 4096, 4097, -1):
+        assert lib.scg_init_stage_partials_bytes(0, n) == 0
+    assert _lib.INIT_STAGE_MAX_STEPS == IS.MAX_STEPS == 4096
 
 
 def test_arena_packing(fx):
