@@ -129,7 +129,7 @@ SCG_API int32_t scg_abi_version(void);
 /* sizeof(ScgFrame) / sizeof(ScgWorkspaceLayout) / sizeof(ScgStageEvents) as this library was compiled: a binding that
  * declares the structs itself (ctypes, cgo, JNA) compares them with its own before the first call. */
 SCG_API size_t scg_struct_bytes(int32_t which /* 0 ScgFrame, 1 ScgWorkspaceLayout, 2 ScgStageEvents, 3 ScgModel, 4 ScgModelGrads,
-                                                 5 ScgAdamSegment */);
+                                                 5 ScgAdamSegment, 6 ScgInitSegment, 7 ScgDensifyScatter */);
 
 /* ---- stage 1: per-Gaussian geometry (replaces the preprocess step of upstream rasterize_gaussians;
  *      inputs as passed at reference gaussian_renderer/__init__.py:100-108) ---------------------------
@@ -477,6 +477,71 @@ SCG_API int scg_adam_step(const ScgAdamSegment* segments, int32_t nseg, const do
  * max_radii2D[i] = max(max_radii2D[i], (float)radii[i]).  accum, denom, max_radii2D: P floats each. */
 SCG_API int scg_densify_stats(int32_t P, const int32_t* radii, const float* means2D_grad, int64_t grad_row_stride,
                               float* accum, float* denom, float* max_radii2D, void* stream);
+
+/* ---- Densify-and-prune and the opacity reset (csrc/densify.hip) ------------------------------------------------------------
+ * GaussianModel.densify_and_prune (reference scene/gaussian_model.py:758-930, train.py:195-197) as classify / scan / scatter with
+ * one host read in between, and reset_opacity (:644-651) as one launch.  Additive to ABI 10.
+ *
+ * Source index i runs over [0, P), P = ray.count + bg.count, the ray-bound set first.  With g = accum[i] / denom[i] (NaN -> 0,
+ * inf stays), s = max_k exp(scaling[i][k]) and o = sigmoid(opacity[i]):
+ *   clone  (|g| >= max_grad and s <= dense_scale)   one new background row: xyz = rayo + rayd * zval (one multiply, one add) or the
+ *                                                   background xyz; every other attribute copied
+ *   split  (g >= max_grad and s > dense_scale)      two new background rows c = 0, 1: xyz = R(q) (exp(scaling) * noise[c][i]) + xyz_i,
+ *                                                   scaling = log(exp(scaling) / 1.6), the rest copied.  A split background source is
+ *                                                   removed; a split ray-bound source stays with its RAW scaling row divided by 1.6.
+ *   prune  (background rows only: originals, clones, children)   o < min_opacity, or — when big_scale >= 0 — the row's own
+ *                                                   max_k exp(scaling) > big_scale (for a child: its new scaling).
+ * The new background set: surviving originals in order, surviving clones in source order, surviving children of copy 0, then of
+ * copy 1 (both children of a source share their fate).  The four section sizes are what the caller reads between the two calls.
+ * dense_scale = percent_dense * extent and big_scale = 0.2 * extent (or < 0: no world-size term), rounded to fp32 by the caller. */
+
+/* Bytes of the workspace both calls share for P sources (0 for P < 0): 8 words (the first four are the section totals: originals,
+ * clones, children of copy 0, children of copy 1), three words per workgroup of 256 sources, one fate byte per source. */
+SCG_API size_t scg_densify_workspace_bytes(int32_t P);
+/* Two launches: classify (one thread per source: the fate byte with the final prune folded in, per-workgroup counts) and an
+ * exclusive scan of the counts by one workgroup in a fixed order (no atomics).  Afterwards the first four uint32 words of the
+ * workspace hold the section totals.  accum, denom: P floats each (the statistics tensors as they are, ray-bound set first). */
+SCG_API int scg_densify_classify(const ScgModel* model, const float* accum, const float* denom, float max_grad, float min_opacity,
+                                 float dense_scale, float big_scale, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The six tensors of a background set, or one Adam moment of each (shapes of ScgModelSet: xyz (n,3), features_dc (n,1,3),
+ * features_rest (n,15,3), opacity (n,1), scaling (n,3), rotation (n,4)). */
+typedef struct ScgDensifyTensors {
+    float* xyz;
+    float* features_dc;
+    float* features_rest;
+    float* opacity;
+    float* scaling;
+    float* rotation;
+} ScgDensifyTensors;
+
+typedef struct ScgDensifyScatter {
+    int32_t out_rows;                      /* rows of every output tensor: the sum of the four section totals.  No row at or beyond
+                                              it is written, whatever the workspace says. */
+    ScgDensifyTensors out;                 /* the new background set: fully written */
+    ScgDensifyTensors out_exp_avg;         /* its Adam moments: gathered for surviving originals, zero for new rows.  An entry is */
+    ScgDensifyTensors out_exp_avg_sq;      /* NULL (in both) for a group without optimizer state: nothing is written for it */
+    ScgDensifyTensors in_exp_avg;          /* the moments of the current background set (bg.count rows): required wherever the */
+    ScgDensifyTensors in_exp_avg_sq;       /* output entry is given and bg.count > 0 */
+    float* ray_scaling;                    /* = model->ray.scaling, writable: rows of split sources are divided by 1.6 in place */
+    float* ray_scaling_exp_avg;            /* (ray.count,3) zeroed entirely; NULL: no state */
+    float* ray_scaling_exp_avg_sq;
+    float* accum;                          /* ray.count + out_rows floats each, zeroed: the statistics of the new model */
+    float* denom;
+    float* max_radii2D;
+    const float* noise;                    /* (2, P, 3) unit normal samples indexed by (copy, source) */
+} ScgDensifyScatter;                       /* scg_struct_bytes(7) */
+
+/* One launch on the workspace scg_densify_classify filled for the same model: ranks within a workgroup are recomputed from the
+ * fate bytes, rows are copied / computed into `out`, and the in-place edits listed above are made.  The model's tensors must not
+ * overlap any output. */
+SCG_API int scg_densify_scatter(const ScgModel* model, const ScgDensifyScatter* args, const void* workspace, size_t workspace_bytes,
+                                void* stream);
+
+/* reset_opacity: x = logit(min(sigmoid(x), 0.01)) over both raw opacity tensors in place, and the four moment tensors (NULL: no
+ * state) zeroed, in one launch. */
+SCG_API int scg_reset_opacity(int32_t n_ray, float* ray_opacity, float* ray_exp_avg, float* ray_exp_avg_sq, int32_t n_bg,
+                              float* bg_opacity, float* bg_exp_avg, float* bg_exp_avg_sq, void* stream);
 
 #ifdef __cplusplus
 }

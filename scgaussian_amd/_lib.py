@@ -83,6 +83,18 @@ class ScgInitSegment(C.Structure):
                 ("intr", C.c_float * 9), ("w2c", C.c_float * 12)]
 
 
+class ScgDensifyTensors(C.Structure):
+    """The six tensors of a background set, or one Adam moment of each (include/scg_raster.h ScgDensifyTensors)."""
+    _fields_ = [(n, C.c_void_p) for n in ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation")]
+
+
+class ScgDensifyScatter(C.Structure):
+    _fields_ = [("out_rows", C.c_int32)] + [(n, ScgDensifyTensors) for n in ("out", "out_exp_avg", "out_exp_avg_sq", "in_exp_avg",
+                                                                             "in_exp_avg_sq")] + [
+        (n, C.c_void_p) for n in ("ray_scaling", "ray_scaling_exp_avg", "ray_scaling_exp_avg_sq", "accum", "denom", "max_radii2D",
+                                  "noise")]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/scg_raster.h
 _P = C.c_void_p
 SYMBOLS = {
@@ -129,6 +141,10 @@ SYMBOLS = {
     "scg_adam_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "scg_adam_step": (C.c_int, [C.POINTER(ScgAdamSegment), C.c_int32, _P, _P, C.c_size_t, _P]),
     "scg_densify_stats": (C.c_int, [C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "scg_densify_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "scg_densify_classify": (C.c_int, [C.POINTER(ScgModel), _P, _P] + [C.c_float] * 4 + [_P, C.c_size_t, _P]),
+    "scg_densify_scatter": (C.c_int, [C.POINTER(ScgModel), C.POINTER(ScgDensifyScatter), _P, C.c_size_t, _P]),
+    "scg_reset_opacity": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -158,7 +174,7 @@ def open_library(path: str) -> C.CDLL:
     if lib.scg_abi_version() != ABI_VERSION:
         raise ScgError(f"ABI version mismatch: library {lib.scg_abi_version()} != binding {ABI_VERSION}")
     for which, struct in enumerate((ScgFrame, ScgWorkspaceLayout, ScgStageEvents, ScgModel, ScgModelGrads, ScgAdamSegment,
-                                    ScgInitSegment)):
+                                    ScgInitSegment, ScgDensifyScatter)):
         if lib.scg_struct_bytes(which) != C.sizeof(struct):
             raise ScgError(f"struct layout mismatch: {struct.__name__} is {lib.scg_struct_bytes(which)} bytes in the library, "
                            f"{C.sizeof(struct)} in the binding")

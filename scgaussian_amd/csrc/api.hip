@@ -107,6 +107,7 @@ size_t scg_struct_bytes(int32_t which) {
         case 4: return sizeof(ScgModelGrads);
         case 5: return sizeof(ScgAdamSegment);
         case 6: return sizeof(ScgInitSegment);
+        case 7: return sizeof(ScgDensifyScatter);
         default: return 0;
     }
 }

@@ -290,6 +290,14 @@ class ArenaAdam(torch.optim.Adam):
             slot[1] = ev
             d.synced = (tuple(gis), tuple(lrs))
 
+    def tensors_replaced(self) -> None:
+        """The caller replaced parameters or moments wholesale (densify.densify_and_prune): drop the cached segment tables, which
+        would keep the old tensors alive, and trust no watermark at the next step."""
+        for d in self._dev.values():
+            d.policy.invalidate()
+            d.tables.clear()
+            d.last_slots = []
+
     # ---- test access -----------------------------------------------------------------------------------------------------
     def live_columns(self) -> Dict[torch.Tensor, int]:
         """{row-segment parameter: its watermark after the latest step} (reads the device: tests and diagnostics only)."""
