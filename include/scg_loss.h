@@ -57,6 +57,42 @@ SCG_API int scg_image_loss_backward_combined(const float* img, const float* gt, 
                                              int32_t W, const float* upstream, float lambda_dssim, float* d_img,
                                              void* stream);
 
+/* ---- DTU scenes (csrc/dtumask.hip): what train.py runs only when "dtu" is in the source path ------------------------------
+ * Same conventions: caller-owned buffers, stream-ordered, int status, arguments validated before anything touches a device;
+ * counts and upstream gradients are read from DEVICE memory, so nothing here forces a host read and every call can be captured
+ * in a graph.
+ *
+ * Background mask (train.py:149-158).  gt: (3,H,W) fp32.  mask (H,W) uint8 = 1 where the pixel is dark (max over the channels
+ * < thr) and the run of dark pixels ending at its row in its column is at least min(row + 1, run) long — the closed form of the
+ * reference's 49 shifted products (run = 50).  gt_masked (3,H,W) = gt with the masked pixels zeroed; it MAY BE gt itself (the
+ * reference's in-place form) when thr > 0, since a zeroed pixel stays dark; thr <= 0 with aliasing, a partial overlap and
+ * run < 1 are refused with SCG_E_RANGE.  count: one uint32, the number of masked pixels (reset and written by this call).
+ * Comparisons only: the result is exact. */
+SCG_API int scg_dtu_bg_mask(const float* gt, int32_t H, int32_t W, float thr, int32_t run, uint8_t* mask, float* gt_masked,
+                            uint32_t* count, void* stream);
+/* rows of one row segment of the mask kernel (a segment re-reads up to run - 1 rows above itself): for tests at its edges */
+SCG_API int32_t scg_dtu_bg_mask_segment_rows(void);
+
+/* Alpha term (train.py:167-168: rendered_alpha[bg_mask].mean()).  x: n fp32, mask: n uint8, count: one uint32 in device memory
+ * (what scg_dtu_bg_mask wrote).  Forward: out[0] = sum(x[mask]) / count, per-workgroup partial sums added in a fixed order
+ * (bitwise reproducible); count == 0 gives NaN, as torch's mean of an empty selection.  Backward: d_x = mask ? upstream / count : 0
+ * with `upstream` one float in device memory; count == 0 gives all zeros. */
+SCG_API size_t scg_masked_mean_scratch_bytes(int64_t n);
+SCG_API int scg_masked_mean_forward(const float* x, const uint8_t* mask, int64_t n, const uint32_t* count, float* out,
+                                    void* scratch, size_t scratch_bytes, void* stream);
+SCG_API int scg_masked_mean_backward(const uint8_t* mask, int64_t n, const uint32_t* count, const float* upstream, float* d_x,
+                                     void* stream);
+
+/* Evaluation metrics (train.py:252-265).  img, gt: (C,H,W) fp32, C <= 16, both clamped to [0, 1] inside the kernel; mask: (H,W)
+ * fp32 or NULL, a pixel is selected when mask > 0 (NULL: all n = H*W pixels).  out: 2 + C floats,
+ *   out[0] = l1 = mean of |a - b| over the selected C x n elements,
+ *   out[1] = psnr = mean over c of 20 * log10(1 / sqrt(mse[c]))                                     utils/image_utils.py:17-19
+ *   out[2 + c] = mse[c] = mean over the selected pixels of (a - b)^2 in channel c.
+ * Reduced in a fixed order; an empty selection gives NaN everywhere. */
+SCG_API size_t scg_eval_metrics_scratch_bytes(int32_t C, int32_t H, int32_t W);
+SCG_API int scg_eval_metrics(const float* img, const float* gt, const float* mask, int32_t C, int32_t H, int32_t W, float* out,
+                             void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

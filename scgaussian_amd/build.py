@@ -34,6 +34,7 @@ SOURCES = {
     "blend.hip": ["-fno-slp-vectorize"],
     "knn.hip": [],
     "loss.hip": [],
+    "dtumask.hip": [],                            # DTU scenes: background mask, alpha term, masked metrics (scg_loss.h)
     "matchloss.hip": [],
     "optim.hip": ["-ffp-contract=off"],           # Adam in torch's rounding order (no fused multiply-adds)
     "initstage.hip": ["-ffp-contract=off"],       # the init stage's Adam: the same arithmetic (csrc/adam_math.h)
