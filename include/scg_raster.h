@@ -543,6 +543,67 @@ SCG_API int scg_densify_scatter(const ScgModel* model, const ScgDensifyScatter* 
 SCG_API int scg_reset_opacity(int32_t n_ray, float* ray_opacity, float* ray_exp_avg, float* ray_exp_avg_sq, int32_t n_bg,
                               float* bg_opacity, float* bg_exp_avg, float* bg_exp_avg_sq, void* stream);
 
+/* ---- Seeding the model from the init stage (csrc/seed.hip) ------------------------------------------------------------------
+ * GaussianModel.create_from_pcd (reference scene/gaussian_model.py:362-468, train.py:102) as classify / scan / scatter / finish
+ * with one host read (the row count) after the scan.  Additive to ABI 10.
+ *
+ * The N matches of all ordered view pairs lie flat in arena order (for a in views, for b in match_infos[a]): the order the
+ * reference walks.  Match i is kept iff min_loss[i] < threshold (fp32; a NaN is dropped, -inf is kept; min_loss == NULL keeps
+ * every match); kept matches keep their order (stable compaction).  Kept match i at output row r:
+ *   zval[r] = z[i], rayo[r] = rays_o[i], rayd[r] = rays_d[i]                      bit copies
+ *   points[r] = rays_o[i] + rays_d[i] * z[i]                                      one multiply, one add
+ *   features_dc[r] = (color[i] - 0.5f) / C0, C0 = (float)0.28209479177387814      correctly rounded division
+ *   features_rest[r] = 0, rotation[r] = (1,0,0,0), opacity[r] = the caller's constant, max_radii2D[r] = 0
+ * sparse_depths (V,H,W): the pixel (row (int)clamp(uv.y, 0, H-1), column (int)clamp(uv.x, 0, W-1)) of the source view's plane
+ * receives z[i] * cam_z[i] of the kept match LATEST in arena order that hits it (an integer atomic max of the arena index, then
+ * one pass over the pixels: no float atomics, no dependence on the order threads run in); a match with a non-finite uv writes
+ * no depth but is seeded; every other pixel is 0.  masks = sparse_depths > 0.
+ * scaling[r][0..2] = logf(sqrtf(fmaxf(dist2[r], 1e-7f))), dist2 from scg_knn3_mean_dist2_ws on `points`. */
+
+typedef struct ScgSeedSegment {       /* one ordered view pair: matches [offset, offset + count) belong to source view `view` */
+    int32_t offset, count, view;
+} ScgSeedSegment;
+#define SCG_SEED_MAX_SEGMENTS 1024    /* the scatter kernel holds the table in LDS */
+
+/* Bytes of the workspace the three calls share for N matches and `pixels` = V * H * W (0 when out of range): 8 words (the
+ * first is the row count n), one word per workgroup of 256 matches, one int32 winner per pixel, one keep byte per match. */
+SCG_API size_t scg_seed_workspace_bytes(int32_t N, int64_t pixels);
+/* Two launches: the keep bytes, the per-workgroup counts and the winner map set to -1; then the exclusive scan of the counts by
+ * one workgroup in workgroup order.  Afterwards the first uint32 word of the workspace holds n. */
+SCG_API int scg_seed_classify(const float* min_loss, int32_t N, float threshold, int64_t pixels, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
+typedef struct ScgSeedScatter {
+    int32_t struct_bytes;                  /* sizeof(ScgSeedScatter) as the caller sees it */
+    int32_t N, n_out;                      /* n_out: rows of every output tensor (the counted n); no row at or beyond it is written */
+    int32_t V, H, W;                       /* views, and the size they share */
+    int32_t nseg;                          /* 1 .. SCG_SEED_MAX_SEGMENTS when N > 0 */
+    const ScgSeedSegment* segments;        /* HOST table, validated before anything is launched: sorted, tiling [0, N) exactly */
+    const ScgSeedSegment* segments_dev;    /* the same records in device memory */
+    const float* rays_o;                   /* (N,3) */
+    const float* rays_d;                   /* (N,3) */
+    const float* z;                        /* (N) */
+    const float* color;                    /* (N,3) */
+    const float* uv;                       /* (N,2) the match's own pixel in its source view */
+    float opacity;                         /* the raw opacity of every row: log(x / (1 - x)), x = 0.1f, formed by the caller in fp32 */
+    float* zval;                           /* (n,1) */
+    float* rayo;                           /* (n,3) */
+    float* rayd;                           /* (n,3) */
+    float* points;                         /* (n,3) the input of the kNN */
+    float* features_dc;                    /* (n,1,3) */
+    float* features_rest;                  /* (n,15,3) */
+    float* rotation;                       /* (n,4) */
+    float* opacity_out;                    /* (n,1) */
+    float* max_radii2D;                    /* (n) */
+} ScgSeedScatter;
+
+/* One launch on the workspace scg_seed_classify filled for the same N and pixels (= V * H * W). */
+SCG_API int scg_seed_scatter(const ScgSeedScatter* args, void* workspace, size_t workspace_bytes, void* stream);
+/* One launch: the scales from dist2 (n_out rows), and sparse_depths / masks (V*H*W floats / bytes) from the winner map. */
+SCG_API int scg_seed_finish(int32_t n_out, const float* dist2, float* scaling, int32_t N, const float* z, const float* cam_z,
+                            int32_t V, int32_t H, int32_t W, float* sparse_depths, uint8_t* masks, const void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,21 @@ class ScgDensifyScatter(C.Structure):
                                   "noise")]
 
 
+SEED_MAX_SEGMENTS = 1024
+
+
+class ScgSeedSegment(C.Structure):
+    """One ordered view pair of the seeding step's table (include/scg_raster.h ScgSeedSegment)."""
+    _fields_ = [("offset", C.c_int32), ("count", C.c_int32), ("view", C.c_int32)]
+
+
+class ScgSeedScatter(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_bytes", "N", "n_out", "V", "H", "W", "nseg")] + [
+        (n, C.c_void_p) for n in ("segments", "segments_dev", "rays_o", "rays_d", "z", "color", "uv")] + [("opacity", C.c_float)] + [
+        (n, C.c_void_p) for n in ("zval", "rayo", "rayd", "points", "features_dc", "features_rest", "rotation", "opacity_out",
+                                  "max_radii2D")]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/scg_raster.h
 _P = C.c_void_p
 SYMBOLS = {
@@ -152,6 +167,10 @@ SYMBOLS = {
     "scg_densify_classify": (C.c_int, [C.POINTER(ScgModel), _P, _P] + [C.c_float] * 4 + [_P, C.c_size_t, _P]),
     "scg_densify_scatter": (C.c_int, [C.POINTER(ScgModel), C.POINTER(ScgDensifyScatter), _P, C.c_size_t, _P]),
     "scg_reset_opacity": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    "scg_seed_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "scg_seed_classify": (C.c_int, [_P, C.c_int32, C.c_float, C.c_int64, _P, C.c_size_t, _P]),
+    "scg_seed_scatter": (C.c_int, [C.POINTER(ScgSeedScatter), _P, C.c_size_t, _P]),
+    "scg_seed_finish": (C.c_int, [C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
 }
 
 _lib = None

@@ -4,7 +4,8 @@
 
 hipcc cross-compiles without a GPU.  The .so is git-ignored but travels to the GPU box with the
 gpurun snapshot.  geometry.hip is compiled with -ffp-contract=off (bit-exact tile assignment).
-optim.hip and initstage.hip are too: Adam rounded where torch rounds it.  So is densify.hip (the clone's xyz, the / 1.6).
+optim.hip and initstage.hip are too: Adam rounded where torch rounds it.  So are densify.hip (the clone's xyz, the / 1.6) and
+seed.hip (the seeded points).
 """
 from __future__ import annotations
 
@@ -39,6 +40,7 @@ SOURCES = {
     "optim.hip": ["-ffp-contract=off"],           # Adam in torch's rounding order (no fused multiply-adds)
     "initstage.hip": ["-ffp-contract=off"],       # the init stage's Adam: the same arithmetic (csrc/adam_math.h)
     "densify.hip": ["-ffp-contract=off"],         # clone xyz = rayo + rayd * zval and the / 1.6 rounded as torch rounds them
+    "seed.hip": ["-ffp-contract=off"],            # create_from_pcd: points = rays_o + rays_d * z as torch's two operators round it
 }
 HEADERS = [os.path.join(CSRC, "scg_common.h"), os.path.join(CSRC, "tile_sort.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "scg_debug.h"), os.path.join(CSRC, "adam_math.h"), os.path.join(INCLUDE, "scg_raster.h"), os.path.join(INCLUDE, "scg_knn.h"), os.path.join(INCLUDE, "scg_loss.h"), os.path.join(INCLUDE, "scg_matchloss.h")]
 

@@ -5,10 +5,12 @@ The reference runs 2 000 Adam iterations on the per-match ray depths `z_val` aga
 matches whose smallest term is below 0.1.  Here the whole stage is four launches (one per learning-rate segment):
 
     from scgaussian_amd.init_stage import InitStage
+    from scgaussian_amd import seed
     stage = InitStage.from_view_gs(gaussians.view_gs)          # instead of gaussians.training_setup_init()
+    seed.install(gaussians, stage)                             # gaussians.create_from_pcd now runs in csrc/seed.hip (seed.py)
     stage.run_schedule(2000, halve_at=(500, 1000, 1500))       # instead of the loop of train.py:57-93
     stage.load_best(gaussians.view_gs)                         # instead of gaussians.load_z_val(best_state_dict)
-    gaussians.create_from_pcd(stage.min_loss_state())
+    gaussians.create_from_pcd(stage.min_loss_state())          # train.py:102 unchanged: the stage's arena is read in place
 
 A caller who keeps the reference's loop and its torch Adam replaces the body of get_matchloss_from_base by
 `match_loss_from_base(view_gs, stage)`: one launch forward, none backward.
