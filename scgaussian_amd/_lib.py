@@ -225,3 +225,12 @@ def check(rc: int, what: str) -> None:
 def ptr(t) -> int:
     """Device pointer of a tensor (None -> NULL)."""
     return None if t is None else t.data_ptr()
+
+
+def stream_of(t, what: str) -> int:
+    """The current stream of the device of `t` (a tensor or a torch.device), as the handle the C entries take.  The one place that
+    knows that the kernels need a GPU: anything that is not on one raises, `what` naming the step."""
+    dev = getattr(t, "device", t)
+    if not isinstance(dev, torch.device) or dev.type != "cuda":
+        raise ScgError(f"{what} needs tensors on the ROCm GPU ('cuda'); there is no CPU path")
+    return torch.cuda.current_stream(dev).cuda_stream

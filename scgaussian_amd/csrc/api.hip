@@ -31,6 +31,13 @@ int check_hip(hipError_t e, const char* what) {
     return (int)e;
 }
 
+int check_workspace(const char* who, const void* ws, size_t bytes, size_t need) {
+    if (!ws) return fail(SCG_E_NULL, "%s: workspace is NULL", who);
+    if (bytes < need) return fail(SCG_E_SCRATCH, "%s: workspace of %zu bytes < %zu", who, bytes, need);
+    if (reinterpret_cast<uintptr_t>(ws) % 4) return fail(SCG_E_ALIGN, "%s: workspace not 4-byte aligned", who);
+    return 0;
+}
+
 int validate_frame(const ScgFrame* f, bool need_bg) {
     if (!f) return fail(SCG_E_NULL, "frame is NULL");
     if (f->P < 0) return fail(SCG_E_RANGE, "P = %d < 0", f->P);

@@ -6,22 +6,21 @@
 //
 //   densify_classify_kernel   one thread per source: the fate byte (keep-original, clone-survives, children-survive, split) with
 //                             the final prune folded in, and the workgroup's count of the first three
-//   densify_scan_kernel       one workgroup: exclusive scan of the per-workgroup counts in workgroup order (fixed order, no
-//                             atomics), the section totals into the head of the workspace
+//   densify_scan_kernel       one workgroup: exclusive scan of the per-workgroup counts in workgroup order (compact.h: fixed order,
+//                             no atomics), the section totals into the head of the workspace
 //   (the caller reads the four totals and allocates the new background tensors)
-//   densify_scatter_kernel    the same partition of the sources: ranks within the workgroup recomputed from the fate bytes, every
+//   densify_scatter_kernel    the same partition of the sources: ranks within the workgroup recomputed from the fate bits, every
 //                             surviving row copied or computed at base + rank; the 45-float features_rest rows and their moments
 //                             move with the lanes running across the floats of a row.  The same launch divides the raw scaling of
 //                             split ray-bound sources, zeroes the ray optimizer's scaling moments and the new statistics tensors.
 //
 // Sources are read through the two-segment model (ray-bound set, then background set): no concatenated copy exists.  Compiled with
 // -ffp-contract=off: the clone's xyz (one multiply, one add) and the divisions by 1.6 round where torch rounds them.
-#include "scg_common.h"
+#include "compact.h"
 
 namespace scg {
 
 constexpr int kDnBlock = 256;
-constexpr int kDnWaves = kDnBlock / kWave;
 constexpr int kDnHeadWords = 8;                       // [0..3] section totals, [4..7] zero
 constexpr int kDnRest = 45;                           // floats of a features_rest row
 constexpr int32_t kDnMaxP = 1 << 29;                  // 3 P rows at most leave a call: they are counted in 32 bits
@@ -76,40 +75,8 @@ __device__ __forceinline__ bool pruned(float o, float smax, float min_opacity, f
     return (o < min_opacity) || (big_scale >= 0.0f && smax > big_scale);
 }
 
-// Exclusive prefix sums of v[0..2] over the threads of the workgroup in thread order, and the workgroup's sums.  Every thread
-// calls it; s_w is kDnWaves x 3 words of LDS, free again on return.
-__device__ __forceinline__ void block_exscan3(uint32_t v[3], uint32_t tot[3], uint32_t (*s_w)[3]) {
-    const int lane = lane_id(), w = wave_id();
-    uint32_t inc[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        uint32_t x = v[k];
-        for (int off = 1; off < kWave; off <<= 1) {
-            const uint32_t y = (uint32_t)__shfl_up((int)x, off, kWave);
-            if (lane >= off) x += y;
-        }
-        inc[k] = x;
-        if (lane == kWave - 1) s_w[w][k] = x;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        uint32_t before = 0, all = 0;
-        for (int j = 0; j < kDnWaves; ++j) {
-            const uint32_t u = s_w[j][k];
-            if (j < w) before += u;
-            all += u;
-        }
-        v[k] = before + inc[k] - v[k];
-        tot[k] = all;
-    }
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(kDnBlock) void densify_classify_kernel(DnClassifyArgs a) {
-    __shared__ uint32_t s_w[kDnWaves][3];
-    const int tid = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * kDnBlock + tid;
+    const int64_t i = (int64_t)blockIdx.x * kDnBlock + threadIdx.x;
     uint32_t f = 0;
     if (i < a.P) {
         const int nr = a.m.ray.count;
@@ -135,40 +102,21 @@ __global__ __launch_bounds__(kDnBlock) void densify_classify_kernel(DnClassifyAr
         }
         a.fate[i] = (uint8_t)f;
     }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const unsigned long long b = __ballot((f >> k) & 1u);
-        if (lane_id() == 0) s_w[wave_id()][k] = (uint32_t)__popcll(b);
-    }
-    __syncthreads();
-    if (tid < 3) {
-        uint32_t n = 0;
-        for (int w = 0; w < kDnWaves; ++w) n += s_w[w][tid];
-        a.counts[(int64_t)blockIdx.x * 3 + tid] = n;
-    }
+    uint32_t rank[3], tot[3];
+    block_counts<3, kDnBlock>(f, rank, tot);                              // bits 0..2: keep, clone, child
+    if (threadIdx.x == 0)
+        for (int k = 0; k < 3; ++k) a.counts[(int64_t)blockIdx.x * 3 + k] = tot[k];
 }
 
-// counts (groups x 3) -> exclusive bases in place, totals into the head; one workgroup walks the groups kDnBlock at a time
+// counts (groups x 3) -> exclusive bases in place, the section totals into the head
 __global__ __launch_bounds__(kDnBlock) void densify_scan_kernel(uint32_t* head, uint32_t* counts, int groups) {
-    __shared__ uint32_t s_w[kDnWaves][3];
-    const int tid = threadIdx.x;
-    uint32_t carry[3] = {0, 0, 0};
-    for (int base = 0; base < groups; base += kDnBlock) {
-        const int g = base + tid;
-        uint32_t v[3] = {0, 0, 0}, tot[3];
-        if (g < groups)
-            for (int k = 0; k < 3; ++k) v[k] = counts[(int64_t)g * 3 + k];
-        block_exscan3(v, tot, s_w);
-        for (int k = 0; k < 3; ++k) {
-            if (g < groups) counts[(int64_t)g * 3 + k] = carry[k] + v[k];
-            carry[k] += tot[k];
-        }
-    }
-    if (tid == 0) {
-        head[0] = carry[0];
-        head[1] = carry[1];
-        head[2] = carry[2];
-        head[3] = carry[2];
+    uint32_t tot[3];
+    carry_scan<3, kDnBlock>(counts, groups, tot);
+    if (threadIdx.x == 0) {
+        head[0] = tot[0];
+        head[1] = tot[1];
+        head[2] = tot[2];
+        head[3] = tot[2];                                                 // the children of copy 1
         for (int k = 4; k < kDnHeadWords; ++k) head[k] = 0;
     }
 }
@@ -206,7 +154,6 @@ __device__ __forceinline__ void put_row(const DnScatterArgs& a, int64_t d, const
 }
 
 __global__ __launch_bounds__(kDnBlock) void densify_scatter_kernel(DnScatterArgs a) {
-    __shared__ uint32_t s_w[kDnWaves][3];
     __shared__ int32_t s_dst[4][kDnBlock];                               // keep, clone, child 0, child 1: new row or -1
     const int tid = threadIdx.x;
     const int64_t g0 = (int64_t)blockIdx.x * kDnBlock;
@@ -214,8 +161,8 @@ __global__ __launch_bounds__(kDnBlock) void densify_scatter_kernel(DnScatterArgs
     if (g0 < a.P) {                                                       // (uniform: the whole workgroup or none of it)
         const int64_t i = g0 + tid;
         const uint32_t f = i < a.P ? a.fate[i] : 0u;
-        uint32_t v[3] = {f & 1u, (f >> 1) & 1u, (f >> 2) & 1u}, tot[3];
-        block_exscan3(v, tot, s_w);
+        uint32_t v[3], tot[3];
+        block_counts<3, kDnBlock>(f, v, tot);                             // v: the rank among the workgroup's keeps, clones, children
         const uint32_t K = a.head[0], C = a.head[1], S = a.head[2];
         const uint32_t* b = a.bases + (int64_t)blockIdx.x * 3;
         int64_t dst[4] = {-1, -1, -1, -1};
@@ -359,14 +306,6 @@ static int validate_model_pointers(const char* who, const ScgModel* m) {
     return 0;
 }
 
-static int validate_workspace(const char* who, const void* ws, size_t bytes, int P) {
-    if (!ws) return fail(SCG_E_NULL, "%s: workspace is NULL", who);
-    if (bytes < dn_workspace_bytes(P))
-        return fail(SCG_E_SCRATCH, "%s: workspace of %zu bytes < %zu", who, bytes, dn_workspace_bytes(P));
-    if (reinterpret_cast<uintptr_t>(ws) % 4) return fail(SCG_E_ALIGN, "%s: workspace not 4-byte aligned", who);
-    return 0;
-}
-
 static void tensors_to_array(const ScgDensifyTensors& t, float* out[kTensors]) {
     out[kTXyz] = t.xyz; out[kTDc] = t.features_dc; out[kTRest] = t.features_rest;
     out[kTOpacity] = t.opacity; out[kTScaling] = t.scaling; out[kTRotation] = t.rotation;
@@ -385,7 +324,7 @@ int scg_densify_classify(const ScgModel* model, const float* accum, const float*
     if (int rc = validate_model("densify_classify", model)) return rc;
     if (!(max_grad > 0.0f)) return fail(SCG_E_RANGE, "densify_classify: max_grad = %g must be > 0", (double)max_grad);
     const int P = model->ray.count + model->bg.count;
-    if (int rc = validate_workspace("densify_classify", workspace, workspace_bytes, P)) return rc;
+    if (int rc = check_workspace("densify_classify", workspace, workspace_bytes, dn_workspace_bytes(P))) return rc;
     if (int rc = validate_model_pointers("densify_classify", model)) return rc;
     if (P > 0 && (!accum || !denom)) return fail(SCG_E_NULL, "densify_classify: accum / denom is NULL");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -413,7 +352,7 @@ int scg_densify_scatter(const ScgModel* model, const ScgDensifyScatter* args, co
     const int P = model->ray.count + model->bg.count;
     if (args->out_rows < 0 || (int64_t)args->out_rows > 3ll * P)
         return fail(SCG_E_RANGE, "densify_scatter: out_rows = %d not in 0..3 P", args->out_rows);
-    if (int rc = validate_workspace("densify_scatter", workspace, workspace_bytes, P)) return rc;
+    if (int rc = check_workspace("densify_scatter", workspace, workspace_bytes, dn_workspace_bytes(P))) return rc;
     if (int rc = validate_model_pointers("densify_scatter", model)) return rc;
     DnScatterArgs a;
     a.m = *model;

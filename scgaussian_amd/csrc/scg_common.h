@@ -61,6 +61,7 @@ inline FrameDev make_frame_dev(const ScgFrame* f) {
 // error plumbing (api.hip)
 int fail(int code, const char* fmt, ...);
 int check_hip(hipError_t e, const char* what);
+int check_workspace(const char* who, const void* ws, size_t bytes, size_t need);   // NULL, then too small, then not 4-byte aligned
 int validate_frame(const ScgFrame* f, bool need_bg);
 
 // stage launchers (each returns 0 or an error code; all work goes on `stream`)

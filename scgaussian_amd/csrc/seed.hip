@@ -6,7 +6,8 @@
 //
 //   seed_classify_kernel   one thread per match: the keep byte (min_loss < threshold) and the workgroup's count; the same grid sets
 //                          the winner map (one int32 per pixel of sparse_depths) to -1
-//   seed_scan_kernel       one workgroup: exclusive scan of the per-workgroup counts in workgroup order, the total into the head
+//   seed_scan_kernel       one workgroup: exclusive scan of the per-workgroup counts in workgroup order (compact.h), the total into
+//                          the head
 //   (the caller reads the total n and allocates the model's tensors)
 //   seed_scatter_kernel    the same partition: ranks within the workgroup recomputed from the keep bytes, the per-row values written
 //                          at base + rank; a workgroup's rows are consecutive, so features_rest, rotation, opacity and max_radii2D
@@ -19,12 +20,11 @@
 //
 // No workgroup waits for another inside a kernel.  Compiled with -ffp-contract=off: points = rays_o + rays_d * z is one multiply
 // and one add, as torch's two operators are.
-#include "scg_common.h"
+#include "compact.h"
 
 namespace scg {
 
 constexpr int kSdBlock = 256;
-constexpr int kSdWaves = kSdBlock / kWave;
 constexpr int kSdHeadWords = 8;                       // [0] the row count n, [1..7] zero
 constexpr int kSdRest = 45;                           // floats of a features_rest row
 constexpr int kSdMaxFillGroups = 1024;                // workgroups that share the fill of the winner map when N is small
@@ -77,81 +77,43 @@ struct SdScatterArgs {
 
 __global__ __launch_bounds__(kSdBlock) void seed_classify_kernel(const float* min_loss, int N, float threshold, int groups,
                                                                  uint8_t* keep, uint32_t* counts, int32_t* winner, int64_t pixels) {
-    __shared__ uint32_t s_w[kSdWaves];
-    const int tid = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * kSdBlock + tid;
+    const int64_t i = (int64_t)blockIdx.x * kSdBlock + threadIdx.x;
     bool k = false;
     if (i < N) {
         k = min_loss ? (min_loss[i] < threshold) : true;                  // a NaN compares false: dropped
         keep[i] = (uint8_t)k;
     }
-    const unsigned long long b = __ballot(k);
-    if (lane_id() == 0) s_w[wave_id()] = (uint32_t)__popcll(b);
-    __syncthreads();
-    if (tid == 0 && (int)blockIdx.x < groups) {
-        uint32_t n = 0;
-        for (int w = 0; w < kSdWaves; ++w) n += s_w[w];
-        counts[blockIdx.x] = n;
-    }
+    uint32_t rank, n;
+    block_counts<1, kSdBlock>(k, &rank, &n);
+    if (threadIdx.x == 0 && (int)blockIdx.x < groups) counts[blockIdx.x] = n;
     const int64_t stride = (int64_t)gridDim.x * kSdBlock;
     for (int64_t p = i; p < pixels; p += stride) winner[p] = -1;
 }
 
-// counts -> exclusive bases in place, the total into the head; one workgroup walks the groups kSdBlock at a time
+// counts -> exclusive bases in place, the total into the head
 __global__ __launch_bounds__(kSdBlock) void seed_scan_kernel(uint32_t* head, uint32_t* counts, int groups) {
-    __shared__ uint32_t s_w[kSdWaves];
-    const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
-    uint32_t carry = 0;
-    for (int base = 0; base < groups; base += kSdBlock) {
-        const int g = base + tid;
-        const uint32_t v = g < groups ? counts[g] : 0u;
-        uint32_t x = v;
-        for (int off = 1; off < kWave; off <<= 1) {
-            const uint32_t y = (uint32_t)__shfl_up((int)x, off, kWave);
-            if (lane >= off) x += y;
-        }
-        if (lane == kWave - 1) s_w[w] = x;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-        for (int j = 0; j < kSdWaves; ++j) {
-            const uint32_t u = s_w[j];
-            if (j < w) before += u;
-            all += u;
-        }
-        if (g < groups) counts[g] = carry + before + x - v;
-        carry += all;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        head[0] = carry;
+    uint32_t n;
+    carry_scan<1, kSdBlock>(counts, groups, &n);
+    if (threadIdx.x == 0) {
+        head[0] = n;
         for (int k = 1; k < kSdHeadWords; ++k) head[k] = 0;
     }
 }
 
 __global__ __launch_bounds__(kSdBlock) void seed_scatter_kernel(SdScatterArgs a) {
-    __shared__ uint32_t s_w[kSdWaves];
     __shared__ int32_t s_off[SCG_SEED_MAX_SEGMENTS];
     __shared__ int32_t s_view[SCG_SEED_MAX_SEGMENTS];
-    const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
+    const int tid = threadIdx.x;
     for (int s = tid; s < a.nseg; s += kSdBlock) {
         s_off[s] = a.seg[s].offset;
         s_view[s] = a.seg[s].view;
     }
     const int64_t i = (int64_t)blockIdx.x * kSdBlock + tid;
     const bool k = i < a.N && a.keep[i] != 0;
-    // rank of this match among the workgroup's kept ones, in thread order
-    const unsigned long long b = __ballot(k);
-    const uint32_t in_wave = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) s_w[w] = (uint32_t)__popcll(b);
-    __syncthreads();                                                      // ... and the segment table is in LDS
-    uint32_t before = 0, tot = 0;
-    for (int j = 0; j < kSdWaves; ++j) {
-        const uint32_t u = s_w[j];
-        if (j < w) before += u;
-        tot += u;
-    }
+    uint32_t rank, tot;                                                   // rank of this match among the workgroup's kept ones
+    block_counts<1, kSdBlock>(k, &rank, &tot);                            // ... and its barrier: the segment table is in LDS
     const int64_t base = a.bases[blockIdx.x];
-    const int64_t r = base + before + in_wave;
+    const int64_t r = base + rank;
     if (k && r < a.n_out) {                                               // never beyond what the caller allocated
         const float z = a.z[i];
         a.zval[r] = z;
@@ -216,14 +178,6 @@ static int validate_sizes(const char* who, int64_t N, int64_t V, int64_t H, int6
     return 0;
 }
 
-static int validate_workspace(const char* who, const void* ws, size_t bytes, int N, int64_t pixels) {
-    if (!ws) return fail(SCG_E_NULL, "%s: workspace is NULL", who);
-    if (bytes < sd_workspace_bytes(N, pixels))
-        return fail(SCG_E_SCRATCH, "%s: workspace of %zu bytes < %zu", who, bytes, sd_workspace_bytes(N, pixels));
-    if (reinterpret_cast<uintptr_t>(ws) % 4) return fail(SCG_E_ALIGN, "%s: workspace not 4-byte aligned", who);
-    return 0;
-}
-
 static int fill_groups(int N, int64_t pixels) {
     int64_t fill = (pixels + 4 * kSdBlock - 1) / (4 * kSdBlock);
     if (fill > kSdMaxFillGroups) fill = kSdMaxFillGroups;
@@ -242,7 +196,7 @@ int scg_seed_classify(const float* min_loss, int32_t N, float threshold, int64_t
                       void* stream) {
     if (N < 0) return fail(SCG_E_RANGE, "seed_classify: N = %d < 0", N);
     if (pixels < 0 || pixels > kSdMaxPixels) return fail(SCG_E_RANGE, "seed_classify: pixels = %lld out of range", (long long)pixels);
-    if (int rc = validate_workspace("seed_classify", workspace, workspace_bytes, N, pixels)) return rc;
+    if (int rc = check_workspace("seed_classify", workspace, workspace_bytes, sd_workspace_bytes(N, pixels))) return rc;
     if (min_loss && reinterpret_cast<uintptr_t>(min_loss) % 4) return fail(SCG_E_ALIGN, "seed_classify: min_loss not 4-byte aligned");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const SdWorkspace w = sd_carve(workspace, N, pixels);
@@ -278,7 +232,7 @@ int scg_seed_scatter(const ScgSeedScatter* p, void* workspace, size_t workspace_
     }
     if (at != N) return fail(SCG_E_RANGE, "seed_scatter: the segments cover %lld of N = %d matches", (long long)at, N);
     const int64_t pixels = (int64_t)p->V * p->H * p->W;
-    if (int rc = validate_workspace("seed_scatter", workspace, workspace_bytes, N, pixels)) return rc;
+    if (int rc = check_workspace("seed_scatter", workspace, workspace_bytes, sd_workspace_bytes(N, pixels))) return rc;
     if (N > 0 && (!p->rays_o || !p->rays_d || !p->z || !p->color || !p->uv)) return fail(SCG_E_NULL, "seed_scatter: an input tensor is NULL");
     if (p->n_out > 0 && (!p->zval || !p->rayo || !p->rayd || !p->points || !p->features_dc || !p->features_rest || !p->rotation ||
                          !p->opacity_out || !p->max_radii2D))
@@ -304,7 +258,7 @@ int scg_seed_finish(int32_t n_out, const float* dist2, float* scaling, int32_t N
     if (int rc = validate_sizes("seed_finish", N, V, H, W)) return rc;
     if (n_out < 0 || n_out > N) return fail(SCG_E_RANGE, "seed_finish: n_out = %d not in 0..N = %d", n_out, N);
     const int64_t pixels = (int64_t)V * H * W;
-    if (int rc = validate_workspace("seed_finish", workspace, workspace_bytes, N, pixels)) return rc;
+    if (int rc = check_workspace("seed_finish", workspace, workspace_bytes, sd_workspace_bytes(N, pixels))) return rc;
     if (n_out > 0 && (!dist2 || !scaling)) return fail(SCG_E_NULL, "seed_finish: dist2 / scaling is NULL");
     if (N > 0 && (!z || !cam_z)) return fail(SCG_E_NULL, "seed_finish: z / cam_z is NULL");
     if (pixels > 0 && (!sparse_depths || !masks)) return fail(SCG_E_NULL, "seed_finish: sparse_depths / masks is NULL");

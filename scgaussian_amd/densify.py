@@ -37,9 +37,7 @@ def _err(msg: str):
 def _check(name: str, t, rows: int, tail, dev) -> torch.Tensor:
     if not torch.is_tensor(t):
         raise _err(f"{name} is not a tensor")
-    if not t.is_cuda:
-        raise _err(f"{name} must be a CUDA tensor (there is no CPU path)")
-    if dev is not None and t.device != dev:
+    if t.device != dev:
         raise _err(f"{name} is on {t.device}, the model on {dev}")
     if t.dtype != torch.float32:
         raise _err(f"{name} must be fp32, not {t.dtype}")
@@ -88,8 +86,7 @@ class _Model:
             if not hasattr(g, a):
                 raise _err(f"the model has no attribute {a}")
         z = g._zval
-        if not torch.is_tensor(z) or not z.is_cuda:
-            raise _err("_zval must be a CUDA tensor (there is no CPU path)")
+        self.stream = _lib.stream_of(z, "densify: the model")
         self.dev = dev = z.device
         self.nr = nr = z.shape[0]
         self.ray = {a: _check(a, getattr(g, a), nr, _RAY_SHAPES[a], dev) for a in RAY_ATTRS}
@@ -144,14 +141,13 @@ def densify_and_prune(gaussians, max_grad, min_opacity, extent, max_screen_size,
         groups.append((a, g, st) + _moments(a, st, md.bg[a]))
 
     lib = _lib.load()
-    stream = torch.cuda.current_stream(dev).cuda_stream
     ws_bytes = lib.scg_densify_workspace_bytes(P)
     if ws_bytes == 0:
         raise _err(f"{P} Gaussians are more than the kernels take")
     ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
     big = 0.2 * extent if max_screen_size else -1.0
     _lib.check(lib.scg_densify_classify(C.byref(md.c), accum.data_ptr() or None, denom.data_ptr() or None, max_grad, min_opacity,
-                                        float(gaussians.percent_dense) * extent, big, ws.data_ptr(), ws_bytes, stream),
+                                        float(gaussians.percent_dense) * extent, big, ws.data_ptr(), ws_bytes, md.stream),
                "scg_densify_classify")
     kept, clones, children, _ = (int(x) for x in ws[:4].tolist())                          # the one host read
     rows = kept + clones + 2 * children
@@ -181,7 +177,7 @@ def densify_and_prune(gaussians, max_grad, min_opacity, extent, max_screen_size,
         if sc_m is not None:
             a.ray_scaling_exp_avg, a.ray_scaling_exp_avg_sq = sc_m.data_ptr(), sc_v.data_ptr()
     a.noise = noise.data_ptr() or None
-    _lib.check(lib.scg_densify_scatter(C.byref(md.c), C.byref(a), ws.data_ptr(), ws_bytes, stream), "scg_densify_scatter")
+    _lib.check(lib.scg_densify_scatter(C.byref(md.c), C.byref(a), ws.data_ptr(), ws_bytes, md.stream), "scg_densify_scatter")
 
     # hand over: one re-keying per background group (cat_tensors_to_optimizer's, once instead of three times)
     opt = gaussians.optimizer_bg
@@ -215,9 +211,8 @@ def reset_opacity(gaussians) -> None:
     if md.nb:
         _g, st = _group(gaussians.optimizer_bg, "bg_opacity", md.bg["bg_opacity"])
         bm, bv = _moments("bg_opacity", st, md.bg["bg_opacity"])
-    stream = torch.cuda.current_stream(md.dev).cuda_stream
     _lib.check(_lib.load().scg_reset_opacity(md.nr, md.ray["_opacity"].data_ptr() or None, _lib.ptr(rm), _lib.ptr(rv), md.nb,
-                                             md.bg["bg_opacity"].data_ptr() or None, _lib.ptr(bm), _lib.ptr(bv), stream),
+                                             md.bg["bg_opacity"].data_ptr() or None, _lib.ptr(bm), _lib.ptr(bv), md.stream),
                "scg_reset_opacity")
 
 

@@ -26,22 +26,13 @@ def threshold_for(source_path: str) -> float:
     return THRESHOLD_SCAN110 if "scan110" in str(source_path) else THRESHOLD
 
 
-def _need_gpu(t: torch.Tensor, what: str) -> None:
-    if not t.is_cuda:
-        raise _lib.ScgError(f"{what} needs tensors on the ROCm GPU ('cuda'); there is no CPU path")
-
-
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def background_mask(gt: torch.Tensor, threshold: float = THRESHOLD, run: int = RUN, inplace: bool = False):
     """train.py:149-158 in one launch.  gt: (3,H,W) fp32 on the GPU.  Returns (mask, gt_masked, count): mask bool (1,H,W) — true
     where the pixel is dark (max over the channels < threshold) and so are the min(row, run - 1) pixels above it —, gt_masked = gt
     with those pixels zeroed, count a 0-dim int32 device tensor holding the number of masked pixels (never read here).
     inplace=True writes into `gt` and returns it, as the reference does (needs a contiguous fp32 `gt` and threshold > 0)."""
     lib = _lib.load()
-    _need_gpu(gt, "background_mask")
+    stream = _lib.stream_of(gt, "background_mask")
     if gt.dim() != 3 or gt.shape[0] != 3:
         raise ValueError("gt must be (3,H,W)")
     if inplace:
@@ -57,7 +48,7 @@ def background_mask(gt: torch.Tensor, threshold: float = THRESHOLD, run: int = R
         mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
         count = torch.empty((1,), dtype=torch.int32, device=dev)        # the library's one uint32: H * W < 2^31
         check(lib.scg_dtu_bg_mask(src.data_ptr(), H, W, float(threshold), int(run), mask.data_ptr(), dst.data_ptr(),
-                                  count.data_ptr(), _stream(dev)), "scg_dtu_bg_mask")
+                                  count.data_ptr(), stream), "scg_dtu_bg_mask")
     return mask.view(torch.bool)[None], (gt if inplace else dst), count.reshape(())
 
 
@@ -94,7 +85,7 @@ class _MaskedMean(torch.autograd.Function):
             nbytes = lib.scg_masked_mean_scratch_bytes(n)
             scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
             check(lib.scg_masked_mean_forward(xs.data_ptr(), mask_u8.data_ptr(), n, count.data_ptr(), out.data_ptr(),
-                                              scratch.data_ptr(), nbytes, _stream(dev)), "scg_masked_mean_forward")
+                                              scratch.data_ptr(), nbytes, _lib.stream_of(dev, "alpha_term")), "scg_masked_mean_forward")
         ctx.mask_u8, ctx.count, ctx.shape, ctx.in_dtype = mask_u8, count, x.shape, x.dtype
         return out.reshape(())
 
@@ -110,14 +101,14 @@ class _MaskedMean(torch.autograd.Function):
         n = mask_u8.numel()
         with torch.cuda.device(dev):
             d_x = torch.empty((n,), dtype=torch.float32, device=dev)
-            check(lib.scg_masked_mean_backward(mask_u8.data_ptr(), n, count.data_ptr(), g.data_ptr(), d_x.data_ptr(), _stream(dev)),
-                  "scg_masked_mean_backward")
+            check(lib.scg_masked_mean_backward(mask_u8.data_ptr(), n, count.data_ptr(), g.data_ptr(), d_x.data_ptr(),
+                                               _lib.stream_of(dev, "alpha_term")), "scg_masked_mean_backward")
         return d_x.reshape(ctx.shape).to(ctx.in_dtype), None, None
 
 
 def alpha_term(rendered_alpha: torch.Tensor, view: DtuView) -> torch.Tensor:
     """train.py:168: rendered_alpha[bg_mask].mean() — NaN for an empty mask, as in torch.  No host read: capturable."""
-    _need_gpu(rendered_alpha, "alpha_term")
+    _lib.stream_of(rendered_alpha, "alpha_term")
     return _MaskedMean.apply(rendered_alpha, view._mask_u8, view.count)
 
 
@@ -130,7 +121,7 @@ def eval_metrics_all(image: torch.Tensor, gt: torch.Tensor, dtumask=None):
     """(l1, psnr, mse (C,)) of train.py:252-265 as device tensors from one fused pass: both images clamped to [0, 1], the pixels
     with dtumask > 0 selected (all of them without a mask).  NaN for an empty selection."""
     lib = _lib.load()
-    _need_gpu(image, "eval_metrics")
+    stream = _lib.stream_of(image, "eval_metrics")
     if image.dim() != 3:
         raise ValueError("image must be (C,H,W)")
     a = image.detach().float().contiguous()
@@ -149,7 +140,7 @@ def eval_metrics_all(image: torch.Tensor, gt: torch.Tensor, dtumask=None):
         nbytes = lib.scg_eval_metrics_scratch_bytes(C, H, W)
         scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
         check(lib.scg_eval_metrics(a.data_ptr(), b.data_ptr(), _lib.ptr(m), C, H, W, out.data_ptr(), scratch.data_ptr(), nbytes,
-                                   _stream(dev)), "scg_eval_metrics")
+                                   stream), "scg_eval_metrics")
     return out[0], out[1], out[2:]
 
 

@@ -25,7 +25,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _arena, _lib
 from ._lib import check, ptr
 
 BETAS = (0.9, 0.999)                            # training_setup_init: torch.optim.Adam(l_init, lr=0.0, eps=1e-15)
@@ -38,10 +38,7 @@ _GROUP = 64                                     # elements per workgroup (one wa
 
 
 def _current_stream(t: torch.Tensor) -> int:
-    """The stream a launch on `t`'s device goes to.  The one place that knows that the init stage needs a GPU."""
-    if not t.is_cuda:
-        raise _lib.ScgError("the init stage needs tensors on the ROCm GPU ('cuda'); there is no CPU path")
-    return torch.cuda.current_stream(t.device).cuda_stream
+    return _lib.stream_of(t, "the init stage")
 
 
 class InitStage:
@@ -64,41 +61,35 @@ class InitStage:
     # ---- packing ---------------------------------------------------------------------------------------------------------
     @classmethod
     def from_view_gs(cls, view_gs: Dict, lr: float = 0.5, loss_scale: float = 5.0, record_losses: bool = True) -> "InitStage":
-        keys = list(view_gs.keys())
-        order = {k: i for i, k in enumerate(keys)}
+        keys, pairs = _arena.walk(view_gs)
         segments, recs, empty = [], [], []
         rays_o, rays_d, uv_t, wgt, z = [], [], [], [], []
-        off = 0
-        dev = None
-        for a in keys:
-            for b, info in view_gs[a]["match_infos"].items():
-                back = view_gs[b]["match_infos"][a]
-                zv = info["z_val"].detach()
-                dev = zv.device if dev is None else dev
-                M = zv.shape[0]
-                if back["uv"].shape[0] != M or info["rays_o"].shape[0] != M:
-                    raise _lib.ScgError(f"init stage: pair ({a}, {b}) has {M} depths but {back['uv'].shape[0]} partner matches")
-                valid = ((info["blender_mask"].detach().float() * back["blender_mask"].detach().float()) > 0).float()
-                count = float(valid.sum())
-                if count == 0:
-                    empty.append((a, b))
-                first = a if order[a] < order[b] else b            # the reference normalises by the earlier view's size
-                rec = np.zeros((), dtype=_SEG_DTYPE)
-                rec["offset"], rec["count"] = off, M
-                rec["width"], rec["height"] = float(view_gs[first]["width"]), float(view_gs[first]["height"])
-                rec["intr"] = view_gs[b]["intr"].detach().float().cpu().numpy().reshape(9)
-                rec["w2c"] = view_gs[b]["w2c"].detach().float().cpu().numpy()[:3].reshape(12)
-                recs.append(rec)
-                segments.append((a, b, off, M))
-                rays_o.append(info["rays_o"].detach().float().reshape(M, 3))
-                rays_d.append(info["rays_d"].detach().float().reshape(M, 3))
-                uv_t.append(back["uv"].detach().float().reshape(M, 2))
-                wgt.append(valid / count if count > 0 else valid)
-                z.append(zv.float().reshape(M))
-                off += M
+        for a, b, off, M, info in pairs:
+            back = view_gs[b]["match_infos"][a]
+            zv = info["z_val"].detach()
+            if back["uv"].shape[0] != M or zv.shape[0] != M:
+                raise _lib.ScgError(f"init stage: pair ({a}, {b}) has {zv.shape[0]} depths but {back['uv'].shape[0]} partner matches")
+            valid = ((info["blender_mask"].detach().float() * back["blender_mask"].detach().float()) > 0).float()
+            count = float(valid.sum())
+            if count == 0:
+                empty.append((a, b))
+            first = a if keys.index(a) < keys.index(b) else b      # the reference normalises by the earlier view's size
+            rec = np.zeros((), dtype=_SEG_DTYPE)
+            rec["offset"], rec["count"] = off, M
+            rec["width"], rec["height"] = float(view_gs[first]["width"]), float(view_gs[first]["height"])
+            rec["intr"] = view_gs[b]["intr"].detach().float().cpu().numpy().reshape(9)
+            rec["w2c"] = view_gs[b]["w2c"].detach().float().cpu().numpy()[:3].reshape(12)
+            recs.append(rec)
+            segments.append((a, b, off, M))
+            rays_o.append(info["rays_o"].detach().float().reshape(M, 3))
+            rays_d.append(info["rays_d"].detach().float().reshape(M, 3))
+            uv_t.append(back["uv"].detach().float().reshape(M, 2))
+            wgt.append(valid / count if count > 0 else valid)
+            z.append(zv.float().reshape(M))
         if not segments:
             raise _lib.ScgError("init stage: view_gs holds no match pair")
-        table = torch.from_numpy(np.stack(recs).view(np.uint8).reshape(-1).copy()).to(dev)
+        dev = pairs[0][4]["z_val"].device
+        table = _arena.upload_table(np.stack(recs), dev)
         cat = lambda ts: torch.cat([t.to(dev) for t in ts]).contiguous()           # noqa: E731
         return cls(segments, table, cat(rays_o), cat(rays_d), cat(uv_t), cat(wgt), cat(z), empty, lr, loss_scale, record_losses)
 
@@ -106,16 +97,9 @@ class InitStage:
     def N(self) -> int:
         return self.z.numel()
 
-    def _nested(self, flat: torch.Tensor, column: bool) -> Dict:
-        out: Dict = {}
-        for a, b, off, M in self.segments:
-            v = flat[off:off + M]
-            out.setdefault(a, {})[b] = v.view(M, 1) if column else v
-        return out
-
     def z_views(self) -> Dict:
         """{a: {b: (M,1) view into the flat z}}."""
-        return self._nested(self.z, True)
+        return _arena.nested(self.segments, self.z, True)
 
     def install(self, view_gs: Dict) -> None:
         """Put the (M,1) views of the flat z back into view_gs as nn.Parameters (they share the arena's memory), so the
@@ -197,11 +181,11 @@ class InitStage:
 
     def best_state_dict(self) -> Dict:
         """{a: {b: (M,1)}}: per match the depth at which its loss term was smallest (the reference's best_state_dict)."""
-        return self._nested(self.best_z, True)
+        return _arena.nested(self.segments, self.best_z, True)
 
     def min_loss_state(self) -> Dict:
         """{a: {b: (M)}}: that smallest term (the reference's min_loss_state, what create_from_pcd thresholds at 0.1)."""
-        return self._nested(self.min_loss, False)
+        return _arena.nested(self.segments, self.min_loss, False)
 
     def load_best(self, view_gs: Optional[Dict] = None) -> None:
         """What load_z_val(best_state_dict) does: the depths become the best ones (and, given view_gs, are installed)."""
@@ -235,9 +219,7 @@ class _MatchLossFromBase(torch.autograd.Function):
 
 
 def _is_arena(stage: InitStage, zs) -> bool:
-    base = stage.z.data_ptr()
-    return all(z.dtype == torch.float32 and z.is_contiguous() and z.data_ptr() == base + 4 * off
-               for z, (_a, _b, off, _M) in zip(zs, stage.segments))
+    return _arena.is_arena(stage.z, zs, stage.segments)
 
 
 def match_loss_from_base(view_gs: Dict, stage: Optional[InitStage] = None):
@@ -251,4 +233,4 @@ def match_loss_from_base(view_gs: Dict, stage: Optional[InitStage] = None):
         if z.numel() != M:
             raise _lib.ScgError(f"init stage: z_val of pair ({a}, {b}) has {z.numel()} elements, the packed arena {M}")
     loss, flat = _MatchLossFromBase.apply(stage, *zs)
-    return loss, stage._nested(flat, False)
+    return loss, _arena.nested(stage.segments, flat, False)

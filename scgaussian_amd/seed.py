@@ -29,11 +29,12 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _arena, _lib
 
 THRESHOLD = 0.1                                 # create_from_pcd: min_loss_state[a][b] < 0.1
 _BG_NAMES = ("bg_xyz", "bg_features_dc", "bg_features_rest", "bg_scaling", "bg_rotation", "bg_opacity")
 _SEG_DTYPE = np.dtype([("offset", "<i4"), ("count", "<i4"), ("view", "<i4")])
+_WHAT = "seed: the seeding step"                # ... needs tensors on the GPU (_lib.stream_of)
 assert _SEG_DTYPE.itemsize == C.sizeof(_lib.ScgSeedSegment)
 
 
@@ -48,8 +49,7 @@ def raw_opacity() -> float:
 
 
 def _flat(t: torch.Tensor, tail: Tuple[int, ...], dev) -> torch.Tensor:
-    if not t.is_cuda:
-        raise _err("the seeding step needs tensors on the ROCm GPU ('cuda'); there is no CPU path")
+    _lib.stream_of(t, _WHAT)
     return t.detach().to(device=dev, dtype=torch.float32).reshape((-1,) + tail)
 
 
@@ -59,7 +59,7 @@ def _table(segments, views, dev):
     rec["offset"] = [s[2] for s in segments]
     rec["count"] = [s[3] for s in segments]
     rec["view"] = views
-    return rec, torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(dev)
+    return rec, _arena.upload_table(rec, dev)
 
 
 class SeedInputs:
@@ -87,37 +87,27 @@ class SeedInputs:
     def from_view_gs(cls, view_gs: Dict, stage=None) -> "SeedInputs":
         """Given `stage` (the InitStage of this view_gs), its rays_o, rays_d, z and min_loss are shared, not copied: the inputs can
         be packed before the stage runs and see its result.  Without it they are concatenated from view_gs as it is now."""
-        keys = list(view_gs.keys())
+        keys, pairs = _arena.walk(view_gs)
         if not keys:
             raise _err("view_gs holds no view")
-        index = {k: v for v, k in enumerate(keys)}
         sizes = {(int(view_gs[k]["height"]), int(view_gs[k]["width"])) for k in keys}
         if len(sizes) != 1:
             raise _err(f"the views have unequal sizes {sorted(sizes)}: sparse_depths and img_colors cannot be stacked")
         (H, W), = sizes
         if H <= 0 or W <= 0:
             raise _err(f"views of {W} x {H} pixels")
-        segments, infos, off = [], [], 0
-        for a in keys:
-            for b, info in view_gs[a]["match_infos"].items():
-                M = info["rays_o"].shape[0]
-                segments.append((a, b, off, M))
-                infos.append(info)
-                off += M
-        if not segments:
+        if not pairs:
             raise _err("view_gs holds no match pair")
+        segments, infos = [p[:4] for p in pairs], [p[4] for p in pairs]
+        off = pairs[-1][2] + pairs[-1][3]
         if len(segments) > _lib.SEED_MAX_SEGMENTS:
             raise _err(f"{len(segments)} ordered view pairs are more than the kernels take ({_lib.SEED_MAX_SEGMENTS})")
         if off >= 2 ** 31:
             raise _err(f"{off} matches are more than the kernels take")
-        if stage is not None:
-            if [s[2:] for s in stage.segments] != [s[2:] for s in segments] or [s[:2] for s in stage.segments] != [s[:2] for s in segments]:
-                raise _err("the init stage was packed from another view_gs (its segments differ)")
-            dev = stage.z.device
-        else:
-            dev = infos[0]["rays_o"].device
-        if dev.type != "cuda":
-            raise _err("the seeding step needs tensors on the ROCm GPU ('cuda'); there is no CPU path")
+        if stage is not None and list(stage.segments) != segments:
+            raise _err("the init stage was packed from another view_gs (its segments differ)")
+        dev = stage.z.device if stage is not None else infos[0]["rays_o"].device
+        _lib.stream_of(dev, _WHAT)
         cat = lambda key, tail: torch.cat([_flat(i[key], tail, dev) for i in infos]).contiguous()      # noqa: E731
         color, uv = cat("color", (3,)), cat("uv", (2,))
         cam_z = torch.cat([_flat(i["cam_rays_d"], (3,), dev)[:, 2] for i in infos]).contiguous()
@@ -128,10 +118,10 @@ class SeedInputs:
             rays_o, rays_d, z, min_loss = stage.rays_o, stage.rays_d, stage.z, stage.min_loss
         else:
             rays_o, rays_d, min_loss = cat("rays_o", (3,)), cat("rays_d", (3,)), None
-            z = torch.cat([_flat(i["z_val"], (), dev) for i in infos]).contiguous()
+            z = cat("z_val", ())
             if z.shape[0] != off or rays_d.shape[0] != off:
                 raise _err(f"z_val / rays_d hold {z.shape[0]} / {rays_d.shape[0]} rows, rays_o {off}")
-        rec, table_dev = _table(segments, [index[s[0]] for s in segments], dev)
+        rec, table_dev = _table(segments, [keys.index(s[0]) for s in segments], dev)
         return cls(segments, rec, table_dev, [view_gs[k] for k in keys], H, W, color, uv, cam_z, rays_o, rays_d, z, min_loss, stage)
 
     @classmethod
@@ -146,16 +136,15 @@ class SeedInputs:
         for s, (M, v) in enumerate(zip(counts, seg_view)):
             segments.append((int(v), s, off, int(M)))
             off += int(M)
-        if not torch.is_tensor(z) or not z.is_cuda:
-            raise _err("the seeding step needs tensors on the ROCm GPU ('cuda'); there is no CPU path")
+        _lib.stream_of(z, _WHAT)
         rec, table_dev = _table(segments, [int(v) for v in seg_view], z.device)
         return cls(segments, rec, table_dev, list(views) if views is not None else [None] * V, H, W, color, uv, cam_z, rays_o,
                    rays_d, z, None, None)
 
 
 def _min_loss_flat(inputs: SeedInputs, state: Optional[Dict], stage) -> Optional[torch.Tensor]:
-    """The (N) tensor of the nested min_loss_state: the stage's own arena when the dict holds its views in arena order (the test of
-    init_stage._is_arena, on min_loss), one concatenation otherwise."""
+    """The (N) tensor of the nested min_loss_state: the stage's own arena when the dict holds its views in arena order
+    (_arena.is_arena), one concatenation otherwise."""
     if state is None:
         return None
     ts = []
@@ -164,18 +153,14 @@ def _min_loss_flat(inputs: SeedInputs, state: Optional[Dict], stage) -> Optional
             t = state[a][b]
         except KeyError:
             raise _err(f"min_loss_state has no entry for pair ({a}, {b})") from None
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise _err("min_loss_state must hold tensors on the ROCm GPU ('cuda'); there is no CPU path")
+        _lib.stream_of(t, "seed: min_loss_state")
         if t.numel() != M:
             raise _err(f"min_loss_state of pair ({a}, {b}) has {t.numel()} elements, the pair {M} matches")
         ts.append(t)
     for flat in ([stage.min_loss] if stage is not None else []) + ([inputs.min_loss] if inputs.min_loss is not None else []):
-        base = flat.data_ptr()
-        if flat.numel() == inputs.N and all(t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() == base + 4 * off
-                                            for t, (_a, _b, off, _M) in zip(ts, inputs.segments)):
+        if flat.numel() == inputs.N and _arena.is_arena(flat, ts, inputs.segments):
             return flat
-    dev = inputs.z.device
-    return torch.cat([t.detach().to(device=dev, dtype=torch.float32).reshape(-1) for t in ts]).contiguous()
+    return torch.cat([_flat(t, (), inputs.z.device) for t in ts]).contiguous()
 
 
 def check_rows(n_out: int, counted: int) -> None:
@@ -189,14 +174,13 @@ def seed_arrays(inputs: SeedInputs, min_loss: Optional[torch.Tensor], threshold:
     (n,1,3), features_rest (n,15,3), rotation (n,4), opacity (n,1), scaling (n,3), max_radii2D (n), dist2 (n), sparse_depths
     (V,H,W), masks (V,H,W) bool) and n.  n_out: the rows the caller expects; a contradiction with the counted total raises."""
     N, V, H, W = inputs.N, inputs.V, inputs.H, inputs.W
+    stream = _lib.stream_of(inputs.z, _WHAT)
     dev = inputs.z.device
     for name, t, shape in (("rays_o", inputs.rays_o, (N, 3)), ("rays_d", inputs.rays_d, (N, 3)), ("z", inputs.z, (N,)),
                            ("color", inputs.color, (N, 3)), ("uv", inputs.uv, (N, 2)), ("cam_z", inputs.cam_z, (N,)),
                            ("min_loss", min_loss, (N,))):
         if t is None and name == "min_loss":
             continue
-        if not t.is_cuda:
-            raise _err(f"{name} must be a CUDA tensor (there is no CPU path)")
         if t.device != dev or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
             raise _err(f"{name} must be a contiguous fp32 tensor of shape {shape} on {dev}")
     lib = _lib.load()
@@ -205,7 +189,6 @@ def seed_arrays(inputs: SeedInputs, min_loss: Optional[torch.Tensor], threshold:
     if ws_bytes == 0:
         raise _err(f"{N} matches / {pixels} pixels are more than the kernels take")
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
         ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
         _lib.check(lib.scg_seed_classify(_lib.ptr(min_loss), N, float(threshold), pixels, ws.data_ptr(), ws_bytes, stream),
                    "scg_seed_classify")
