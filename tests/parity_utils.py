@@ -265,3 +265,18 @@ def one_quadrant_scene(P, W, H, seed=0):
     sc.means3D[:, 0] = z * (tany * W / H) * ((16 * qx + 8) / W - 1)
     sc.means3D[:, 1] = z * tany * ((16 * qy + 8) / H - 1)
     return sc
+
+
+def model_oracle_side(model_cpu, act):
+    """Raw CPU leaves, the reference getters on them (autograd), the getters' VALUES replaced by the kernel's activated values
+    `act` = (xyz, opacity, scaling, rotation) so that the oracle runs at the very point the kernels run at."""
+    from scgaussian_amd import ply_io
+    leaves = ply_io.RayBoundModel(**{k: (v.clone().requires_grad_(k not in ("rayo", "rayd")) if isinstance(v, torch.Tensor) else v)
+                                     for k, v in model_cpu.__dict__.items()})
+    xyz, opa, sca, rot = (a.cpu() for a in act)
+
+    def at(getter, value):
+        return getter + (value - getter).detach()
+    inputs = dict(means3D=at(leaves.get_xyz, xyz), opacities=at(leaves.get_opacity, opa), scales=at(leaves.get_scaling, sca),
+                  rotations=at(leaves.get_rotation, rot), shs=leaves.get_features)
+    return leaves, inputs

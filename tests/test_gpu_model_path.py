@@ -41,18 +41,7 @@ def _on_device(model, grad=False):
     return m
 
 
-def _oracle_side(model_cpu, act):
-    """Raw CPU leaves, the reference getters on them (autograd), the getters' VALUES replaced by the kernel's activated values
-    `act` = (xyz, opacity, scaling, rotation) so that the oracle runs at the very point the kernels run at."""
-    leaves = ply_io.RayBoundModel(**{k: (v.clone().requires_grad_(k not in ("rayo", "rayd")) if isinstance(v, torch.Tensor) else v)
-                                     for k, v in model_cpu.__dict__.items()})
-    xyz, opa, sca, rot = (a.cpu() for a in act)
-
-    def at(getter, value):
-        return getter + (value - getter).detach()
-    inputs = dict(means3D=at(leaves.get_xyz, xyz), opacities=at(leaves.get_opacity, opa), scales=at(leaves.get_scaling, sca),
-                  rotations=at(leaves.get_rotation, rot), shs=leaves.get_features)
-    return leaves, inputs
+_oracle_side = pu.model_oracle_side            # (shared with tests/test_gpu_geometry_edges.py)
 
 
 def test_activations_equal_the_reference_getters():
