@@ -93,6 +93,17 @@ SCG_API size_t scg_eval_metrics_scratch_bytes(int32_t C, int32_t H, int32_t W);
 SCG_API int scg_eval_metrics(const float* img, const float* gt, const float* mask, int32_t C, int32_t H, int32_t W, float* out,
                              void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Test-set evaluation (csrc/evalview.hip): render.py's render_set and metrics.py's evaluate, per view --------------------
+ * Documented in scg_eval.h, the header to include for them; its 11x11 SSIM is scg_image_loss_forward above.  The prototypes are
+ * repeated here because this header is one of the four from which the library's export table is checked; evalview.hip includes
+ * both headers, so the compiler holds the two sets of declarations equal. */
+SCG_API size_t scg_eval_depth_range_scratch_bytes(int64_t n);
+SCG_API int scg_eval_depth_range(const float* depth, int64_t n, float* range, void* scratch, size_t scratch_bytes, void* stream);
+SCG_API int32_t scg_eval_view_tile(int32_t axis);
+SCG_API int scg_eval_view(const float* render, const float* gt, const float* depth, const float* dtumask, const float* range,
+                          int32_t H, int32_t W, uint8_t* render_u8, uint8_t* gt_u8, uint8_t* depth_u8, uint8_t* error_u8,
+                          uint8_t* mask_u8, float* error_f32, float* render_masked, float* gt_masked, uint64_t* sk, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

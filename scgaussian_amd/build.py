@@ -5,7 +5,7 @@
 hipcc cross-compiles without a GPU.  The .so is git-ignored but travels to the GPU box with the
 gpurun snapshot.  geometry.hip is compiled with -ffp-contract=off (bit-exact tile assignment).
 optim.hip and initstage.hip are too: Adam rounded where torch rounds it.  So are densify.hip (the clone's xyz, the / 1.6) and
-seed.hip (the seeded points).
+seed.hip (the seeded points) and evalview.hip (the evaluation's 8-bit quantiser).
 """
 from __future__ import annotations
 
@@ -36,13 +36,14 @@ SOURCES = {
     "knn.hip": [],
     "loss.hip": [],
     "dtumask.hip": [],                            # DTU scenes: background mask, alpha term, masked metrics (scg_loss.h)
+    "evalview.hip": ["-ffp-contract=off"],        # test-set evaluation (scg_eval.h): save_image's quantiser rounded as torch rounds it
     "matchloss.hip": [],
     "optim.hip": ["-ffp-contract=off"],           # Adam in torch's rounding order (no fused multiply-adds)
     "initstage.hip": ["-ffp-contract=off"],       # the init stage's Adam: the same arithmetic (csrc/adam_math.h)
     "densify.hip": ["-ffp-contract=off"],         # clone xyz = rayo + rayd * zval and the / 1.6 rounded as torch rounds them
     "seed.hip": ["-ffp-contract=off"],            # create_from_pcd: points = rays_o + rays_d * z as torch's two operators round it
 }
-HEADERS = [os.path.join(CSRC, "scg_common.h"), os.path.join(CSRC, "tile_sort.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "scg_debug.h"), os.path.join(CSRC, "adam_math.h"), os.path.join(CSRC, "compact.h"), os.path.join(INCLUDE, "scg_raster.h"), os.path.join(INCLUDE, "scg_knn.h"), os.path.join(INCLUDE, "scg_loss.h"), os.path.join(INCLUDE, "scg_matchloss.h")]
+HEADERS = [os.path.join(CSRC, "scg_common.h"), os.path.join(CSRC, "tile_sort.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "scg_debug.h"), os.path.join(CSRC, "adam_math.h"), os.path.join(CSRC, "compact.h"), os.path.join(INCLUDE, "scg_raster.h"), os.path.join(INCLUDE, "scg_knn.h"), os.path.join(INCLUDE, "scg_loss.h"), os.path.join(INCLUDE, "scg_matchloss.h"), os.path.join(INCLUDE, "scg_eval.h")]
 
 
 def _hipcc() -> str:
