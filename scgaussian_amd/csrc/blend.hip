@@ -587,6 +587,12 @@ __device__ __forceinline__ int backward_walk(BwdLds& L, const FrameDev& f, int t
     uint64_t odd_lanes = 0xAAAAAAAAAAAAAAAAull, hi_lanes = 0xCCCCCCCCCCCCCCCCull;
     asm volatile("" : "+s"(odd_lanes), "+s"(hi_lanes));
     auto flush = [&](int rows, float dx, float dy0) {
+        // No contraction in here: every fused multiply-add of the flush is written out (__builtin_fmaf), and the hand-written
+        // block's flush, which this one must equal bit for bit (it IS the partial flush of the hand-written walk, so a splat's
+        // sums must not depend on which of the two flushed it), forms Sy as a rounded product and a plain add.  Left to
+        // itself the compiler fuses `Sy += qw.x * dy` (tests/test_gpu_blend_edges.py: records of one pattern at another phase
+        // of the four-row block; tests/test_gpu_parity.py: the two libraries' records on single-atomic frames).
+#pragma clang fp contract(off)
         // the (q, w) stores of the trips and the transposed reads below are different lanes' views of one LDS block: the
         // wave's LDS operations execute in order; the fence keeps the compiler from reordering them
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");

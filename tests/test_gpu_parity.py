@@ -926,6 +926,11 @@ for i, (P, W, H, scale, deg) in enumerate([(4000, 208, 120, -4.0, 3), (9000, 256
     # ... and the backward walk (hand-written since round 4): gradients of a fixed upstream
     for k, v in pu.gradients_for_fixed_upstream(pu.hip_settings(cam, deg, (0.2, 0.4, 0.1)), sc, W, H, seed=50 + i).items():
         out[f"{i}_grad_{k}"] = v
+# ... and the two staged blend calls alone on the planted frames of tests/blend_refs.py (chunk, flush, cull and image edges)
+import blend_refs as B
+for key in B.TWIN_FRAMES:
+    for k, v in B.run_staged(B.frame(key)).items():
+        out[f"edge_{key}_{k}"] = v
 np.savez(sys.argv[2], **out)
 """
 
@@ -935,7 +940,8 @@ def test_hand_written_forward_trip_equals_the_compiler_written_one_bit_for_bit(t
     -DSCG_FWD_TRIP_CXX builds both from C++.  The two libraries must produce bit-identical color / depth / alpha / final_T /
     n_contrib — and the same gradients up to the order of the float atomics (the per-pixel arithmetic of the two backward
     walks is the same operations in the same order): a toolchain change that breaks the inline assembly's assumptions shows
-    up here."""
+    up here.  The two staged blend calls are also run on the planted frames of tests/blend_refs.py: forward outputs bit for bit,
+    and the gradient records bit for bit where every record receives a single atomic."""
     import os
     import subprocess
     import sys
@@ -965,6 +971,16 @@ def test_hand_written_forward_trip_equals_the_compiler_written_one_bit_for_bit(t
             # (two runs of ONE library differ by up to 2.5e-6 of the tensor maximum here — the order of the float atomics,
             #  tools/probes/atomics_noise.py: rotations of scene 1 — so the bar is 2e-5, a fifth of the suite's)
             pu.assert_close(v, ref[f"{i}_grad_{k}"], ("hand-written vs compiler-written backward walk", i, k), rel=2e-5)
+    # the staged blend calls on the planted frames (b), (d), (e) and a frame of translated single-quadrant patterns: the forward
+    # outputs bit for bit; the gradient records bit for bit where every record receives ONE atomic (no summation order)
+    import blend_refs as B
+    for key in B.TWIN_FRAMES:
+        out = B.run_staged(B.frame(key))
+        for k in B.FORWARD_OUTPUTS:
+            assert np.array_equal(out[k], ref[f"edge_{key}_{k}"]), (key, k)
+        assert np.isfinite(out["dsplats"]).all() and out["dsplats"].any(), key
+        if key in B.TWIN_SINGLE_ATOMIC:
+            assert np.array_equal(out["dsplats"], ref[f"edge_{key}_dsplats"]), key
 
 
 def _fused_vs_staged(sc, cam, deg, bg):
