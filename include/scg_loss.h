@@ -104,6 +104,17 @@ SCG_API int scg_eval_view(const float* render, const float* gt, const float* dep
                           int32_t H, int32_t W, uint8_t* render_u8, uint8_t* gt_u8, uint8_t* depth_u8, uint8_t* error_u8,
                           uint8_t* mask_u8, float* error_f32, float* render_masked, float* gt_masked, uint64_t* sk, void* stream);
 
+/* ---- Cross-view depth consistency (csrc/geocheck.hip): utils/geo_check.py's geocheck in two launches ------------------------
+ * Documented in scg_geocheck.h, the header to include for them.  The prototypes are repeated here for the same reason as the
+ * evaluation's above; geocheck.hip includes both headers. */
+SCG_API size_t scg_geocheck_workspace_bytes(int32_t N, int32_t num_src);
+SCG_API int32_t scg_geocheck_tile(int32_t axis);
+SCG_API int scg_geocheck_setup(const double* intrs, const double* exts, int32_t N, int32_t num_src, void* workspace,
+                               size_t workspace_bytes, void* stream);
+SCG_API int scg_geocheck(const float* depths, int32_t N, int32_t H, int32_t W, int32_t num_src, double dist_thresh,
+                         double depth_thresh, int32_t view_thresh, const void* workspace, size_t workspace_bytes, uint8_t* votes,
+                         float* masks, float* filtered, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

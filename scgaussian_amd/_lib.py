@@ -145,6 +145,10 @@ SYMBOLS = {
     "scg_eval_depth_range": (C.c_int, [_P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "scg_eval_view_tile": (C.c_int32, [C.c_int32]),
     "scg_eval_view": (C.c_int, [_P] * 5 + [C.c_int32, C.c_int32] + [_P] * 9 + [_P]),
+    "scg_geocheck_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "scg_geocheck_tile": (C.c_int32, [C.c_int32]),
+    "scg_geocheck_setup": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P]),
+    "scg_geocheck": (C.c_int, [_P] + [C.c_int32] * 4 + [C.c_double, C.c_double, C.c_int32, _P, C.c_size_t, _P, _P, _P, _P]),
     "scg_match_loss_pair": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 9 + [C.c_int32, C.c_float, C.c_float, _P, _P, _P]),
     "scg_init_stage_partials_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "scg_init_stage_run": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 4 + [_P] * 5 + [C.c_int32, C.c_int32] + [C.c_double] * 4

@@ -10,12 +10,17 @@ This is the same computation as torch tensor code on whatever device the depth m
 already in HBM: no host round trip, no cv2).  Differences from the reference, by construction: cv2.remap interpolates
 with 5-bit fixed-point weights, this uses exact fp weights; pixels whose projection is not finite sample 0.
 The function is dead code in the reference (never imported) — it is provided for BASELINE config 3.
+
+`GeoCheck` / `geocheck_hip` at the end of this module are the same rule as two HIP launches (csrc/geocheck.hip), in the reference's
+float64 between its fp32 casts: the path for depth maps that are already on the GPU.
 """
 from __future__ import annotations
 
 from typing import Tuple
 
 import torch
+
+from . import _lib
 
 
 def get_pairs(c2ws: torch.Tensor, num_select: int = 10) -> torch.Tensor:
@@ -149,3 +154,74 @@ def geocheck(intrs: torch.Tensor, c2ws: torch.Tensor, depths: torch.Tensor, dist
         out_d.append(averaged * final.float())
         out_m.append(final.float())
     return torch.stack(out_d), torch.stack(out_m)
+
+
+# ---- the same rule as two HIP launches (csrc/geocheck.hip, include/scg_geocheck.h) ------------------------------------------------
+# Device tensors should go through geocheck_hip / GeoCheck: the twin above builds (J, 3, H*W) intermediates in the intrinsics' dtype
+# and a few dozen launches per view, the kernels decide every pixel of every view in one launch from registers, in the reference's
+# own float64 between its fp32 casts.  CPU tensors raise ScgError: there is no CPU path besides the twin.
+
+class GeoCheck:
+    """The check for `n_views` depth maps of H x W with the `num_src` nearest views of each as its sources.  Owns the workspace
+    (pair table, composed matrices) and the three outputs; `setup` is one launch per set of cameras, `run` one launch per set of
+    depth maps.  Nothing is read on the host: both can be captured in a graph, `run` on depth maps rewritten in place."""
+
+    def __init__(self, n_views: int, H: int, W: int, num_src: int = 15, device="cuda"):
+        self.device = torch.device(device)
+        _lib.stream_of(self.device, "GeoCheck")
+        self._lib = _lib.load()
+        self.n_views, self.H, self.W, self.num_src = int(n_views), int(H), int(W), int(num_src)
+        nbytes = self._lib.scg_geocheck_workspace_bytes(self.n_views, self.num_src)
+        if nbytes == 0 or self.H < 1 or self.W < 1 or self.H * self.W >= 1 << 31:
+            raise ValueError(f"GeoCheck: {n_views} views (1 ... 1024), num_src = {num_src} (1 ... 64) or {H} x {W} out of range")
+        self.J = min(self.num_src, self.n_views)
+        with torch.cuda.device(self.device):
+            self.workspace = torch.zeros((nbytes,), dtype=torch.uint8, device=self.device)
+            shape = (self.n_views, self.H, self.W)
+            self.votes = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+            self.masks = torch.zeros(shape, dtype=torch.float32, device=self.device)
+            self.filtered_depths = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        self.pairs = self.workspace[:self.n_views * self.J * 4].view(torch.int32).reshape(self.n_views, self.J)
+        self._ready = False
+
+    def setup(self, intrs: torch.Tensor, exts: torch.Tensor) -> "GeoCheck":
+        """intrs (N,3,3), exts (N,4,4) of any float dtype, on the device: the pair table and the matrices of every pair."""
+        for t in (intrs, exts):
+            _lib.stream_of(t, "GeoCheck.setup")
+        if tuple(intrs.shape) != (self.n_views, 3, 3) or tuple(exts.shape) != (self.n_views, 4, 4):
+            raise ValueError(f"GeoCheck.setup: intrs must be ({self.n_views},3,3) and exts ({self.n_views},4,4)")
+        k = intrs.detach().to(self.device, torch.float64).contiguous()
+        e = exts.detach().to(self.device, torch.float64).contiguous()
+        with torch.cuda.device(self.device):
+            stream = _lib.stream_of(k, "GeoCheck.setup")
+            _lib.check(self._lib.scg_geocheck_setup(k.data_ptr(), e.data_ptr(), self.n_views, self.num_src, self.workspace.data_ptr(),
+                                                    self.workspace.numel(), stream), "scg_geocheck_setup")
+        self._ready = True
+        return self
+
+    def run(self, depths: torch.Tensor, dist_thresh: float = 1.0, depth_thresh: float = 0.01, view_thresh: int = 5
+            ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """depths (N,H,W) on the device.  Returns (filtered depths, masks), both (N,H,W) fp32 and owned by this object (the next
+        run overwrites them); the per-pixel number of agreeing sources is left in `.votes` (uint8)."""
+        _lib.stream_of(depths, "GeoCheck.run")
+        if not self._ready:
+            raise RuntimeError("GeoCheck.run before GeoCheck.setup")
+        if tuple(depths.shape) != (self.n_views, self.H, self.W):
+            raise ValueError(f"GeoCheck.run: depths must be ({self.n_views},{self.H},{self.W})")
+        d = depths.detach().to(self.device, torch.float32).contiguous()
+        with torch.cuda.device(self.device):
+            stream = _lib.stream_of(d, "GeoCheck.run")
+            _lib.check(self._lib.scg_geocheck(d.data_ptr(), self.n_views, self.H, self.W, self.num_src, float(dist_thresh),
+                                              float(depth_thresh), int(view_thresh), self.workspace.data_ptr(), self.workspace.numel(),
+                                              self.votes.data_ptr(), self.masks.data_ptr(), self.filtered_depths.data_ptr(), stream),
+                       "scg_geocheck")
+        return self.filtered_depths, self.masks
+
+
+def geocheck_hip(intrs: torch.Tensor, c2ws: torch.Tensor, depths: torch.Tensor, dist_thresh: float = 1.0,
+                 depth_thresh: float = 0.01, view_thresh: int = 5, num_src: int = 15) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`geocheck` with its signature and return values, as two HIP launches.  All tensors on the GPU."""
+    _lib.stream_of(depths, "geocheck_hip")
+    n, H, W = depths.shape
+    gc = GeoCheck(n, H, W, num_src=num_src, device=depths.device)
+    return gc.setup(intrs, c2ws).run(depths, dist_thresh, depth_thresh, view_thresh)
