@@ -115,6 +115,17 @@ SCG_API int scg_geocheck(const float* depths, int32_t N, int32_t H, int32_t W, i
                          double depth_thresh, int32_t view_thresh, const void* workspace, size_t workspace_bytes, uint8_t* votes,
                          float* masks, float* filtered, void* stream);
 
+/* ---- Depth colour maps and video frames (csrc/depthviz.hip): `visualization` and render_video.py's loop, per frame ----------
+ * Documented in scg_viz.h, the header to include for them.  The prototypes are repeated here for the same reason as the
+ * evaluation's above; depthviz.hip includes both headers. */
+SCG_API int32_t scg_viz_select_block(void);
+SCG_API size_t scg_viz_select_scratch_bytes(int64_t n);
+SCG_API int scg_viz_select(const float* depth, const float* range, int64_t n, double percentile, float* stats, int32_t* nan_count,
+                           void* scratch, size_t scratch_bytes, void* stream);
+SCG_API int scg_viz_frame(const float* render, const float* depth, const float* range, const float* stats, const int32_t* nan_count,
+                          const uint8_t* lut, int32_t H, int32_t W, uint8_t* depth_color_u8, uint8_t* depth_color_bgr_u8,
+                          uint8_t* depth_u8, uint8_t* render_u8, uint8_t* frame_bgr_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

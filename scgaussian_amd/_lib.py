@@ -149,6 +149,10 @@ SYMBOLS = {
     "scg_geocheck_tile": (C.c_int32, [C.c_int32]),
     "scg_geocheck_setup": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P]),
     "scg_geocheck": (C.c_int, [_P] + [C.c_int32] * 4 + [C.c_double, C.c_double, C.c_int32, _P, C.c_size_t, _P, _P, _P, _P]),
+    "scg_viz_select_block": (C.c_int32, []),
+    "scg_viz_select_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "scg_viz_select": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P, _P, _P, C.c_size_t, _P]),
+    "scg_viz_frame": (C.c_int, [_P] * 6 + [C.c_int32, C.c_int32] + [_P] * 5 + [_P]),
     "scg_match_loss_pair": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 9 + [C.c_int32, C.c_float, C.c_float, _P, _P, _P]),
     "scg_init_stage_partials_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "scg_init_stage_run": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 4 + [_P] * 5 + [C.c_int32, C.c_int32] + [C.c_double] * 4

@@ -5,7 +5,8 @@
 hipcc cross-compiles without a GPU.  The .so is git-ignored but travels to the GPU box with the
 gpurun snapshot.  geometry.hip is compiled with -ffp-contract=off (bit-exact tile assignment).
 optim.hip and initstage.hip are too: Adam rounded where torch rounds it.  So are densify.hip (the clone's xyz, the / 1.6) and
-seed.hip (the seeded points) and evalview.hip (the evaluation's 8-bit quantiser) and geocheck.hip (fp64 as numpy rounds it).
+seed.hip (the seeded points) and evalview.hip (the evaluation's 8-bit quantiser) and geocheck.hip (fp64 as numpy rounds it) and
+depthviz.hip (the percentile's interpolation and the colour index as numpy and matplotlib round them).
 """
 from __future__ import annotations
 
@@ -43,8 +44,9 @@ SOURCES = {
     "densify.hip": ["-ffp-contract=off"],         # clone xyz = rayo + rayd * zval and the / 1.6 rounded as torch rounds them
     "seed.hip": ["-ffp-contract=off"],            # create_from_pcd: points = rays_o + rays_d * z as torch's two operators round it
     "geocheck.hip": ["-ffp-contract=off"],        # cross-view depth check (scg_geocheck.h): numpy's float64 products and sums, none fused
+    "depthviz.hip": ["-ffp-contract=off"],        # depth colour maps and video frames (scg_viz.h): numpy's percentile, matplotlib's Normalize
 }
-HEADERS = [os.path.join(CSRC, "scg_common.h"), os.path.join(CSRC, "tile_sort.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "scg_debug.h"), os.path.join(CSRC, "adam_math.h"), os.path.join(CSRC, "compact.h"), os.path.join(INCLUDE, "scg_raster.h"), os.path.join(INCLUDE, "scg_knn.h"), os.path.join(INCLUDE, "scg_loss.h"), os.path.join(INCLUDE, "scg_matchloss.h"), os.path.join(INCLUDE, "scg_eval.h"), os.path.join(INCLUDE, "scg_geocheck.h")]
+HEADERS = [os.path.join(CSRC, "scg_common.h"), os.path.join(CSRC, "tile_sort.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "scg_debug.h"), os.path.join(CSRC, "adam_math.h"), os.path.join(CSRC, "compact.h"), os.path.join(INCLUDE, "scg_raster.h"), os.path.join(INCLUDE, "scg_knn.h"), os.path.join(INCLUDE, "scg_loss.h"), os.path.join(INCLUDE, "scg_matchloss.h"), os.path.join(INCLUDE, "scg_eval.h"), os.path.join(INCLUDE, "scg_geocheck.h"), os.path.join(INCLUDE, "scg_viz.h")]
 
 
 def _hipcc() -> str:

@@ -166,16 +166,20 @@ def _save_png(path, arr):
     Image.fromarray(arr).save(path, format="PNG")
 
 
-def render_set(views, gaussians, pipe, background, out_dir=None, name="test", iteration=0, render=_render.render, lpips_fn=None):
+def render_set(views, gaussians, pipe, background, out_dir=None, name="test", iteration=0, render=_render.render, lpips_fn=None,
+               color_depth=False):
     """render.py:133-162 and metrics.py's evaluate over `views` under torch.no_grad().  A view needs what render() needs plus
     `original_image` and, optionally, `dtumask`.  Returns (full, per_view, images): the two dicts in the shape of results.json /
     per_view.json — keyed by the method "ours_<iteration>", the views named "<idx:05d>.png" — and per view the dict of uint8 device
     tensors.  With `out_dir` the reference's tree <out_dir>/<name>/ours_<iteration>/{renders,gt,depth,error_map,dtumask}/ is
-    written with PIL from those tensors, copied to the host after the loop.  The matplotlib depth visualisation and the colour
-    point cloud of render.py are not part of this."""
+    written with PIL from those tensors, copied to the host after the loop.  With `color_depth` every view's dict also holds
+    `depth_color`, render.py:162's `visualization` of the normalised depth as an (H,W,3) uint8 device tensor (video.DepthColorizer),
+    written as depth/color_<idx:05d>.png; the default leaves every result, file and key as without it.  The colour point cloud of
+    render.py is not part of this."""
     views = list(views)
     method = f"ours_{iteration}"
     images = []
+    colorizers = {}
     with torch.no_grad():
         es = EvalSet(max(len(views), 1), lpips_fn=lpips_fn, device=background.device)
         for idx, view in enumerate(views):
@@ -183,6 +187,12 @@ def render_set(views, gaussians, pipe, background, out_dir=None, name="test", it
             out = es.add(f"{idx:05d}.png", pkg["render"], view.original_image[0:3, :, :], pkg["rendered_depth"],
                          getattr(view, "dtumask", None))
             images.append({k: out[k] for k in ("renders", "gt", "depth", "error_map", "dtumask")})
+            if color_depth:
+                from .video import DepthColorizer
+                shape = tuple(out["depth"].shape)
+                if shape not in colorizers:
+                    colorizers[shape] = DepthColorizer(*shape, device=background.device)
+                images[-1]["depth_color"] = colorizers[shape].colorize_depth(pkg["rendered_depth"])
         if out_dir is not None:
             base = os.path.join(out_dir, name, method)
             for sub in SUBDIRS:
@@ -193,6 +203,8 @@ def render_set(views, gaussians, pipe, background, out_dir=None, name="test", it
                 for sub, key in zip(SUBDIRS, ("renders", "gt", "depth", "error_map", "dtumask")):
                     if im[key] is not None:
                         _save_png(os.path.join(base, sub, f"{idx:05d}.png"), im[key].numpy())
+                if color_depth:
+                    _save_png(os.path.join(base, "depth", f"color_{idx:05d}.png"), im["depth_color"].numpy())
         full, per_view = es.results() if views else ({}, {})
     return {method: full}, {method: per_view}, images
 
