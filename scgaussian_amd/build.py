@@ -5,8 +5,9 @@
 hipcc cross-compiles without a GPU.  The .so is git-ignored but travels to the GPU box with the
 gpurun snapshot.  geometry.hip is compiled with -ffp-contract=off (bit-exact tile assignment).
 optim.hip and initstage.hip are too: Adam rounded where torch rounds it.  So are densify.hip (the clone's xyz, the / 1.6) and
-seed.hip (the seeded points) and evalview.hip (the evaluation's 8-bit quantiser) and geocheck.hip (fp64 as numpy rounds it) and
-depthviz.hip (the percentile's interpolation and the colour index as numpy and matplotlib round them).
+seed.hip (the seeded points) and evalview.hip (the evaluation's masked images and error map) and geocheck.hip (fp64 as numpy rounds
+it) and depthviz.hip (the percentile's interpolation and the colour index as numpy and matplotlib round them).  The 8-bit quantiser
+those two share (csrc/pixel_rules.h) turns contraction off in its own body and does not depend on the flag.
 """
 from __future__ import annotations
 
@@ -37,7 +38,8 @@ SOURCES = {
     "knn.hip": [],
     "loss.hip": [],
     "dtumask.hip": [],                            # DTU scenes: background mask, alpha term, masked metrics (scg_loss.h)
-    "evalview.hip": ["-ffp-contract=off"],        # test-set evaluation (scg_eval.h): save_image's quantiser rounded as torch rounds it
+    # (the 8-bit quantiser pins its own contraction, csrc/pixel_rules.h: in the next two files the flag is there for the rest)
+    "evalview.hip": ["-ffp-contract=off"],        # test-set evaluation (scg_eval.h): the masked images and the error map's products as torch rounds them
     "matchloss.hip": [],
     "optim.hip": ["-ffp-contract=off"],           # Adam in torch's rounding order (no fused multiply-adds)
     "initstage.hip": ["-ffp-contract=off"],       # the init stage's Adam: the same arithmetic (csrc/adam_math.h)
@@ -46,7 +48,7 @@ SOURCES = {
     "geocheck.hip": ["-ffp-contract=off"],        # cross-view depth check (scg_geocheck.h): numpy's float64 products and sums, none fused
     "depthviz.hip": ["-ffp-contract=off"],        # depth colour maps and video frames (scg_viz.h): numpy's percentile, matplotlib's Normalize
 }
-HEADERS = [os.path.join(CSRC, "scg_common.h"), os.path.join(CSRC, "tile_sort.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "scg_debug.h"), os.path.join(CSRC, "adam_math.h"), os.path.join(CSRC, "compact.h"), os.path.join(INCLUDE, "scg_raster.h"), os.path.join(INCLUDE, "scg_knn.h"), os.path.join(INCLUDE, "scg_loss.h"), os.path.join(INCLUDE, "scg_matchloss.h"), os.path.join(INCLUDE, "scg_eval.h"), os.path.join(INCLUDE, "scg_geocheck.h"), os.path.join(INCLUDE, "scg_viz.h")]
+HEADERS = [os.path.join(CSRC, "scg_common.h"), os.path.join(CSRC, "tile_sort.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "scg_debug.h"), os.path.join(CSRC, "adam_math.h"), os.path.join(CSRC, "compact.h"), os.path.join(CSRC, "reduce.h"), os.path.join(CSRC, "pixel_rules.h"), os.path.join(INCLUDE, "scg_raster.h"), os.path.join(INCLUDE, "scg_knn.h"), os.path.join(INCLUDE, "scg_loss.h"), os.path.join(INCLUDE, "scg_matchloss.h"), os.path.join(INCLUDE, "scg_eval.h"), os.path.join(INCLUDE, "scg_geocheck.h"), os.path.join(INCLUDE, "scg_viz.h")]
 
 
 def _hipcc() -> str:

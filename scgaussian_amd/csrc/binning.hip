@@ -5,6 +5,7 @@
 // HBM-bound streaming / scatter kernels: 16-byte lane-contiguous loads, wave64 ballot ranking, LDS
 // histograms.  No MFMA (nothing here is a contraction).
 #include "scg_common.h"
+#include "reduce.h"
 
 namespace scg {
 
@@ -45,9 +46,7 @@ __global__ __launch_bounds__(kBlock) void scan_block_sums_kernel(const uint32_t*
                                                                  uint32_t* __restrict__ block_sums) {
     __shared__ uint32_t s_wave[4];
     const int64_t i = (int64_t)blockIdx.x * kScanChunk + threadIdx.x;
-    uint32_t s = (i < n) ? in[i] : 0u;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, kWave);
+    const uint32_t s = wave_reduce((i < n) ? in[i] : 0u, Sum());
     if (lane_id() == 0) s_wave[wave_id()] = s;
     __syncthreads();
     if (threadIdx.x == 0) block_sums[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
@@ -193,8 +192,7 @@ __global__ __launch_bounds__(kBlock) void total_kernel(const uint32_t* __restric
     __shared__ uint32_t s_wave[4];
     uint32_t s = 0;
     for (int i = threadIdx.x; i < nb; i += kBlock) s += block_sums[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, kWave);
+    s = wave_reduce(s, Sum());
     if (lane_id() == 0) s_wave[wave_id()] = s;
     __syncthreads();
     if (threadIdx.x == 0) *total_out = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];

@@ -36,6 +36,7 @@
 //     instruction count of its trip almost 1:1 (four v_mov more per trip: +6 %; thirteen scalar instructions and
 //     branches less: -4 %).  Hence the hand-written forward trip below.
 #include "scg_common.h"
+#include "reduce.h"
 #include "tile_sort.h"
 
 namespace scg {
@@ -985,9 +986,7 @@ __global__ __launch_bounds__(kWave) SCG_BWD_OCCUPANCY void blend_backward_kernel
     const int n = (int)(range.y - range.x);
     const BwdPixel s = load_pixel_final(f, px, py, final_T, n_contrib, dL_dcolor, dL_ddepth, dL_dalpha);
     // highest list index any pixel of the quadrant blended
-    uint32_t mx = s.last;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = max(mx, (uint32_t)__shfl_down((int)mx, off, kWave));
+    const uint32_t mx = wave_reduce((uint32_t)s.last, Max());
     const int limit = min(n, __builtin_amdgcn_readfirstlane((int)mx));
 #ifdef SCG_PROBE_TIMELINE                // tools/probes/backward_timeline.py
     const uint32_t tp0 = (uint32_t)wall_clock64();

@@ -18,12 +18,15 @@
 //      at most kMergeRounds distinct digits; lanes left after that add on their own
 //   2  every wave of the first pass has a histogram of its own (the later passes count only the few values under the chosen prefix)
 //
-// Compiled with -ffp-contract=off: x, the interpolation between the two order statistics, the normalisation and both byte casts
-// are chains of separately rounded fp32 operations, as numpy and torch round them.  Divisions are the correctly rounded __fdiv_rn;
-// the one of the normalisation is matplotlib's, in fp64 (viz_frame_kernel).
+// Compiled with -ffp-contract=off: x, the interpolation between the two order statistics and the normalisation are chains of
+// separately rounded fp32 operations, as numpy and torch round them (the byte rules are pixel_rules.h's; its quantiser pins its own
+// two roundings).  Divisions are the correctly rounded __fdiv_rn; the one of the normalisation is matplotlib's, in fp64
+// (viz_frame_kernel).
 #include <math.h>
 
 #include "scg_common.h"
+#include "reduce.h"
+#include "pixel_rules.h"
 #include "../../include/scg_viz.h"
 #include "../../include/scg_loss.h"
 
@@ -184,17 +187,10 @@ __global__ __launch_bounds__(kBlock) void select_pass_kernel(const float* __rest
         if (v) atomicAdd(&g_hist[i], v);
     }
     if (PASS == 0) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            max_inv = max(max_inv, (uint32_t)__shfl_down(max_inv, off, kWave));
-            nans += __shfl_down(nans, off, kWave);
-        }
-        if (lane_id() == 0) { s_red[0][wave_id()] = max_inv; s_red[1][wave_id()] = nans; }
+        wave_publish(max_inv, nans, s_red[0], s_red[1], Max(), Sum());
         __syncthreads();
         if (threadIdx.x == 0) {
-            uint32_t m = 0, z = 0;
-#pragma unroll
-            for (int w = 0; w < kBlock / kWave; ++w) { m = max(m, s_red[0][w]); z += s_red[1][w]; }
+            const uint32_t m = wg_fold<kBlock / kWave>(s_red[0], Max()), z = wg_fold<kBlock / kWave>(s_red[1], Sum());
             if (m) atomicMax(&scratch[kOffMaxInv], m);
             if (z) atomicAdd(&scratch[kOffNan], z);
         }
@@ -214,19 +210,6 @@ __global__ __launch_bounds__(kBlock) void select_finish_kernel(const uint32_t* _
     if (nans) vmin = vmax = __uint_as_float(0x7FC00000u);
     stats[0] = vmin; stats[1] = vmax; stats[2] = a; stats[3] = b;
     *nan_count = (int32_t)nans;
-}
-
-// torchvision.utils.save_image's quantiser (scg_eval.h); q(NaN) = 0
-__device__ __forceinline__ uint32_t quantise(float x) {
-    const float v = x * 255.f + 0.5f;
-    if (!(v >= 0.f)) return 0u;
-    return v >= 255.f ? 255u : (uint32_t)v;
-}
-__device__ __forceinline__ float unit_clamp(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }      // a NaN stays a NaN (torch.clamp)
-// render_video.py:148: the truncating cast of clamp(r) * 255.; NaN -> 0
-__device__ __forceinline__ uint32_t video_byte(float r) {
-    const float v = unit_clamp(r) * 255.f;
-    return v != v ? 0u : (uint32_t)v;
 }
 
 constexpr int kPxPerThread = 4;                            // 12 bytes of an interleaved image: three aligned words

@@ -11,12 +11,14 @@
 // above it, so a thread owns one column of one row segment and re-reads up to run - 1 rows above the segment for its seed: loads
 // coalesce along x, no workgroup waits for another.  Comparisons only: exact.
 //
-// The sums follow loss.hip: per-workgroup partial sums, then ONE workgroup adds them in a fixed order.  No float atomics, the
-// results are bitwise reproducible.  All three are bandwidth-trivial next to a render (one or two reads per pixel); what they
-// replace is a hundred launches and three host reads per iteration.
+// The sums follow loss.hip: per-workgroup partial sums, then ONE workgroup adds them, all in the fixed order of reduce.h.
+// All three are bandwidth-trivial next to a render (one or two reads per pixel); what they replace is a hundred launches and three
+// host reads per iteration.
 #include <math.h>
 
 #include "scg_common.h"
+#include "reduce.h"
+#include "pixel_rules.h"
 #include "../../include/scg_loss.h"
 
 namespace scg {
@@ -26,30 +28,6 @@ constexpr int kChunk = 4096;                     // elements a workgroup of the 
 constexpr int kPerThread = kChunk / kBlock;      // 16, all loaded before the first is used
 constexpr int kReduceBlock = 1024;
 constexpr int kMaxMetricChannels = 16;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    return v;
-}
-
-// sum over the workgroup, waves added in index order (NW waves); every thread gets the total
-template <int NW, typename T>
-__device__ __forceinline__ T wg_total(T wave_value, T* s_red) {
-    if (lane_id() == 0) s_red[wave_id()] = wave_value;
-    __syncthreads();
-    T t = s_red[0];
-#pragma unroll
-    for (int k = 1; k < NW; ++k) t += s_red[k];
-    __syncthreads();
-    return t;
-}
 
 // ---- background mask --------------------------------------------------------------------------------------------------------
 // `out` may be `gt` itself: a pixel is read by its own thread before that thread writes it, and by the threads of the segments
@@ -80,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void dtu_bg_mask_kernel(const float* gt, in
             n += m ? 1u : 0u;
         }
     }
-    const uint32_t total = wg_total<kBlock / kWave>(wave_sum_u32(n), s_red);
+    const uint32_t total = wg_reduce<kBlock / kWave>(n, s_red, Sum());
     if (threadIdx.x == 0 && total) atomicAdd(count, total);         // integers: the sum does not depend on the order
 }
 
@@ -99,7 +77,7 @@ __global__ __launch_bounds__(kBlock) void masked_sum_kernel(const float* __restr
     float acc = 0.f;
 #pragma unroll
     for (int k = 0; k < kPerThread; ++k) acc += (base + (int64_t)k * kBlock < n && m[k]) ? v[k] : 0.f;      // selected, not multiplied
-    const float total = wg_total<kBlock / kWave>(wave_sum(acc), s_red);
+    const float total = wg_reduce<kBlock / kWave>(acc, s_red, Sum());
     if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
@@ -108,7 +86,7 @@ __global__ __launch_bounds__(kReduceBlock) void masked_mean_reduce_kernel(const 
     __shared__ float s_red[kReduceBlock / kWave];
     float a = 0.f;
     for (int i = threadIdx.x; i < n; i += kReduceBlock) a += partials[i];
-    const float total = wg_total<kReduceBlock / kWave>(wave_sum(a), s_red);
+    const float total = wg_reduce<kReduceBlock / kWave>(a, s_red, Sum());
     if (threadIdx.x == 0) {
         const uint32_t c = count[0];
         out[0] = c ? total / (float)c : __builtin_nanf("");          // torch: the mean of an empty selection is NaN
@@ -124,8 +102,6 @@ __global__ __launch_bounds__(kBlock) void masked_mean_backward_kernel(const uint
 }
 
 // ---- evaluation metrics -----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }      // a NaN stays a NaN (torch.clamp)
-
 // grid (chunks, C): partials[c * chunks + chunk] = (sum |a - b|, sum (a - b)^2) over the selected pixels of the chunk
 __global__ __launch_bounds__(kBlock) void eval_metrics_kernel(const float* __restrict__ img, const float* __restrict__ gt,
                                                               const float* __restrict__ mask, int64_t hw, float2* __restrict__ partials,
@@ -146,14 +122,14 @@ __global__ __launch_bounds__(kBlock) void eval_metrics_kernel(const float* __res
 #pragma unroll
     for (int k = 0; k < kPerThread; ++k) {
         const bool sel = base + (int64_t)k * kBlock < hw && m[k] > 0.f;
-        const float d = clamp01(a[k]) - clamp01(b[k]);
+        const float d = unit_clamp(a[k]) - unit_clamp(b[k]);
         sa += sel ? fabsf(d) : 0.f;
         sq += sel ? d * d : 0.f;
         n += sel ? 1u : 0u;
     }
-    const float t_a = wg_total<kBlock / kWave>(wave_sum(sa), s_red);
-    const float t_q = wg_total<kBlock / kWave>(wave_sum(sq), s_red);
-    const uint32_t t_n = wg_total<kBlock / kWave>(wave_sum_u32(n), s_cnt);
+    const float t_a = wg_reduce<kBlock / kWave>(sa, s_red, Sum());
+    const float t_q = wg_reduce<kBlock / kWave>(sq, s_red, Sum());
+    const uint32_t t_n = wg_reduce<kBlock / kWave>(n, s_cnt, Sum());
     if (threadIdx.x == 0) {
         partials[(size_t)c * gridDim.x + blockIdx.x] = make_float2(t_a, t_q);
         if (c == 0) selected[blockIdx.x] = t_n;
@@ -168,13 +144,13 @@ __global__ __launch_bounds__(kReduceBlock) void eval_metrics_reduce_kernel(const
     __shared__ uint32_t s_cnt[kReduceBlock / kWave];
     uint32_t n = 0;
     for (int i = threadIdx.x; i < chunks; i += kReduceBlock) n += selected[i];
-    const uint32_t count = wg_total<kReduceBlock / kWave>(wave_sum_u32(n), s_cnt);
+    const uint32_t count = wg_reduce<kReduceBlock / kWave>(n, s_cnt, Sum());
     float abs_all = 0.f, psnr_all = 0.f;
     for (int c = 0; c < C; ++c) {
         float a = 0.f, q = 0.f;
         for (int i = threadIdx.x; i < chunks; i += kReduceBlock) { const float2 p = partials[(size_t)c * chunks + i]; a += p.x; q += p.y; }
-        const float t_a = wg_total<kReduceBlock / kWave>(wave_sum(a), s_red);
-        const float t_q = wg_total<kReduceBlock / kWave>(wave_sum(q), s_red);
+        const float t_a = wg_reduce<kReduceBlock / kWave>(a, s_red, Sum());
+        const float t_q = wg_reduce<kReduceBlock / kWave>(q, s_red, Sum());
         // utils/image_utils.py:18-19 per channel
         const float mse = count ? t_q / (float)count : __builtin_nanf("");
         abs_all += t_a;

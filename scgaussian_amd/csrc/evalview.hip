@@ -9,15 +9,17 @@
 // six planes of render and ground truth: a workgroup stages its tile of them in LDS with a halo of 2, reflected at the image border
 // (ReflectionPad2d(2)), and every other input is read once by the pixel's own thread.  No workgroup waits for another.
 //
-// Compiled with -ffp-contract=off: the quantiser q(x) = trunc(clamp(fl(fl(x * 255) + 0.5), 0, 255)) and the masked images
-// fl(fl(a * m) + fl(1 - m)) are held bit for bit to torch's separately rounded operators, and the error map's products are
-// rounded before they are summed, as torch's x ** 2 and x * y are.  Divisions are the correctly rounded __fdiv_rn (seed.hip).
+// Compiled with -ffp-contract=off: the masked images fl(fl(a * m) + fl(1 - m)) are held bit for bit to torch's separately rounded
+// operators, and the error map's products are rounded before they are summed, as torch's x ** 2 and x * y are (the quantiser of
+// pixel_rules.h pins its own two roundings).  Divisions are the correctly rounded __fdiv_rn (seed.hip).
 //
 // S and K are integers: a workgroup adds its pixels' in 32 bits (at most 256 * 3 * 255^2 < 2^26) and issues one 64-bit atomic each;
 // the totals are exact in any order.
 #include <math.h>
 
 #include "scg_common.h"
+#include "reduce.h"
+#include "pixel_rules.h"
 #include "../../include/scg_eval.h"
 #include "../../include/scg_loss.h"
 
@@ -30,28 +32,16 @@ constexpr int kRangeChunk = 4096;                // depths a workgroup of the ra
 constexpr int kRangeReduceBlock = 1024;
 static_assert(kTileW * kTileH == kBlock, "one thread per pixel of the tile");
 
-// torch.min / torch.max: a NaN on either side wins
-__device__ __forceinline__ float nan_min(float a, float b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
-__device__ __forceinline__ float nan_max(float a, float b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
-
-// (min, max) over the workgroup of NW waves; every thread gets the result
+// (min, max) over the workgroup of NW waves in the order of reduce.h, one barrier; every thread gets the result
 template <int NW>
-__device__ __forceinline__ float2 wg_min_max(float mn, float mx, float2* s_red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        mn = nan_min(mn, __shfl_down(mn, off, kWave));
-        mx = nan_max(mx, __shfl_down(mx, off, kWave));
-    }
-    if (lane_id() == 0) s_red[wave_id()] = make_float2(mn, mx);
+__device__ __forceinline__ float2 wg_min_max(float mn, float mx, float (*s_red)[NW]) {
+    wave_publish(mn, mx, s_red[0], s_red[1], NanMin(), NanMax());
     __syncthreads();
-    float2 t = s_red[0];
-#pragma unroll
-    for (int k = 1; k < NW; ++k) { t.x = nan_min(t.x, s_red[k].x); t.y = nan_max(t.y, s_red[k].y); }
-    return t;
+    return make_float2(wg_fold<NW>(s_red[0], NanMin()), wg_fold<NW>(s_red[1], NanMax()));
 }
 
 __global__ __launch_bounds__(kBlock) void depth_range_kernel(const float* __restrict__ depth, int64_t n, float2* __restrict__ partials) {
-    __shared__ float2 s_red[kBlock / kWave];
+    __shared__ float s_red[2][kBlock / kWave];
     const int64_t base = (int64_t)blockIdx.x * kRangeChunk + threadIdx.x;
     float mn = INFINITY, mx = -INFINITY;
 #pragma unroll
@@ -65,33 +55,18 @@ __global__ __launch_bounds__(kBlock) void depth_range_kernel(const float* __rest
 
 __global__ __launch_bounds__(kRangeReduceBlock) void depth_range_reduce_kernel(const float2* __restrict__ partials, int chunks,
                                                                                float* __restrict__ range) {
-    __shared__ float2 s_red[kRangeReduceBlock / kWave];
+    __shared__ float s_red[2][kRangeReduceBlock / kWave];
     float mn = INFINITY, mx = -INFINITY;
     for (int i = threadIdx.x; i < chunks; i += kRangeReduceBlock) { const float2 p = partials[i]; mn = nan_min(mn, p.x); mx = nan_max(mx, p.y); }
     const float2 t = wg_min_max<kRangeReduceBlock / kWave>(mn, mx, s_red);
     if (threadIdx.x == 0) { range[0] = t.x; range[1] = t.y; }
 }
 
-// torchvision.utils.save_image's quantiser; q(NaN) = 0 (torch leaves that cast undefined)
-__device__ __forceinline__ uint32_t quantise(float x) {
-    const float v = x * 255.f + 0.5f;                  // two roundings: contraction is off for this file
-    if (!(v >= 0.f)) return 0u;                        // below the clamp, and NaN
-    return v >= 255.f ? 255u : (uint32_t)v;            // the cast truncates
-}
-
-__device__ __forceinline__ float unit_clamp(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }      // a NaN stays a NaN (torch.clamp)
-
 // index i of a reflection-padded axis of n >= 3 entries, i in [-2, n + 1]; the tile's overhang past the image is pinned to the
 // last entry (no pixel inside the image reads those slots)
 __device__ __forceinline__ int reflect(int i, int n) {
     const int r = i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i);
     return min(max(r, 0), n - 1);
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    return v;
 }
 
 __global__ __launch_bounds__(kBlock) void eval_view_kernel(const float* __restrict__ render, const float* __restrict__ gt,
@@ -164,14 +139,10 @@ __global__ __launch_bounds__(kBlock) void eval_view_kernel(const float* __restri
         const float lo = range[0], hi = range[1];
         depth_u8[p] = (uint8_t)quantise(__fdiv_rn(depth[p] - lo, hi - lo));
     }
-    s = wave_sum_u32(s);
-    k = wave_sum_u32(k);
-    if (lane_id() == 0) { s_red[0][wave_id()] = s; s_red[1][wave_id()] = k; }
+    wave_publish(s, k, s_red[0], s_red[1], Sum(), Sum());
     __syncthreads();
     if (threadIdx.x == 0) {
-        uint32_t ts = 0, tk = 0;
-#pragma unroll
-        for (int w = 0; w < kBlock / kWave; ++w) { ts += s_red[0][w]; tk += s_red[1][w]; }
+        const uint32_t ts = wg_fold<kBlock / kWave>(s_red[0], Sum()), tk = wg_fold<kBlock / kWave>(s_red[1], Sum());
         if (ts) atomicAdd(&sk[0], (unsigned long long)ts);
         if (tk) atomicAdd(&sk[1], (unsigned long long)tk);
     }

@@ -14,6 +14,7 @@
 // One thread per Gaussian, 256-thread workgroups (4 waves).  Loads of the (P,3)/(P,4) arrays are
 // lane-contiguous; the 192-byte SH record is read with 16-byte loads (12 per lane at degree 3).
 #include "scg_common.h"
+#include "reduce.h"
 #include "tile_walk.h"
 
 #include <type_traits>
@@ -494,9 +495,7 @@ __device__ __forceinline__ void geometry_forward_body(
     flush_stage(stage, i - lane_id(), f.P, splats, radii, clamped, rects, depth_keys);
 
     // per-block sum of tiles_touched: first phase of the inclusive scan, fused here
-    uint32_t s = my_tiles;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, kWave);
+    const uint32_t s = wave_reduce(my_tiles, Sum());
     if (lane_id() == 0) s_wave_sum[wave_id()] = s;
     __syncthreads();
     if (threadIdx.x == 0) block_sums[blockIdx.x] = s_wave_sum[0] + s_wave_sum[1] + s_wave_sum[2] + s_wave_sum[3];
@@ -597,9 +596,7 @@ __device__ __forceinline__ void geometry_hist_body(
         { const uint32_t t = (uint32_t)wall_clock64(); g_tp[3] += t - g_tp[4]; g_tp[4] = t; ++tp_iters; }
 #endif
         pending = i - lane;
-        uint32_t s = my_tiles;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, kWave);
+        const uint32_t s = wave_reduce(my_tiles, Sum());
         if (lane == 0 && s) atomicAdd(&s_blk[(chunk >> 2) - blk_a], s);
         chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)grabbed);
     }

@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "scg_common.h"
+#include "reduce.h"
 #include "../../include/scg_loss.h"
 
 namespace scg {
@@ -49,16 +50,6 @@ static Window make_window() {
     return w;
 }
 
-__device__ __forceinline__ float block_sum(float v, float* s_red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    if (lane_id() == 0) s_red[wave_id()] = v;
-    __syncthreads();
-    const float t = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-    __syncthreads();
-    return t;
-}
-
 __global__ __launch_bounds__(kBlock) void image_loss_forward_kernel(const float* __restrict__ img,
                                                                     const float* __restrict__ gt, int H, int W,
                                                                     Window win, float2* __restrict__ partials,
@@ -66,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void image_loss_forward_kernel(const float*
     __shared__ float s_x[kLHY][kLH + 1];
     __shared__ float s_y[kLHY][kLH + 1];
     __shared__ float s_h[5][kLHY][kLT + 1];       // horizontal pass: x, y, xx, yy, xy
-    __shared__ float s_red[4];
+    __shared__ float s_red[kBlock / kWave];
     const int c = blockIdx.z;
     const int x0 = blockIdx.x * kLT, y0 = blockIdx.y * kLTY;
     const size_t plane = (size_t)c * H * W;
@@ -155,28 +146,28 @@ __global__ __launch_bounds__(kBlock) void image_loss_forward_kernel(const float*
             }
         }
     }
-    const float t_l1 = block_sum(l1, s_red);
-    const float t_ss = block_sum(ss, s_red);
+    const float t_l1 = wg_reduce<kBlock / kWave>(l1, s_red, Sum());
+    const float t_ss = wg_reduce<kBlock / kWave>(ss, s_red, Sum());
     if (threadIdx.x == 0)
         partials[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = make_float2(t_l1, t_ss);
 }
 
-// fixed-order reduction of the per-workgroup partial sums (single 1024-thread workgroup)
+// the per-workgroup partial sums added by ONE workgroup in the fixed order of reduce.h
 // lambda_dssim >= 0: also sums[2] = (1 - lambda) * L1 + lambda * (1 - SSIM), the training loss (train.py:160-161) — the
 // operations of the reference's expression in its order, each rounded on its own (no contraction)
-__global__ __launch_bounds__(1024) void image_loss_reduce_kernel(const float2* __restrict__ partials, int n,
-                                                                 float* __restrict__ sums, float inv_count,
-                                                                 float lambda_dssim) {
-    __shared__ float s_a[16], s_b[16];
+constexpr int kLossReduceBlock = 1024;
+__global__ __launch_bounds__(kLossReduceBlock) void image_loss_reduce_kernel(const float2* __restrict__ partials, int n,
+                                                                             float* __restrict__ sums, float inv_count,
+                                                                             float lambda_dssim) {
+    constexpr int NW = kLossReduceBlock / kWave;
+    __shared__ float s_a[NW], s_b[NW];
     float a = 0.f, b = 0.f;
-    for (int i = threadIdx.x; i < n; i += 1024) { const float2 p = partials[i]; a += p.x; b += p.y; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off, kWave); b += __shfl_down(b, off, kWave); }
-    if (lane_id() == 0) { s_a[wave_id()] = a; s_b[wave_id()] = b; }
+    for (int i = threadIdx.x; i < n; i += kLossReduceBlock) { const float2 p = partials[i]; a += p.x; b += p.y; }
+    wave_publish(a, b, s_a, s_b, Sum(), Sum());
     __syncthreads();
     if (threadIdx.x == 0) {
-        float ta = 0.f, tb = 0.f;
-        for (int k = 0; k < 16; ++k) { ta += s_a[k]; tb += s_b[k]; }
+        // (from wave 0's word, not from 0.f: a and b start at +0.f and x + y is -0.f only if both are, so no word is -0.f)
+        const float ta = wg_fold<NW>(s_a, Sum()), tb = wg_fold<NW>(s_b, Sum());
         sums[0] = ta; sums[1] = tb;
         if (lambda_dssim >= 0.f) {
 #pragma clang fp contract(off)
@@ -297,7 +288,7 @@ static int image_loss_forward(const float* img, const float* gt, int32_t C, int3
     const dim3 grid((W + kLT - 1) / kLT, (H + kLTY - 1) / kLTY, C);
     float2* partials = reinterpret_cast<float2*>(scratch);
     hipLaunchKernelGGL(image_loss_forward_kernel, grid, dim3(kBlock), 0, s, img, gt, H, W, win, partials, dmaps);
-    hipLaunchKernelGGL(image_loss_reduce_kernel, dim3(1), dim3(1024), 0, s, partials, (int)(grid.x * grid.y * grid.z),
+    hipLaunchKernelGGL(image_loss_reduce_kernel, dim3(1), dim3(kLossReduceBlock), 0, s, partials, (int)(grid.x * grid.y * grid.z),
                        sums, 1.0f / ((float)C * (float)H * (float)W), lambda_dssim);
     return check_hip(hipGetLastError(), "image_loss_forward_kernel");
 }

@@ -148,6 +148,9 @@ __global__ __launch_bounds__(kMlThreads) void match_loss_pair_kernel(
         const MatchTerm t = term_of(i);
         num += t.li * t.m; den += t.m;
     }
+    // The tree and the fold of reduce.h, written out here on purpose.  This file is compiled with contraction on, and with the tree
+    // inside a helper the compiler optimises the rest of the kernel differently (it no longer unswitches the loops over the matches
+    // beyond 2 x 1024) and fuses other products of match_term: the loss of a 777-match pair moved by one ulp on the MI355X.
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { num += __shfl_down(num, off, kWave); den += __shfl_down(den, off, kWave); }
     if (lane_id() == 0) { s_num[wave_id()] = num; s_den[wave_id()] = den; }
