@@ -126,6 +126,16 @@ SCG_API int scg_viz_frame(const float* render, const float* depth, const float* 
                           const uint8_t* lut, int32_t H, int32_t W, uint8_t* depth_color_u8, uint8_t* depth_color_bgr_u8,
                           uint8_t* depth_u8, uint8_t* render_u8, uint8_t* frame_bgr_u8, void* stream);
 
+/* ---- Scene setup (csrc/mono.hip): GaussianModel.create_from_mono in three launches ------------------------------------------
+ * Documented in scg_mono.h, the header to include for them and for the ScgMono struct.  The prototypes are repeated here for the same
+ * reason as the evaluation's above; mono.hip includes both headers. */
+struct ScgMono;
+SCG_API size_t scg_mono_struct_bytes(int32_t which);
+SCG_API int32_t scg_mono_block(void);
+SCG_API int scg_mono_images(const struct ScgMono* a, void* stream);
+SCG_API int scg_mono_matches(const struct ScgMono* a, void* stream);
+SCG_API int scg_mono_pairs(const struct ScgMono* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

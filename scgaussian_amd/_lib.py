@@ -110,6 +110,33 @@ class ScgSeedScatter(C.Structure):
                                   "max_radii2D")]
 
 
+MONO_MAX_VIEWS, MONO_MAX_SEGMENTS = 1024, 65536
+
+
+class ScgMonoView(C.Structure):
+    """One view of the scene setup's device table (include/scg_mono.h ScgMonoView)."""
+    _fields_ = [("image_off", C.c_int64), ("mask_off", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("near_z", C.c_float),
+                ("far_z", C.c_float), ("Kinv", C.c_double * 9), ("Rc2w", C.c_double * 9), ("Rw2c", C.c_double * 9),
+                ("origin", C.c_double * 3)]
+
+
+class ScgMonoSegment(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("offset", "count", "view", "partner")]
+
+
+class ScgMonoGroup(C.Structure):
+    _fields_ = [("segment", C.c_int32), ("first", C.c_int32)]
+
+
+class ScgMono(C.Structure):
+    """Everything the three scg_mono_* calls take (include/scg_mono.h ScgMono)."""
+    _fields_ = [(n, C.c_int32) for n in ("struct_bytes", "V", "nseg", "ngroups", "N", "reserved")] + [
+        (n, C.c_int64) for n in ("image_pixels", "mask_pixels", "max_view_pixels")] + [
+        (n, C.c_void_p) for n in ("views", "segments", "groups", "image_bytes", "masks", "match_pixel", "u", "image_color", "uv",
+                                  "color", "blender_mask", "rays_o", "rays_d", "cam_rays_d", "cam_z", "z", "uv_t", "valid", "wgt",
+                                  "counts")]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/scg_raster.h
 _P = C.c_void_p
 SYMBOLS = {
@@ -153,6 +180,11 @@ SYMBOLS = {
     "scg_viz_select_scratch_bytes": (C.c_size_t, [C.c_int64]),
     "scg_viz_select": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P, _P, _P, C.c_size_t, _P]),
     "scg_viz_frame": (C.c_int, [_P] * 6 + [C.c_int32, C.c_int32] + [_P] * 5 + [_P]),
+    "scg_mono_struct_bytes": (C.c_size_t, [C.c_int32]),
+    "scg_mono_block": (C.c_int32, []),
+    "scg_mono_images": (C.c_int, [C.POINTER(ScgMono), _P]),
+    "scg_mono_matches": (C.c_int, [C.POINTER(ScgMono), _P]),
+    "scg_mono_pairs": (C.c_int, [C.POINTER(ScgMono), _P]),
     "scg_match_loss_pair": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 9 + [C.c_int32, C.c_float, C.c_float, _P, _P, _P]),
     "scg_init_stage_partials_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "scg_init_stage_run": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 4 + [_P] * 5 + [C.c_int32, C.c_int32] + [C.c_double] * 4
@@ -215,6 +247,10 @@ def open_library(path: str) -> C.CDLL:
                                     ScgInitSegment, ScgDensifyScatter)):
         if lib.scg_struct_bytes(which) != C.sizeof(struct):
             raise ScgError(f"struct layout mismatch: {struct.__name__} is {lib.scg_struct_bytes(which)} bytes in the library, "
+                           f"{C.sizeof(struct)} in the binding")
+    for which, struct in enumerate((ScgMono, ScgMonoView, ScgMonoSegment, ScgMonoGroup)):
+        if lib.scg_mono_struct_bytes(which) != C.sizeof(struct):
+            raise ScgError(f"struct layout mismatch: {struct.__name__} is {lib.scg_mono_struct_bytes(which)} bytes in the library, "
                            f"{C.sizeof(struct)} in the binding")
     return lib
 

@@ -6,7 +6,8 @@ hipcc cross-compiles without a GPU.  The .so is git-ignored but travels to the G
 gpurun snapshot.  geometry.hip is compiled with -ffp-contract=off (bit-exact tile assignment).
 optim.hip and initstage.hip are too: Adam rounded where torch rounds it.  So are densify.hip (the clone's xyz, the / 1.6) and
 seed.hip (the seeded points) and evalview.hip (the evaluation's masked images and error map) and geocheck.hip (fp64 as numpy rounds
-it) and depthviz.hip (the percentile's interpolation and the colour index as numpy and matplotlib round them).  The 8-bit quantiser
+it) and depthviz.hip (the percentile's interpolation and the colour index as numpy and matplotlib round them) and mono.hip (the
+scene setup's sampler in fp32 and its ray chain in fp64, operation by operation).  The 8-bit quantiser
 those two share (csrc/pixel_rules.h) turns contraction off in its own body and does not depend on the flag.
 """
 from __future__ import annotations
@@ -46,9 +47,10 @@ SOURCES = {
     "densify.hip": ["-ffp-contract=off"],         # clone xyz = rayo + rayd * zval and the / 1.6 rounded as torch rounds them
     "seed.hip": ["-ffp-contract=off"],            # create_from_pcd: points = rays_o + rays_d * z as torch's two operators round it
     "geocheck.hip": ["-ffp-contract=off"],        # cross-view depth check (scg_geocheck.h): numpy's float64 products and sums, none fused
+    "mono.hip": ["-ffp-contract=off"],            # create_from_mono (scg_mono.h): torch's grid_sample in fp32 and the ray chain in fp64, none fused
     "depthviz.hip": ["-ffp-contract=off"],        # depth colour maps and video frames (scg_viz.h): numpy's percentile, matplotlib's Normalize
 }
-HEADERS = [os.path.join(CSRC, "scg_common.h"), os.path.join(CSRC, "tile_sort.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "scg_debug.h"), os.path.join(CSRC, "adam_math.h"), os.path.join(CSRC, "compact.h"), os.path.join(CSRC, "reduce.h"), os.path.join(CSRC, "pixel_rules.h"), os.path.join(INCLUDE, "scg_raster.h"), os.path.join(INCLUDE, "scg_knn.h"), os.path.join(INCLUDE, "scg_loss.h"), os.path.join(INCLUDE, "scg_matchloss.h"), os.path.join(INCLUDE, "scg_eval.h"), os.path.join(INCLUDE, "scg_geocheck.h"), os.path.join(INCLUDE, "scg_viz.h")]
+HEADERS = [os.path.join(CSRC, "scg_common.h"), os.path.join(CSRC, "tile_sort.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "scg_debug.h"), os.path.join(CSRC, "adam_math.h"), os.path.join(CSRC, "compact.h"), os.path.join(CSRC, "reduce.h"), os.path.join(CSRC, "pixel_rules.h"), os.path.join(INCLUDE, "scg_raster.h"), os.path.join(INCLUDE, "scg_knn.h"), os.path.join(INCLUDE, "scg_loss.h"), os.path.join(INCLUDE, "scg_matchloss.h"), os.path.join(INCLUDE, "scg_eval.h"), os.path.join(INCLUDE, "scg_geocheck.h"), os.path.join(INCLUDE, "scg_viz.h"), os.path.join(INCLUDE, "scg_mono.h")]
 
 
 def _hipcc() -> str:

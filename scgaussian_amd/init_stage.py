@@ -93,6 +93,14 @@ class InitStage:
         cat = lambda ts: torch.cat([t.to(dev) for t in ts]).contiguous()           # noqa: E731
         return cls(segments, table, cat(rays_o), cat(rays_d), cat(uv_t), cat(wgt), cat(z), empty, lr, loss_scale, record_losses)
 
+    @classmethod
+    def from_mono(cls, setup, lr: float = 0.5, loss_scale: float = 5.0, record_losses: bool = True) -> "InitStage":
+        """The stage over the arena of a mono.MonoSetup, read in place: rays_o, rays_d, uv_t, wgt and z are the setup's own
+        tensors (z is what its view_gs holds as z_val), the segment records were formed from the host constants and uploaded with
+        the setup's inputs.  One host read: the pairs' counts, for empty_pairs."""
+        return cls(list(setup.segments), setup.init_table, setup.rays_o, setup.rays_d, setup.uv_t, setup.wgt, setup.z,
+                   setup.empty_pairs(), lr, loss_scale, record_losses)
+
     @property
     def N(self) -> int:
         return self.z.numel()

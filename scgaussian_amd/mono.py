@@ -1,0 +1,341 @@
+"""GaussianModel.create_from_mono on the GPU (csrc/mono.hip): the scene's `view_gs` dictionary built in one upload and three launches.
+
+The reference (scene/gaussian_model.py:284-360, called from Scene.__init__) loops over the ordered view pairs in Python: per pair
+two grid_sample calls, batched 3x3 products, three inverse() calls that synchronise, a handful of small uploads.  InitStage and
+SeedInputs then walk the dictionary again and concatenate it.  Here everything a view pair holds lies in ONE arena, in the order
+`_arena.walk` defines (which is the order the reference's loop walks), and the dictionary's entries are views into it:
+
+    from scgaussian_amd import mono, seed
+    from scgaussian_amd.init_stage import InitStage
+    mono.install(gaussians)                                    # gaussians.create_from_mono now runs here (scene/__init__.py:98)
+    gaussians.create_from_mono(cams, match_data, spatial_lr_scale)
+    stage = InitStage.from_mono(gaussians.mono_setup)          # the arena read in place: one host read (the pairs' counts)
+    inputs = seed.SeedInputs.from_mono(gaussians.mono_setup, stage)
+
+Host side (fp64, `view_constants`): per view the reference's fp32 intr and w2c, and the fp64 inverses of THOSE fp32 matrices, by
+adjugate over determinant.  Device side: include/scg_mono.h states the arithmetic.  The initial depths use the reference's own
+random numbers: its `torch.rand(M, 1)` carries no device, so it draws from the CPU generator, one call per ordered pair; so does
+`MonoSetup.build(u=None)`, in the same order, and under torch.manual_seed(s) the depths are the reference's bit for bit.
+
+There is no CPU path for the kernels: `MonoPlan` (walk, layout, tables, staging) runs anywhere, `MonoSetup.build` raises ScgError
+on anything but the GPU.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+import math
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .init_stage import _SEG_DTYPE as _INIT_DTYPE
+from .seed import _SEG_DTYPE as _SEED_DTYPE
+
+_VIEW_DTYPE = np.dtype([("image_off", "<i8"), ("mask_off", "<i8"), ("H", "<i4"), ("W", "<i4"), ("near_z", "<f4"), ("far_z", "<f4"),
+                        ("Kinv", "<f8", (9,)), ("Rc2w", "<f8", (9,)), ("Rw2c", "<f8", (9,)), ("origin", "<f8", (3,))])
+_SEGMENT_DTYPE = np.dtype([("offset", "<i4"), ("count", "<i4"), ("view", "<i4"), ("partner", "<i4")])
+_GROUP_DTYPE = np.dtype([("segment", "<i4"), ("first", "<i4")])
+assert _VIEW_DTYPE.itemsize == C.sizeof(_lib.ScgMonoView) and _SEGMENT_DTYPE.itemsize == C.sizeof(_lib.ScgMonoSegment)
+assert _GROUP_DTYPE.itemsize == C.sizeof(_lib.ScgMonoGroup)
+_ALIGN = 256
+_WHAT = "mono: the scene setup"
+PER_PAIR = ("z_val", "rays_o", "rays_d", "cam_rays_d", "color", "uv", "match_pixel", "blender_mask")
+PER_VIEW = ("image_color", "intr", "w2c", "height", "width", "match_infos", "near_far")
+
+
+def _err(msg: str):
+    return _lib.ScgError("mono: " + msg)
+
+
+def fov2focal(fov: float, pixels: int) -> float:
+    """utils/graphics_utils.py fov2focal."""
+    return pixels / (2 * math.tan(fov / 2))
+
+
+def inv3(a: np.ndarray) -> np.ndarray:
+    """The fp64 inverse of a 3x3 matrix: adjugate over determinant, nothing assumed of the matrix."""
+    a = np.asarray(a, dtype=np.float64).reshape(9)
+    c00, c01, c02 = a[4] * a[8] - a[5] * a[7], a[5] * a[6] - a[3] * a[8], a[3] * a[7] - a[4] * a[6]
+    det = a[0] * c00 + a[1] * c01 + a[2] * c02
+    adj = np.array([c00, a[2] * a[7] - a[1] * a[8], a[1] * a[5] - a[2] * a[4],
+                    c01, a[0] * a[8] - a[2] * a[6], a[2] * a[3] - a[0] * a[5],
+                    c02, a[1] * a[6] - a[0] * a[7], a[0] * a[4] - a[1] * a[3]])
+    with np.errstate(all="ignore"):
+        return (adj / det).reshape(3, 3)
+
+
+def view_constants(cam) -> Dict:
+    """What the kernels need of one camera, formed on the host in fp64.  intr32 (3,3) and w2c32 (4,4): the reference's fp32
+    matrices ([[fx, 0, W/2], [0, fy, H/2], [0, 0, 1]] with fx = fov2focal(FovX, W); [R^T | T]).  Kinv (3,3), c2w (4,4): the fp64
+    inverses of those fp32 matrices; Rw2c: the fp64 copy of w2c32's rotation."""
+    image = np.asarray(cam.image)
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise _err(f"view {cam.image_name}: the image has shape {image.shape}, not (H, W, 3)")
+    H, W = int(image.shape[0]), int(image.shape[1])
+    fx, fy = fov2focal(cam.FovX, W), fov2focal(cam.FovY, H)
+    intr32 = np.array([[fx, 0, W / 2.0], [0, fy, H / 2.0], [0, 0, 1]], dtype=np.float64).astype(np.float32)
+    w2c32 = np.zeros((4, 4), dtype=np.float32)
+    w2c32[:3, :3] = np.asarray(cam.R, dtype=np.float64).astype(np.float32).T
+    w2c32[:3, 3] = np.asarray(cam.T, dtype=np.float64).astype(np.float32)
+    w2c32[3, 3] = 1.0
+    Rw2c = w2c32[:3, :3].astype(np.float64)
+    Rc2w = inv3(Rw2c)
+    T = w2c32[:3, 3].astype(np.float64)
+    c2w = np.zeros((4, 4))
+    c2w[:3, :3] = Rc2w
+    c2w[:3, 3] = [-(Rc2w[r, 0] * T[0] + Rc2w[r, 1] * T[1] + Rc2w[r, 2] * T[2]) for r in range(3)]     # the last row is (0, 0, 0, 1)
+    c2w[3, 3] = 1.0
+    return {"H": H, "W": W, "intr32": intr32, "w2c32": w2c32, "Kinv": inv3(intr32), "c2w": c2w, "Rw2c": Rw2c}
+
+
+class MonoPlan:
+    """The host half of a setup: the walk of the pairs, the arena's layout, the tables and the staged inputs.  Needs no GPU.
+
+    keys: the views' names in cams order.  segments: [(a, b, offset, M)] in arena order.  regions: name -> (byte offset, shape,
+    torch dtype) in the arena; the regions before `staged_bytes` are the upload, the rest the kernels write."""
+
+    STAGED = (("tab_views", torch.uint8), ("tab_segments", torch.uint8), ("tab_groups", torch.uint8), ("init_table", torch.uint8),
+              ("seed_table", torch.uint8), ("intr", torch.float32), ("w2c", torch.float32), ("near_far", torch.float32),
+              ("match_pixel", torch.float32), ("u", torch.float32), ("masks", torch.float32), ("image_bytes", torch.uint8))
+    OUTPUTS = (("image_color", 3), ("uv", 2), ("color", 3), ("blender_mask", 0), ("rays_o", 3), ("rays_d", 3), ("cam_rays_d", 3),
+               ("cam_z", 0), ("z", 0), ("uv_t", 2), ("valid", 0), ("wgt", 0))
+
+    def __init__(self, cams: Sequence, match_data: Dict, u=None, block: Optional[int] = None):
+        if block is None:
+            block = _lib.load().scg_mono_block()
+        cams = list(cams)
+        if not cams:
+            raise _err("no camera")
+        if len(cams) > _lib.MONO_MAX_VIEWS:
+            raise _err(f"{len(cams)} views are more than the kernels take ({_lib.MONO_MAX_VIEWS})")
+        self.keys = [c.image_name for c in cams]
+        if len(set(self.keys)) != len(self.keys):
+            raise _err("two cameras share an image name")
+        self.consts = [view_constants(c) for c in cams]
+        V = len(cams)
+
+        # ---- the walk: for ci, for cj != ci (scene/gaussian_model.py:291, :314) ----------------------------------------------
+        self.segments: List[Tuple[object, object, int, int]] = []
+        index, pixels, off = {}, [], 0
+        for i, a in enumerate(self.keys):
+            for j, b in enumerate(self.keys):
+                if i == j:
+                    continue
+                m = np.asarray(match_data[a][b], dtype=np.float64)
+                if m.ndim != 2 or m.shape[1] != 2:
+                    raise _err(f"match_data[{a!r}][{b!r}] has shape {m.shape}, not (M, 2)")
+                index[(i, j)] = len(self.segments)
+                self.segments.append((a, b, off, m.shape[0]))
+                pixels.append(m.astype(np.float32))                  # torch.tensor(...).type_as(image): one rounding to fp32
+                off += m.shape[0]
+        N, nseg = off, len(self.segments)
+        if nseg == 0 or N == 0:
+            raise _err("the cameras hold no match pair")
+        if nseg > _lib.MONO_MAX_SEGMENTS or N >= 2 ** 31:
+            raise _err(f"{nseg} ordered pairs / {N} matches are more than the kernels take")
+        seg = np.zeros(nseg, dtype=_SEGMENT_DTYPE)
+        for (i, j), s in index.items():
+            t = index[(j, i)]
+            if self.segments[s][3] != self.segments[t][3]:
+                raise _err(f"pair ({self.keys[i]}, {self.keys[j]}) holds {self.segments[s][3]} matches, its reverse {self.segments[t][3]}")
+            seg[s] = (self.segments[s][2], self.segments[s][3], i, t)
+        groups = [(s, f) for s in range(nseg) for f in range(0, int(seg["count"][s]), block)]
+        if not groups or len(groups) >= 2 ** 24:
+            raise _err(f"{len(groups)} workgroups are outside what one launch takes")
+        self.N, self.V, self.nseg, self.ngroups, self.block = N, V, nseg, len(groups), block
+        self.seg_view = [int(v) for v in seg["view"]]
+
+        # ---- the uniform numbers of the initial depths (:339: torch.rand without a device, one call per ordered pair) ----------
+        if u is None:
+            u_flat = np.concatenate([torch.rand(M, 1).numpy().reshape(M) for _a, _b, _off, M in self.segments])
+        else:
+            u_flat = np.asarray(u.detach().cpu() if torch.is_tensor(u) else u, dtype=np.float32).reshape(-1)
+            if u_flat.size != N:
+                raise _err(f"u holds {u_flat.size} numbers, the pairs {N} matches")
+
+        # ---- per view: image bytes, mask, records ----------------------------------------------------------------------------
+        views = np.zeros(V, dtype=_VIEW_DTYPE)
+        images, masks, img_off, mask_off = [], [], 0, 0
+        self.near_far = np.zeros((V, 2), dtype=np.float32)
+        for i, (cam, c) in enumerate(zip(cams, self.consts)):
+            img = np.asarray(cam.image)
+            if img.dtype != np.uint8:
+                raise _err(f"view {cam.image_name}: the image is {img.dtype}, not uint8")
+            H, W = c["H"], c["W"]
+            if H * W >= 2 ** 31:
+                raise _err(f"view {cam.image_name}: {W} x {H} pixels are more than the kernels take")
+            images.append(np.ascontiguousarray(img).reshape(-1))
+            self.near_far[i] = np.asarray(cam.near_far, dtype=np.float64).astype(np.float32).reshape(2)
+            rec = views[i]
+            rec["image_off"], rec["H"], rec["W"] = img_off, H, W
+            rec["near_z"], rec["far_z"] = self.near_far[i]
+            rec["Kinv"], rec["Rc2w"], rec["Rw2c"] = c["Kinv"].reshape(9), c["c2w"][:3, :3].reshape(9), c["Rw2c"].reshape(9)
+            rec["origin"] = c["c2w"][:3, 3]
+            if getattr(cam, "blendermask", None) is not None:
+                bm = np.asarray(cam.blendermask, dtype=np.float64).astype(np.float32)
+                if bm.shape != (H, W):
+                    raise _err(f"view {cam.image_name}: the mask has shape {bm.shape}, the image ({H}, {W})")
+                masks.append(bm.reshape(-1))
+                rec["mask_off"] = mask_off
+                mask_off += H * W
+            else:
+                rec["mask_off"] = -1
+            img_off += H * W
+        self.image_pixels, self.mask_pixels = img_off, mask_off
+        self.max_view_pixels = max(c["H"] * c["W"] for c in self.consts)
+
+        # ---- the consumers' tables, from the host constants (init_stage.py, seed.py) -------------------------------------------
+        init = np.zeros(nseg, dtype=_INIT_DTYPE)
+        seed = np.zeros(nseg, dtype=_SEED_DTYPE)
+        for s, (a, b, o, M) in enumerate(self.segments):
+            i, j = self.keys.index(a), self.keys.index(b)
+            first = self.consts[min(i, j)]                           # the reference normalises by the earlier view's size
+            init[s]["offset"], init[s]["count"] = o, M
+            init[s]["width"], init[s]["height"] = float(first["W"]), float(first["H"])
+            init[s]["intr"] = self.consts[j]["intr32"].reshape(9)
+            init[s]["w2c"] = self.consts[j]["w2c32"][:3].reshape(12)
+            seed[s] = (o, M, i)
+        self.seed_table_host = seed
+
+        # ---- layout and staging ----------------------------------------------------------------------------------------------
+        staged = {"tab_views": views, "tab_segments": seg, "tab_groups": np.array(groups, dtype=np.int32).view(_GROUP_DTYPE).reshape(-1),
+                  "init_table": init, "seed_table": seed,
+                  "intr": np.stack([c["intr32"] for c in self.consts]), "w2c": np.stack([c["w2c32"] for c in self.consts]),
+                  "near_far": self.near_far, "match_pixel": np.concatenate(pixels), "u": u_flat.astype(np.float32),
+                  "masks": np.concatenate(masks) if masks else np.zeros(0, dtype=np.float32), "image_bytes": np.concatenate(images)}
+        self.regions: Dict[str, Tuple[int, Tuple[int, ...], torch.dtype]] = {}
+        pos = 0
+
+        def place(name, nbytes, shape, dtype):
+            nonlocal pos
+            self.regions[name] = (pos, shape, dtype)
+            pos = (pos + nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
+
+        for name, dtype in self.STAGED:
+            arr = staged[name]
+            raw = arr.view(np.uint8).reshape(-1) if arr.size else np.zeros(0, dtype=np.uint8)
+            shape = (raw.size,) if dtype == torch.uint8 else tuple(arr.shape)
+            place(name, raw.size, shape, dtype)
+            staged[name] = raw
+        self.staged_bytes = pos
+        for name, tail in self.OUTPUTS:
+            rows = self.image_pixels if name == "image_color" else N
+            place(name, rows * max(tail, 1) * 4, (rows, tail) if tail else (rows,), torch.float32)
+        place("counts", nseg * 4, (nseg,), torch.int32)
+        self.total_bytes = pos
+        self._staged = staged
+
+    def fill(self, host: torch.Tensor) -> None:
+        """Write the staged inputs into `host`, a uint8 CPU tensor of at least staged_bytes bytes."""
+        buf = host.numpy()
+        for name, _dtype in self.STAGED:
+            raw = self._staged[name]
+            off = self.regions[name][0]
+            buf[off:off + raw.size] = raw
+
+    def carve(self, arena: torch.Tensor, name: str) -> torch.Tensor:
+        """The region `name` of a uint8 arena of total_bytes bytes, as a tensor of its dtype and shape: a view, no copy."""
+        off, shape, dtype = self.regions[name]
+        nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+        return arena[off:off + nbytes].view(dtype).view(shape)
+
+    def view_gs(self, arena: torch.Tensor) -> Dict:
+        """The reference's nested dictionary over `arena`: every tensor a view into it."""
+        t = {name: self.carve(arena, name) for name in self.regions}
+        out: Dict = {}
+        for i, (k, c) in enumerate(zip(self.keys, self.consts)):
+            H, W = c["H"], c["W"]
+            p0 = int(self._view_pixel_off(i))
+            out[k] = {"image_color": t["image_color"][p0:p0 + H * W].view(H, W, 3), "intr": t["intr"][i], "w2c": t["w2c"][i],
+                      "height": H, "width": W, "match_infos": {}, "near_far": t["near_far"][i]}
+        for a, b, off, M in self.segments:
+            out[a]["match_infos"][b] = {
+                "z_val": torch.nn.Parameter(t["z"][off:off + M].view(M, 1), requires_grad=True),
+                "rays_o": t["rays_o"][off:off + M], "rays_d": t["rays_d"][off:off + M], "cam_rays_d": t["cam_rays_d"][off:off + M],
+                "color": t["color"][off:off + M], "uv": t["uv"][off:off + M], "match_pixel": t["match_pixel"][off:off + M],
+                "blender_mask": t["blender_mask"][off:off + M]}
+        return out
+
+    def _view_pixel_off(self, i: int) -> int:
+        return sum(c["H"] * c["W"] for c in self.consts[:i])
+
+
+class MonoSetup:
+    """The arena of a scene on the GPU and the dictionary over it.  plan: the MonoPlan; arena: one uint8 device tensor; every other
+    tensor here (uv, color, blender_mask, rays_o, rays_d, cam_rays_d, cam_z, z, uv_t, valid, wgt, counts, image_color, ...) is a
+    view into it.  view_gs: the reference's dictionary."""
+
+    def __init__(self, plan: MonoPlan, arena: torch.Tensor, host: Optional[torch.Tensor] = None):
+        self.plan, self.arena, self._host = plan, arena, host       # the pinned staging buffer lives as long as the setup
+        for name in plan.regions:
+            setattr(self, name, plan.carve(arena, name))
+        a = _lib.ScgMono()
+        a.struct_bytes = C.sizeof(_lib.ScgMono)
+        a.V, a.nseg, a.ngroups, a.N = plan.V, plan.nseg, plan.ngroups, plan.N
+        a.image_pixels, a.mask_pixels, a.max_view_pixels = plan.image_pixels, plan.mask_pixels, plan.max_view_pixels
+        for name in ("views", "segments", "groups"):
+            setattr(a, name, getattr(self, "tab_" + name).data_ptr())
+        for name in ("image_bytes", "match_pixel", "u", "image_color", "uv", "color", "blender_mask",
+                     "rays_o", "rays_d", "cam_rays_d", "cam_z", "z", "uv_t", "valid", "wgt", "counts"):
+            setattr(a, name, getattr(self, name).data_ptr())
+        a.masks = self.masks.data_ptr() if plan.mask_pixels else None
+        self.args = a
+        self.view_gs = plan.view_gs(arena)
+
+    @property
+    def segments(self):
+        return self.plan.segments
+
+    @property
+    def keys(self):
+        return self.plan.keys
+
+    @classmethod
+    def build(cls, cams: Sequence, match_data: Dict, device="cuda", u=None) -> "MonoSetup":
+        """Walk, stage, ONE upload, three launches.  No host read.  u: the (N) uniform numbers of the initial depths in arena
+        order; None draws torch.rand(M, 1) per ordered pair from the CPU generator, as the reference does."""
+        dev = torch.device(device)
+        _lib.stream_of(dev, _WHAT)
+        plan = MonoPlan(cams, match_data, u)
+        with torch.cuda.device(dev):
+            host = torch.empty(plan.staged_bytes, dtype=torch.uint8, pin_memory=True)
+            plan.fill(host)
+            arena = torch.empty(plan.total_bytes, dtype=torch.uint8, device=dev)
+            arena[:plan.staged_bytes].copy_(host, non_blocking=True)
+            setup = cls(plan, arena, host)
+            setup.launch()
+        return setup
+
+    def launch(self) -> None:
+        """The three launches on the arena's current stream: everything behind the staged inputs is written again."""
+        lib = _lib.load()
+        stream = _lib.stream_of(self.arena, _WHAT)
+        a = C.byref(self.args)
+        _lib.check(lib.scg_mono_images(a, stream), "scg_mono_images")
+        _lib.check(lib.scg_mono_matches(a, stream), "scg_mono_matches")
+        _lib.check(lib.scg_mono_pairs(a, stream), "scg_mono_pairs")
+
+    def empty_pairs(self) -> List[Tuple[object, object]]:
+        """The ordered pairs without a valid match: the one host read of the setup (the per-segment counts)."""
+        counts = self.counts.cpu()
+        return [(a, b) for (a, b, _off, _M), n in zip(self.plan.segments, counts.tolist()) if n == 0]
+
+
+@torch.no_grad()
+def create_from_mono(gaussians, cams, match_data, spatial_lr_scale, *, device="cuda", u=None) -> None:
+    """The reference's GaussianModel.create_from_mono on `gaussians`, any object: sets spatial_lr_scale, match_data and view_gs,
+    and keeps the MonoSetup as `mono_setup`."""
+    gaussians.spatial_lr_scale = spatial_lr_scale
+    gaussians.match_data = match_data
+    setup = MonoSetup.build(cams, match_data, device, u)
+    gaussians.mono_setup = setup
+    gaussians.view_gs = setup.view_gs
+
+
+def install(gaussians, device="cuda") -> None:
+    """Bind create_from_mono as a method of this model instance under the reference's name, so that scene/__init__.py:98 and
+    :171 run unchanged."""
+    gaussians.create_from_mono = functools.partial(create_from_mono, gaussians, device=device)

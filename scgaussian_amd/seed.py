@@ -125,6 +125,25 @@ class SeedInputs:
         return cls(segments, rec, table_dev, [view_gs[k] for k in keys], H, W, color, uv, cam_z, rays_o, rays_d, z, min_loss, stage)
 
     @classmethod
+    def from_mono(cls, setup, stage=None) -> "SeedInputs":
+        """The inputs over the arena of a mono.MonoSetup, read in place: color, uv and cam_z are the setup's own tensors, rays_o,
+        rays_d, z and min_loss the stage's (InitStage.from_mono(setup)) or, without one, the setup's.  No copy, no host read."""
+        plan = setup.plan
+        sizes = {(c["H"], c["W"]) for c in plan.consts}
+        if len(sizes) != 1:
+            raise _err(f"the views have unequal sizes {sorted(sizes)}: sparse_depths and img_colors cannot be stacked")
+        (H, W), = sizes
+        segments = list(setup.segments)
+        if len(segments) > _lib.SEED_MAX_SEGMENTS:
+            raise _err(f"{len(segments)} ordered view pairs are more than the kernels take ({_lib.SEED_MAX_SEGMENTS})")
+        if stage is not None and (list(stage.segments) != segments or stage.z.data_ptr() != setup.z.data_ptr()):
+            raise _err("the init stage was packed from another setup (its segments or its arena differ)")
+        _lib.stream_of(setup.z, _WHAT)
+        rays_o, rays_d, z = (stage.rays_o, stage.rays_d, stage.z) if stage is not None else (setup.rays_o, setup.rays_d, setup.z)
+        return cls(segments, plan.seed_table_host, setup.seed_table, [setup.view_gs[k] for k in setup.keys], H, W, setup.color,
+                   setup.uv, setup.cam_z, rays_o, rays_d, z, stage.min_loss if stage is not None else None, stage)
+
+    @classmethod
     def from_flat(cls, rays_o, rays_d, z, color, uv, cam_z, counts, seg_view, V: int, H: int, W: int, views=None) -> "SeedInputs":
         """Inputs that already lie flat in arena order: counts[s] matches of source view seg_view[s] per segment.  The tensors
         are used as they are (seed_arrays validates them).  views: V per-view dicts for create_from_pcd's stacks."""
