@@ -93,48 +93,9 @@ SCG_API size_t scg_eval_metrics_scratch_bytes(int32_t C, int32_t H, int32_t W);
 SCG_API int scg_eval_metrics(const float* img, const float* gt, const float* mask, int32_t C, int32_t H, int32_t W, float* out,
                              void* scratch, size_t scratch_bytes, void* stream);
 
-/* ---- Test-set evaluation (csrc/evalview.hip): render.py's render_set and metrics.py's evaluate, per view --------------------
- * Documented in scg_eval.h, the header to include for them; its 11x11 SSIM is scg_image_loss_forward above.  The prototypes are
- * repeated here because this header is one of the four from which the library's export table is checked; evalview.hip includes
- * both headers, so the compiler holds the two sets of declarations equal. */
-SCG_API size_t scg_eval_depth_range_scratch_bytes(int64_t n);
-SCG_API int scg_eval_depth_range(const float* depth, int64_t n, float* range, void* scratch, size_t scratch_bytes, void* stream);
-SCG_API int32_t scg_eval_view_tile(int32_t axis);
-SCG_API int scg_eval_view(const float* render, const float* gt, const float* depth, const float* dtumask, const float* range,
-                          int32_t H, int32_t W, uint8_t* render_u8, uint8_t* gt_u8, uint8_t* depth_u8, uint8_t* error_u8,
-                          uint8_t* mask_u8, float* error_f32, float* render_masked, float* gt_masked, uint64_t* sk, void* stream);
-
-/* ---- Cross-view depth consistency (csrc/geocheck.hip): utils/geo_check.py's geocheck in two launches ------------------------
- * Documented in scg_geocheck.h, the header to include for them.  The prototypes are repeated here for the same reason as the
- * evaluation's above; geocheck.hip includes both headers. */
-SCG_API size_t scg_geocheck_workspace_bytes(int32_t N, int32_t num_src);
-SCG_API int32_t scg_geocheck_tile(int32_t axis);
-SCG_API int scg_geocheck_setup(const double* intrs, const double* exts, int32_t N, int32_t num_src, void* workspace,
-                               size_t workspace_bytes, void* stream);
-SCG_API int scg_geocheck(const float* depths, int32_t N, int32_t H, int32_t W, int32_t num_src, double dist_thresh,
-                         double depth_thresh, int32_t view_thresh, const void* workspace, size_t workspace_bytes, uint8_t* votes,
-                         float* masks, float* filtered, void* stream);
-
-/* ---- Depth colour maps and video frames (csrc/depthviz.hip): `visualization` and render_video.py's loop, per frame ----------
- * Documented in scg_viz.h, the header to include for them.  The prototypes are repeated here for the same reason as the
- * evaluation's above; depthviz.hip includes both headers. */
-SCG_API int32_t scg_viz_select_block(void);
-SCG_API size_t scg_viz_select_scratch_bytes(int64_t n);
-SCG_API int scg_viz_select(const float* depth, const float* range, int64_t n, double percentile, float* stats, int32_t* nan_count,
-                           void* scratch, size_t scratch_bytes, void* stream);
-SCG_API int scg_viz_frame(const float* render, const float* depth, const float* range, const float* stats, const int32_t* nan_count,
-                          const uint8_t* lut, int32_t H, int32_t W, uint8_t* depth_color_u8, uint8_t* depth_color_bgr_u8,
-                          uint8_t* depth_u8, uint8_t* render_u8, uint8_t* frame_bgr_u8, void* stream);
-
-/* ---- Scene setup (csrc/mono.hip): GaussianModel.create_from_mono in three launches ------------------------------------------
- * Documented in scg_mono.h, the header to include for them and for the ScgMono struct.  The prototypes are repeated here for the same
- * reason as the evaluation's above; mono.hip includes both headers. */
-struct ScgMono;
-SCG_API size_t scg_mono_struct_bytes(int32_t which);
-SCG_API int32_t scg_mono_block(void);
-SCG_API int scg_mono_images(const struct ScgMono* a, void* stream);
-SCG_API int scg_mono_matches(const struct ScgMono* a, void* stream);
-SCG_API int scg_mono_pairs(const struct ScgMono* a, void* stream);
+/* The evaluation (scg_eval.h), the cross-view depth check (scg_geocheck.h), the depth colour maps (scg_viz.h) and the scene setup
+ * (scg_mono.h) each have their own header, and every entry point is declared in exactly one header under include/.  The 11x11
+ * SSIM of the evaluation is scg_image_loss_forward above. */
 
 #ifdef __cplusplus
 }

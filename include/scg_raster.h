@@ -126,8 +126,8 @@ typedef struct ScgFrame {
 
 SCG_API const char* scg_last_error(void);
 SCG_API int32_t scg_abi_version(void);
-/* sizeof(ScgFrame) / sizeof(ScgWorkspaceLayout) / sizeof(ScgStageEvents) as this library was compiled: a binding that
- * declares the structs itself (ctypes, cgo, JNA) compares them with its own before the first call. */
+/* sizeof of the eight structs listed at `which`, as this library was compiled (anything else: 0): a binding that declares the
+ * structs itself (ctypes, cgo, JNA) compares them with its own before the first call.  scg_mono.h has the same for its four. */
 SCG_API size_t scg_struct_bytes(int32_t which /* 0 ScgFrame, 1 ScgWorkspaceLayout, 2 ScgStageEvents, 3 ScgModel, 4 ScgModelGrads,
                                                  5 ScgAdamSegment, 6 ScgInitSegment, 7 ScgDensifyScatter */);
 

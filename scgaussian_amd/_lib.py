@@ -1,4 +1,4 @@
-"""ctypes binding of libscg_raster.so (include/scg_raster.h).
+"""ctypes binding of libscg_raster.so (the headers under include/).
 
 The library is the product path: if it is missing or fails to load this module raises — there is no
 CPU or PyTorch fallback (the oracle under oracle/ is test infrastructure and is never imported here).
@@ -14,9 +14,16 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SCG_LIB_PATH selects an experiment variant built with `python -m scgaussian_amd.build --tag=...` (profiling only)
 LIB_PATH = os.environ.get("SCG_LIB_PATH") or os.path.join(_HERE, "libscg_raster.so")
 
+# The headers' integer #defines under their own names minus "SCG_" (include/scg_raster.h, scg_matchloss.h, scg_mono.h).
+# tests/test_abi_cpu.py holds every one of them, the enumerators below, the structs and SYMBOLS against the headers' text.
 ABI_VERSION = 10
-# The headers' option / flag enumerators under their own names minus "SCG_" (include/scg_raster.h; DEBUG_*: csrc/scg_debug.h, the
-# library's A/B bits of scg_forward's `options`).  tests/test_abi_cpu.py holds names and values against the headers' text.
+TILE, SPLAT_FLOATS, DSPLAT_FLOATS = 16, 12, 16   # pixels of a tile's edge; floats of a splat record and of a gradient record (64 bytes)
+ADAM_MAX_SEGMENTS, ADAM_FORCE_FULL = 16, 1
+INIT_STAGE_MAX_STEPS = 4096
+SEED_MAX_SEGMENTS = 1024
+MONO_MAX_VIEWS, MONO_MAX_SEGMENTS = 1024, 65536
+# The option / flag enumerators, named the same way (include/scg_raster.h; DEBUG_*: csrc/scg_debug.h, the library's A/B bits of
+# scg_forward's `options`).
 FORWARD_NO_BACKWARD_STATE, FORWARD_SKIP_RARE_SORT, FORWARD_RARE_8WAVE, FORWARD_SPLIT_LONG_LISTS = 4, 8, 16, 32
 FORWARD_ARM_PARTIAL_SUMS = 64
 DEBUG_SEPARATE_SORT, DEBUG_SEPARATE_HIST = 1, 2
@@ -63,18 +70,11 @@ class ScgModelGrads(C.Structure):
     _fields_ = [("ray", ScgModelGradSet), ("bg", ScgModelGradSet)]
 
 
-ADAM_MAX_SEGMENTS = 16
-ADAM_FORCE_FULL = 1
-
-
 class ScgAdamSegment(C.Structure):
     """One parameter tensor of an scg_adam_step launch (include/scg_raster.h ScgAdamSegment)."""
     _fields_ = [(n, C.c_void_p) for n in ("param", "grad", "exp_avg", "exp_avg_sq", "step")] + [
         ("numel", C.c_int64), ("row_len", C.c_int32), ("flags", C.c_int32),
         ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
-
-
-INIT_STAGE_MAX_STEPS = 4096
 
 
 class ScgInitSegment(C.Structure):
@@ -95,9 +95,6 @@ class ScgDensifyScatter(C.Structure):
                                   "noise")]
 
 
-SEED_MAX_SEGMENTS = 1024
-
-
 class ScgSeedSegment(C.Structure):
     """One ordered view pair of the seeding step's table (include/scg_raster.h ScgSeedSegment)."""
     _fields_ = [("offset", C.c_int32), ("count", C.c_int32), ("view", C.c_int32)]
@@ -108,9 +105,6 @@ class ScgSeedScatter(C.Structure):
         (n, C.c_void_p) for n in ("segments", "segments_dev", "rays_o", "rays_d", "z", "color", "uv")] + [("opacity", C.c_float)] + [
         (n, C.c_void_p) for n in ("zval", "rayo", "rayd", "points", "features_dc", "features_rest", "rotation", "opacity_out",
                                   "max_radii2D")]
-
-
-MONO_MAX_VIEWS, MONO_MAX_SEGMENTS = 1024, 65536
 
 
 class ScgMonoView(C.Structure):
@@ -137,7 +131,16 @@ class ScgMono(C.Structure):
                                   "counts")]
 
 
-# name -> (restype, argtypes); must list every symbol declared in include/scg_raster.h
+# The structs whose size the library reports: query function -> the classes in the order of its `which` argument.  open_library
+# compares every one; tests/test_abi_cpu.py walks the same table.
+SIZE_CHECKED = {
+    "scg_struct_bytes": (ScgFrame, ScgWorkspaceLayout, ScgStageEvents, ScgModel, ScgModelGrads, ScgAdamSegment, ScgInitSegment,
+                         ScgDensifyScatter),
+    "scg_mono_struct_bytes": (ScgMono, ScgMonoView, ScgMonoSegment, ScgMonoGroup),
+}
+
+
+# name -> (restype, argtypes): every entry point that a header under include/ declares, each declared in exactly one of them
 _P = C.c_void_p
 SYMBOLS = {
     "scg_last_error": (C.c_char_p, []),
@@ -243,15 +246,11 @@ def open_library(path: str) -> C.CDLL:
         fn.argtypes = args
     if lib.scg_abi_version() != ABI_VERSION:
         raise ScgError(f"ABI version mismatch: library {lib.scg_abi_version()} != binding {ABI_VERSION}")
-    for which, struct in enumerate((ScgFrame, ScgWorkspaceLayout, ScgStageEvents, ScgModel, ScgModelGrads, ScgAdamSegment,
-                                    ScgInitSegment, ScgDensifyScatter)):
-        if lib.scg_struct_bytes(which) != C.sizeof(struct):
-            raise ScgError(f"struct layout mismatch: {struct.__name__} is {lib.scg_struct_bytes(which)} bytes in the library, "
-                           f"{C.sizeof(struct)} in the binding")
-    for which, struct in enumerate((ScgMono, ScgMonoView, ScgMonoSegment, ScgMonoGroup)):
-        if lib.scg_mono_struct_bytes(which) != C.sizeof(struct):
-            raise ScgError(f"struct layout mismatch: {struct.__name__} is {lib.scg_mono_struct_bytes(which)} bytes in the library, "
-                           f"{C.sizeof(struct)} in the binding")
+    for query, structs in SIZE_CHECKED.items():
+        for which, struct in enumerate(structs):
+            if getattr(lib, query)(which) != C.sizeof(struct):
+                raise ScgError(f"struct layout mismatch: {struct.__name__} is {getattr(lib, query)(which)} bytes in the library, "
+                               f"{C.sizeof(struct)} in the binding")
     return lib
 
 

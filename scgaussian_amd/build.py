@@ -12,6 +12,7 @@ those two share (csrc/pixel_rules.h) turns contraction off in its own body and d
 """
 from __future__ import annotations
 
+import glob
 import hashlib
 import os
 import shutil
@@ -50,7 +51,7 @@ SOURCES = {
     "mono.hip": ["-ffp-contract=off"],            # create_from_mono (scg_mono.h): torch's grid_sample in fp32 and the ray chain in fp64, none fused
     "depthviz.hip": ["-ffp-contract=off"],        # depth colour maps and video frames (scg_viz.h): numpy's percentile, matplotlib's Normalize
 }
-HEADERS = [os.path.join(CSRC, "scg_common.h"), os.path.join(CSRC, "tile_sort.h"), os.path.join(CSRC, "tile_walk.h"), os.path.join(CSRC, "scg_debug.h"), os.path.join(CSRC, "adam_math.h"), os.path.join(CSRC, "compact.h"), os.path.join(CSRC, "reduce.h"), os.path.join(CSRC, "pixel_rules.h"), os.path.join(INCLUDE, "scg_raster.h"), os.path.join(INCLUDE, "scg_knn.h"), os.path.join(INCLUDE, "scg_loss.h"), os.path.join(INCLUDE, "scg_matchloss.h"), os.path.join(INCLUDE, "scg_eval.h"), os.path.join(INCLUDE, "scg_geocheck.h"), os.path.join(INCLUDE, "scg_viz.h"), os.path.join(INCLUDE, "scg_mono.h")]
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "*.h")))   # every object depends on all
 
 
 def _hipcc() -> str:

@@ -28,7 +28,6 @@
 #include "reduce.h"
 #include "pixel_rules.h"
 #include "../../include/scg_viz.h"
-#include "../../include/scg_loss.h"
 
 namespace scg {
 

@@ -21,7 +21,6 @@
 #include "reduce.h"
 #include "pixel_rules.h"
 #include "../../include/scg_eval.h"
-#include "../../include/scg_loss.h"
 
 namespace scg {
 

@@ -16,7 +16,6 @@
 
 #include "scg_common.h"
 #include "../../include/scg_geocheck.h"
-#include "../../include/scg_loss.h"
 
 namespace scg {
 

@@ -20,7 +20,6 @@
 #include "scg_common.h"
 #include "reduce.h"
 #include "../../include/scg_mono.h"
-#include "../../include/scg_loss.h"
 
 namespace scg {
 

@@ -19,7 +19,6 @@ There is no CPU path: launching on CPU tensors raises ScgError.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -31,9 +30,7 @@ from ._lib import check, ptr
 BETAS = (0.9, 0.999)                            # training_setup_init: torch.optim.Adam(l_init, lr=0.0, eps=1e-15)
 EPS = 1e-15
 MAX_STEPS = _lib.INIT_STAGE_MAX_STEPS
-_SEG_DTYPE = np.dtype([("offset", "<i4"), ("count", "<i4"), ("width", "<f4"), ("height", "<f4"), ("intr", "<f4", (9,)),
-                       ("w2c", "<f4", (12,))])
-assert _SEG_DTYPE.itemsize == C.sizeof(_lib.ScgInitSegment)
+_SEG_DTYPE = np.dtype(_lib.ScgInitSegment)      # the device table's record: the ctypes struct's fields, offsets and size
 _GROUP = 64                                     # elements per workgroup (one wave): the row length of the partial sums is ceil(N / 64)
 
 

@@ -34,12 +34,8 @@ from . import _lib
 from .init_stage import _SEG_DTYPE as _INIT_DTYPE
 from .seed import _SEG_DTYPE as _SEED_DTYPE
 
-_VIEW_DTYPE = np.dtype([("image_off", "<i8"), ("mask_off", "<i8"), ("H", "<i4"), ("W", "<i4"), ("near_z", "<f4"), ("far_z", "<f4"),
-                        ("Kinv", "<f8", (9,)), ("Rc2w", "<f8", (9,)), ("Rw2c", "<f8", (9,)), ("origin", "<f8", (3,))])
-_SEGMENT_DTYPE = np.dtype([("offset", "<i4"), ("count", "<i4"), ("view", "<i4"), ("partner", "<i4")])
-_GROUP_DTYPE = np.dtype([("segment", "<i4"), ("first", "<i4")])
-assert _VIEW_DTYPE.itemsize == C.sizeof(_lib.ScgMonoView) and _SEGMENT_DTYPE.itemsize == C.sizeof(_lib.ScgMonoSegment)
-assert _GROUP_DTYPE.itemsize == C.sizeof(_lib.ScgMonoGroup)
+# the three device tables' records: the ctypes structs' fields, offsets and sizes
+_VIEW_DTYPE, _SEGMENT_DTYPE, _GROUP_DTYPE = np.dtype(_lib.ScgMonoView), np.dtype(_lib.ScgMonoSegment), np.dtype(_lib.ScgMonoGroup)
 _ALIGN = 256
 _WHAT = "mono: the scene setup"
 PER_PAIR = ("z_val", "rays_o", "rays_d", "cam_rays_d", "color", "uv", "match_pixel", "blender_mask")

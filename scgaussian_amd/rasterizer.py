@@ -36,13 +36,9 @@ import torch
 import torch.nn as nn
 
 from . import _counts, _lib
-from ._lib import (BACKWARD_ACCUMULATE, BINNING_AUTO, DEBUG_SEPARATE_HIST, DEBUG_SEPARATE_SORT, FORWARD_ARM_PARTIAL_SUMS,
-                   FORWARD_NO_BACKWARD_STATE, FORWARD_RARE_8WAVE, FORWARD_SKIP_RARE_SORT, FORWARD_SPLIT_LONG_LISTS, ScgFrame, check,
-                   ptr)
-
-SPLAT_FLOATS = 12
-DSPLAT_FLOATS = 16         # gradient record of a Gaussian: one 64-byte line (scg_raster.h SCG_DSPLAT_FLOATS)
-TILE = 16
+from ._lib import (BACKWARD_ACCUMULATE, BINNING_AUTO, DEBUG_SEPARATE_HIST, DEBUG_SEPARATE_SORT, DSPLAT_FLOATS,
+                   FORWARD_ARM_PARTIAL_SUMS, FORWARD_NO_BACKWARD_STATE, FORWARD_RARE_8WAVE, FORWARD_SKIP_RARE_SORT,
+                   FORWARD_SPLIT_LONG_LISTS, SPLAT_FLOATS, TILE, ScgFrame, check, ptr)
 
 
 class GaussianRasterizationSettings(NamedTuple):

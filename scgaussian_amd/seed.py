@@ -33,9 +33,8 @@ from . import _arena, _lib
 
 THRESHOLD = 0.1                                 # create_from_pcd: min_loss_state[a][b] < 0.1
 _BG_NAMES = ("bg_xyz", "bg_features_dc", "bg_features_rest", "bg_scaling", "bg_rotation", "bg_opacity")
-_SEG_DTYPE = np.dtype([("offset", "<i4"), ("count", "<i4"), ("view", "<i4")])
+_SEG_DTYPE = np.dtype(_lib.ScgSeedSegment)      # the table's record: the ctypes struct's fields, offsets and size
 _WHAT = "seed: the seeding step"                # ... needs tensors on the GPU (_lib.stream_of)
-assert _SEG_DTYPE.itemsize == C.sizeof(_lib.ScgSeedSegment)
 
 
 def _err(msg: str):

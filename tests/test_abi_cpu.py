@@ -1,67 +1,215 @@
-"""CPU-only checks of the C-ABI boundary: the library loads, exports every symbol that
-include/scg_raster.h declares, validates arguments without touching a GPU, and the Python operator
-mirrors the reference's error behaviour.  No compute calls."""
+"""CPU-only checks of the C-ABI boundary: the library exports exactly what the headers under include/ declare, the ctypes binding
+agrees with the headers' text declaration by declaration (tests/abi_text.py reads it), the library validates arguments without
+touching a GPU, and the Python operator mirrors the reference's error behaviour.  No compute calls."""
 import ctypes as C
 import os
 import re
+import subprocess
 
 import pytest
 import torch
 
+import abi_text
 from scgaussian_amd import _lib
 from scgaussian_amd._lib import ScgFrame
 from scgaussian_amd import rasterizer as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ABI = abi_text.read()
+
+# The C scalar types of the headers and their ctypes types.  (On the LP64 targets of this library ctypes has one class for int and
+# int32_t, and one for size_t and uint64_t; int32_t against int64_t, float against double and every count or order are told apart.)
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "size_t": C.c_size_t, "float": C.c_float,
+            "double": C.c_double, "uint8_t": C.c_uint8, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "char": C.c_char}
 
 
-def _declared_symbols():
-    names = set()
-    for hdr in ("scg_raster.h", "scg_knn.h", "scg_loss.h", "scg_matchloss.h"):
-        text = open(os.path.join(ROOT, "include", hdr)).read()
-        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        names |= set(re.findall(r"\b(scg_[a-z0-9_]+)\s*\(", text))
-    return sorted(names)
+def _matches(decl, ctype, structs, returned=False):
+    """Does the ctypes type stand for the C declaration?  structs: {name: ctypes class} for the struct types a header may name."""
+    if decl.array:
+        return (issubclass(ctype, C.Array) and ctype._length_ == decl.array
+                and _matches(decl._replace(array=0), ctype._type_, structs))
+    if decl.pointer == 0:
+        return ctype is (structs[decl.base] if decl.base in structs else _SCALARS.get(decl.base, False))
+    if returned and decl.base == "char":
+        return decl.pointer == 1 and ctype is C.c_char_p
+    if ctype is C.c_void_p:                                          # any pointer
+        return True
+    if decl.pointer == 2:
+        return decl.base == "void" and ctype is C.POINTER(C.c_void_p)
+    target = structs.get(decl.base, _SCALARS.get(decl.base))
+    return target is not None and ctype is C.POINTER(target)
+
+
+def _prototype_differences(fn, restype, argtypes, structs):
+    diffs = []
+    if not _matches(fn.ret, restype, structs, returned=True):
+        diffs.append(f"{fn.name} ({fn.header}): returns {fn.ret.base}{'*' * fn.ret.pointer}, bound as {restype}")
+    if len(fn.params) != len(argtypes):
+        diffs.append(f"{fn.name} ({fn.header}): {len(fn.params)} parameters, bound with {len(argtypes)}")
+    for i, (decl, ctype) in enumerate(zip(fn.params, argtypes)):
+        if not _matches(decl, ctype, structs):
+            diffs.append(f"{fn.name} ({fn.header}): parameter {i} is {decl}, bound as {ctype}")
+    return diffs
+
+
+def _struct_differences(name, fields, cls, structs):
+    bound = list(cls._fields_)
+    if [f.name for f in fields] != [n for n, _ in bound]:
+        return [f"{name}: members {[f.name for f in fields]}, bound as {[n for n, _ in bound]}"]
+    return [f"{name}.{f.name} is {f}, bound as {t}" for f, (_, t) in zip(fields, bound) if not _matches(f, t, structs)]
+
+
+def _bound_structs(module):
+    return {k: v for k, v in vars(module).items() if isinstance(v, type) and issubclass(v, C.Structure) and v is not C.Structure}
 
 
 def test_library_exports_every_declared_symbol():
+    """The dynamic table of the library is the set of names the headers declare, each in exactly one header, and NOTHING ELSE: the
+    sources are compiled with -fvisibility=hidden (the declarations carry SCG_API) and linked with csrc/exports.map, so no internal
+    scg:: function, kernel handle or __hip_cuid_* symbol leaks, and a definition that does not see its declaration is missed here."""
+    where = abi_text.declared_in(ABI)                                # raises, naming both headers, when a name is declared twice
+    assert len(where) == 73 and len(set(where.values())) == 8
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
+    assert exported == sorted(where), {n: where.get(n, "not declared") for n in set(exported) ^ set(where)}
     lib = _lib.load()
-    declared = _declared_symbols()
-    assert len(declared) >= 12
-    for name in declared:
-        assert hasattr(lib, name), f"libscg_raster.so does not export {name}"
-        assert name in _lib.SYMBOLS, f"ctypes binding lacks {name}"
-    assert lib.scg_abi_version() == _lib.ABI_VERSION == 10
-    # ... and NOTHING ELSE: the sources are compiled with -fvisibility=hidden (the declarations carry SCG_API) and linked with
-    # csrc/exports.map, so no internal scg:: function, kernel handle or __hip_cuid_* symbol leaks into the dynamic table
-    import subprocess
-    for path in (_lib.LIB_PATH,):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        exported = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
-        assert exported == declared, sorted(set(exported) ^ set(declared))
-    # the structs the binding declares have the size the library was compiled with (ScgFrame grew in ABI 5)
-    import ctypes as C
+    for name, header in where.items():
+        assert hasattr(lib, name), f"libscg_raster.so does not export {name} ({header})"
+        assert name in _lib.SYMBOLS, f"ctypes binding lacks {name} ({header})"
+    assert lib.scg_abi_version() == _lib.ABI_VERSION == ABI.defines["SCG_ABI_VERSION"] == 10
+    # the structs the binding declares have the size the library was compiled with (all of them: the size test below)
     for which, struct in enumerate((_lib.ScgFrame, _lib.ScgWorkspaceLayout, _lib.ScgStageEvents)):
         assert lib.scg_struct_bytes(which) == C.sizeof(struct) > 0
     assert lib.scg_struct_bytes(99) == 0
 
 
+def test_every_prototype_is_bound_as_declared():
+    where = abi_text.declared_in(ABI)
+    assert sorted(_lib.SYMBOLS) == sorted(where), {n: where.get(n, "not declared") for n in set(_lib.SYMBOLS) ^ set(where)}
+    structs = _bound_structs(_lib)
+    diffs = [d for fn in ABI.functions for d in _prototype_differences(fn, *_lib.SYMBOLS[fn.name], structs)]
+    assert not diffs, "\n".join(diffs)
+
+
+def test_every_struct_is_bound_field_by_field():
+    structs = _bound_structs(_lib)
+    assert sorted(structs) == sorted(ABI.structs) and len(structs) == 17
+    diffs = [d for name, fields in ABI.structs.items() for d in _struct_differences(name, fields, structs[name], structs)]
+    assert not diffs, "\n".join(diffs)
+
+
+def test_every_size_checked_struct_has_the_librarys_size():
+    lib = _lib.load()
+    assert {q: len(s) for q, s in _lib.SIZE_CHECKED.items()} == {"scg_struct_bytes": 8, "scg_mono_struct_bytes": 4}
+    for query, structs in _lib.SIZE_CHECKED.items():
+        for which, struct in enumerate(structs):
+            assert getattr(lib, query)(which) == C.sizeof(struct) > 0, (query, which, struct.__name__)
+        assert getattr(lib, query)(len(structs)) == 0 and getattr(lib, query)(99) == 0
+
+
+def test_mirrored_constants_are_the_headers():
+    """Every integer #define SCG_<NAME> that the binding mirrors as <NAME> has the header's value; the ten it is known to mirror are
+    all there, and the rasterizer's three are the binding's."""
+    mirrored = {n[4:]: v for n, v in ABI.defines.items() if hasattr(_lib, n[4:])}
+    assert sorted(mirrored) == sorted(("ABI_VERSION", "TILE", "SPLAT_FLOATS", "DSPLAT_FLOATS", "ADAM_MAX_SEGMENTS", "ADAM_FORCE_FULL",
+                                       "INIT_STAGE_MAX_STEPS", "SEED_MAX_SEGMENTS", "MONO_MAX_VIEWS", "MONO_MAX_SEGMENTS"))
+    assert {n: getattr(_lib, n) for n in mirrored} == mirrored
+    assert (R.TILE, R.SPLAT_FLOATS, R.DSPLAT_FLOATS) == (_lib.TILE, _lib.SPLAT_FLOATS, _lib.DSPLAT_FLOATS) == (16, 12, 16)
+
+
 def test_option_and_flag_bits_of_the_binding_are_the_headers():
-    """Every SCG_FORWARD_* / SCG_BACKWARD_* / SCG_DEBUG_* / SCG_BINNING_* enumerator of include/scg_raster.h and
-    csrc/scg_debug.h has a constant of the same name (minus SCG_) and value in _lib, and _lib has none the headers lack."""
-    declared = {}
-    for hdr in (os.path.join(ROOT, "include", "scg_raster.h"), os.path.join(ROOT, "scgaussian_amd", "csrc", "scg_debug.h")):
-        text = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(hdr).read(), flags=re.S)
-        for body in re.findall(r"\benum\s*\{(.*?)\}", text, flags=re.S):
-            for name, value in re.findall(r"\bSCG_((?:FORWARD|BACKWARD|DEBUG|BINNING)_[A-Z0-9_]+)\s*=\s*(\w+)", body):
-                assert name not in declared, name
-                declared[name] = int(value, 0)
+    """Every SCG_FORWARD_* / SCG_BACKWARD_* / SCG_DEBUG_* / SCG_BINNING_* enumerator of the headers and of csrc/scg_debug.h has a
+    constant of the same name (minus SCG_) and value in _lib, and _lib has none the headers lack."""
+    kinds = r"(FORWARD|BACKWARD|DEBUG|BINNING)_[A-Z0-9_]+"
+    both = abi_text.read([os.path.join(ROOT, "scgaussian_amd", "csrc", "scg_debug.h")]).enums
+    assert not set(both) & set(ABI.enums)
+    both.update(ABI.enums)
+    declared = {k[4:]: v for k, v in both.items() if re.fullmatch("SCG_" + kinds, k)}
     assert len(declared) >= 11 and declared["FORWARD_ARM_PARTIAL_SUMS"] == 64 and declared["BINNING_AUTO"] == 0
-    bound = {k: v for k, v in vars(_lib).items() if re.fullmatch(r"(FORWARD|BACKWARD|DEBUG|BINNING)_[A-Z0-9_]+", k)}
+    bound = {k: v for k, v in vars(_lib).items() if re.fullmatch(kinds, k)}
     assert bound == declared, sorted(set(bound.items()) ^ set(declared.items()))
     # the bits of one option word do not collide: scg_forward's `options` carries the FORWARD_* and the DEBUG_* bits together
     word = [v for k, v in declared.items() if k.startswith(("FORWARD_", "DEBUG_"))]
     assert all(v > 0 and v & (v - 1) == 0 for v in word) and len(set(word)) == len(word)
+
+
+# ---- the reader and the comparison above, on short headers with one known difference each: neither passes everything ----------
+
+_TOY = """
+#ifndef SCG_TOY_H
+#define SCG_TOY_H
+#define SCG_TOY_MAX 7      /* a constant */
+extern "C" {
+typedef struct ScgToy {
+    int32_t rows, cols;    // two members of one size
+    const float* data;
+    double m[9];
+} ScgToy;
+SCG_API int scg_toy_run(const ScgToy* toy, int64_t n, float* out, void* stream);
+SCG_API size_t scg_toy_bytes(void);
+}
+#endif
+"""
+
+
+class ScgToy(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("data", C.c_void_p), ("m", C.c_double * 9)]
+
+
+_TOY_SYMBOLS = {"scg_toy_run": (C.c_int, [C.POINTER(ScgToy), C.c_int64, C.c_void_p, C.c_void_p]), "scg_toy_bytes": (C.c_size_t, [])}
+
+
+def _toy_differences(text):
+    abi = abi_text.parse(text, "toy.h")
+    structs = {"ScgToy": ScgToy}
+    assert sorted(abi_text.declared_in(abi)) == sorted(_TOY_SYMBOLS) and list(abi.structs) == ["ScgToy"]
+    return ([d for fn in abi.functions for d in _prototype_differences(fn, *_TOY_SYMBOLS[fn.name], structs)]
+            + _struct_differences("ScgToy", abi.structs["ScgToy"], ScgToy, structs))
+
+
+def test_the_toy_header_as_bound_shows_no_difference():
+    assert _toy_differences(_TOY) == []
+    abi = abi_text.parse(_TOY, "toy.h")
+    assert abi.defines == {"SCG_TOY_MAX": 7} and [f.header for f in abi.functions] == ["toy.h", "toy.h"]
+    assert abi.structs["ScgToy"] == [abi_text.Decl("rows", "int32_t", 0, 0), abi_text.Decl("cols", "int32_t", 0, 0),
+                                     abi_text.Decl("data", "float", 1, 0), abi_text.Decl("m", "double", 0, 9)]
+
+
+@pytest.mark.parametrize("what, old, new", [
+    ("two swapped members of one size", "int32_t rows, cols;", "int32_t cols, rows;"),
+    ("int64_t against int32_t", "int64_t n", "int32_t n"),
+    ("a dropped parameter", "int64_t n, float* out", "int64_t n"),
+    ("a changed array length", "double m[9]", "double m[12]"),
+    ("a pointer against a value", "const float* data", "float data"),
+    ("another return type", "SCG_API size_t scg_toy_bytes", "SCG_API int32_t scg_toy_bytes"),
+])
+def test_a_mutated_toy_header_shows_a_difference(what, old, new):
+    assert _TOY.count(old) == 1
+    assert _toy_differences(_TOY.replace(old, new)), what
+
+
+def test_a_name_declared_twice_is_named_with_both_headers():
+    one, two = abi_text.parse(_TOY, "toy.h"), abi_text.parse("SCG_API size_t scg_toy_bytes(void);", "other.h")
+    with pytest.raises(abi_text.AbiTextError, match=r"scg_toy_bytes is declared twice: in toy\.h and in other\.h"):
+        abi_text.declared_in(abi_text.Abi(one.functions + two.functions, {}, {}, {}))
+
+
+@pytest.mark.parametrize("old, new", [
+    ("SCG_API int scg_toy_run(", "SCG_API int scg_toy_run(void (*callback)(int), "),        # a function pointer
+    ("int64_t n,", "unsigned long n,"),                                                      # a two-word type
+    ("SCG_API size_t scg_toy_bytes(void);", "size_t scg_toy_bytes(void);"),                  # a prototype without SCG_API
+    ("SCG_API size_t scg_toy_bytes(void);", "struct ScgOther;"),                             # a forward declaration
+    ("double m[9];", "double m[SCG_TOY_MAX];"),                                              # a length that is not a number
+    ("double m[9];", "double m[9]; union { int a; float b; } u;"),                           # a nested block
+    ("#define SCG_TOY_MAX 7", "#define SCG_TOY_MAX (3 + 4)"),                                # a #define that is not an integer
+    ("#define SCG_TOY_MAX 7", "#define SCG_TOY_MAX 7\n#define SCG_TOY_MAX 8"),               # ... or is there twice
+    ("} ScgToy;", "} ScgToy2;"),                                                             # two names for one struct
+    ("#endif", "}\n#endif"),                                                                 # a brace too many at the end
+])
+def test_an_unreadable_declaration_raises(old, new):
+    assert _TOY.count(old) == 1
+    with pytest.raises(abi_text.AbiTextError):
+        abi_text.parse(_TOY.replace(old, new), "toy.h")
 
 
 def test_scratch_size_queries_are_monotone():

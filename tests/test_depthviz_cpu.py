@@ -5,7 +5,6 @@ What anchors what: depthviz_refs restates the rule; it is held here, bit for bit
 matplotlib's own mapper where matplotlib is installed, and to tests/golden/ref_depthviz.npz, which was recorded from both."""
 import inspect
 import os
-import re
 import types
 import warnings
 
@@ -13,10 +12,10 @@ import numpy as np
 import pytest
 import torch
 
+import abi_text
 import depthviz_refs as D
 from scgaussian_amd import _lib, evaluate, video
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("scg_viz_select_block", "scg_viz_select_scratch_bytes", "scg_viz_select", "scg_viz_frame")
 NULL, RANGE, SCRATCH, ALIGN = -1, -2, -4, -5
 f32 = np.float32
@@ -35,8 +34,7 @@ def _plane(rng, n, kind):
 
 def test_new_symbols_are_declared_exported_and_bound():
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scg_viz.h")).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(scg_[a-z0-9_]+)\s*\(", text)))
+    declared = abi_text.declared_by("scg_viz.h")
     assert declared == sorted(NEW_SYMBOLS)
     for name in declared:
         assert name in _lib.SYMBOLS, f"ctypes binding lacks {name}"

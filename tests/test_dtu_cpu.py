@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_text
 import dtu_refs as DR
 from scgaussian_amd import _lib, dtu
 
@@ -67,9 +68,8 @@ def test_metric_restatement_in_fp64_is_the_reference():
 
 def test_new_symbols_are_declared_exported_and_bound():
     lib = _lib.load()
-    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "scg_loss.h")).read()
     for name in NEW_SYMBOLS:
-        assert name + "(" in text, f"include/scg_loss.h does not declare {name}"
+        assert abi_text.header_of(name) == "scg_loss.h", f"include/scg_loss.h does not declare {name}"
         assert name in _lib.SYMBOLS, f"ctypes binding lacks {name}"
         assert hasattr(lib, name), f"libscg_raster.so does not export {name}"
     assert lib.scg_abi_version() == _lib.ABI_VERSION == 10

@@ -8,12 +8,12 @@ import io
 import json
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_text
 import eval_refs as ER
 from scgaussian_amd import _lib, evaluate
 
@@ -144,8 +144,7 @@ def test_write_results_json_shape(tmp_path):
 
 def test_new_symbols_are_declared_exported_and_bound():
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scg_eval.h")).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(scg_[a-z0-9_]+)\s*\(", text)))
+    declared = abi_text.declared_by("scg_eval.h")
     assert declared == sorted(NEW_SYMBOLS)
     for name in declared:
         assert name in _lib.SYMBOLS, f"ctypes binding lacks {name}"

@@ -3,27 +3,23 @@ validation, and the references the GPU tests lean on.  No kernel runs here.
 
 What anchors what: geocheck_refs.geocheck_ref restates the kernel's rule; it is held here to oracle/geo_check_oracle.py on every
 scene the GPU tests use (votes equal, kept depths within 1 fp32 ulp), and its pair table to the twin's and the oracle's get_pairs."""
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
+import abi_text
 import geocheck_refs as G
 from oracle import geo_check_oracle as orc
 from scgaussian_amd import _lib
 from scgaussian_amd import geo_check as gc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("scg_geocheck_workspace_bytes", "scg_geocheck_tile", "scg_geocheck_setup", "scg_geocheck")
 NULL, RANGE, SCRATCH, ALIGN = -1, -2, -4, -5
 
 
 def test_new_symbols_are_declared_exported_and_bound():
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scg_geocheck.h")).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(scg_[a-z0-9_]+)\s*\(", text)))
+    declared = abi_text.declared_by("scg_geocheck.h")
     assert declared == sorted(NEW_SYMBOLS)
     for name in declared:
         assert name in _lib.SYMBOLS, f"ctypes binding lacks {name}"

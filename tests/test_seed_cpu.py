@@ -3,17 +3,16 @@ create_from_pcd produced (tests/golden/ref_seed.npz), the new C-ABI entry points
 Python binding's refusals."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_text
 import seed_refs as S
 from scgaussian_amd import _lib, seed
 
 FX = S.fixture()
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIT_EXACT = ("zval", "rayo", "rayd", "points", "features_dc", "features_rest", "rotation", "max_radii2D", "sparse_depths", "masks")
 
 
@@ -75,10 +74,9 @@ def test_fixture_holds_the_planted_rows():
 
 def test_abi_has_the_seed_entry_points():
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scg_raster.h")).read(), flags=re.S)
     for name in ("scg_seed_workspace_bytes", "scg_seed_classify", "scg_seed_scatter", "scg_seed_finish"):
         assert hasattr(lib, name) and name in _lib.SYMBOLS, name
-        assert re.search(r"\b%s\s*\(" % name, text), f"{name} is not declared in include/scg_raster.h"
+        assert abi_text.header_of(name) == "scg_raster.h", f"{name} is not declared in include/scg_raster.h"
     assert lib.scg_abi_version() == _lib.ABI_VERSION == 10
     w = lib.scg_seed_workspace_bytes
     assert w(0, 0) == 32 + 4 and w(1, 0) == 32 + 4 + 4 and w(256, 10) == 32 + 4 + 40 + 256 and w(257, 10) == 32 + 8 + 40 + 260
