@@ -1,4 +1,4 @@
-"""Build libscg_raster.so (the C-ABI HIP library) in-tree with hipcc for gfx950.
+"""Build libscg_raster.so (the C-ABI HIP library) and libscg_io.so (scene files, IO_SOURCES) in-tree with hipcc for gfx950.
 
     python -m scgaussian_amd.build [--force] [--verbose]
 
@@ -7,7 +7,8 @@ gpurun snapshot.  geometry.hip is compiled with -ffp-contract=off (bit-exact til
 optim.hip and initstage.hip are too: Adam rounded where torch rounds it.  So are densify.hip (the clone's xyz, the / 1.6) and
 seed.hip (the seeded points) and evalview.hip (the evaluation's masked images and error map) and geocheck.hip (fp64 as numpy rounds
 it) and depthviz.hip (the percentile's interpolation and the colour index as numpy and matplotlib round them) and mono.hip (the
-scene setup's sampler in fp32 and its ray chain in fp64, operation by operation).  The 8-bit quantiser
+scene setup's sampler in fp32 and its ray chain in fp64, operation by operation) and plypack.hip of the second library (the saved
+position and the colour bytes).  The 8-bit quantiser
 those two share (csrc/pixel_rules.h) turns contraction off in its own body and does not depend on the flag.
 """
 from __future__ import annotations
@@ -24,6 +25,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 OBJ_DIR = os.path.join(CSRC, "build")
 LIB_PATH = os.path.join(HERE, "libscg_raster.so")
+IO_LIB_PATH = os.path.join(HERE, "libscg_io.so")
 EXPORTS_MAP = os.path.join(CSRC, "exports.map")           # global: scg_*; local: everything else
 
 ARCH = "gfx950"
@@ -51,7 +53,12 @@ SOURCES = {
     "mono.hip": ["-ffp-contract=off"],            # create_from_mono (scg_mono.h): torch's grid_sample in fp32 and the ray chain in fp64, none fused
     "depthviz.hip": ["-ffp-contract=off"],        # depth colour maps and video frames (scg_viz.h): numpy's percentile, matplotlib's Normalize
 }
-HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "*.h")))   # every object depends on all
+# The second library, libscg_io.so (include/io/scg_ply.h): scene files.  Its entry points are not part of libscg_raster.so's ABI.
+IO_SOURCES = {
+    "plypack.hip": ["-ffp-contract=off"],         # save_ply / load_ply: x = rayo + rayd * zval and the colour bytes, one rounding per operation
+}
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "*.h"))) + \
+    sorted(glob.glob(os.path.join(INCLUDE, "io", "*.h")))                                                 # every object depends on all
 
 
 def _hipcc() -> str:
@@ -81,9 +88,47 @@ def build_cxx_trip_variant(verbose: bool = False) -> str:
     return build(verbose=verbose, tag=CXX_TRIP_TAG, defines=("SCG_FWD_TRIP_CXX",), only=("blend.hip",))
 
 
+def _compile(hipcc: str, src: str, extra, obj: str, force: bool, verbose: bool) -> bool:
+    """Compile csrc/<src> to `obj` unless its stamp says that source, headers and flags are the ones it was built from."""
+    src_path = os.path.join(CSRC, src)
+    stamp = obj + ".sha"
+    dig = _digest([src_path] + HEADERS, " ".join(COMMON + extra))
+    if not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == dig:
+        return False
+    cmd = [hipcc] + COMMON + extra + ["-c", src_path, "-o", obj]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    with open(stamp, "w") as fh:
+        fh.write(dig)
+    return True
+
+
+def _link(hipcc: str, lib_path: str, objs, verbose: bool) -> None:
+    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-Wl,--version-script=" + EXPORTS_MAP, "-o", lib_path] + objs
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+
+
+def build_io(force: bool = False, verbose: bool = False) -> str:
+    """libscg_io.so from IO_SOURCES: the same flags, the same export map, no variants."""
+    os.makedirs(OBJ_DIR, exist_ok=True)
+    hipcc = _hipcc()
+    objs, rebuilt = [], False
+    for src, extra in IO_SOURCES.items():
+        obj = os.path.join(OBJ_DIR, src.replace(".hip", ".o"))
+        objs.append(obj)
+        rebuilt |= _compile(hipcc, src, list(extra), obj, force, verbose)
+    if rebuilt or force or not os.path.exists(IO_LIB_PATH):
+        _link(hipcc, IO_LIB_PATH, objs, verbose)
+    return IO_LIB_PATH
+
+
 def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(), flags=(), only=None) -> str:
     """tag/defines build a VARIANT libscg_raster_<tag>.so (selected at run time with SCG_LIB_PATH); the default build has
-    neither.  `only`: the sources the defines / flags apply to — the others are linked from the default build's objects."""
+    neither and builds libscg_io.so behind the main library.  `only`: the sources the defines / flags apply to — the others are
+    linked from the default build's objects."""
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
     objs = []
@@ -93,25 +138,13 @@ def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(),
         variant = bool(tag) and (only is None or src in only)
         if variant:
             extra = list(extra) + ["-D" + d for d in defines] + list(flags)
-        src_path = os.path.join(CSRC, src)
         obj = os.path.join(OBJ_DIR, src.replace(".hip", (f"_{tag}" if variant else "") + ".o"))
-        stamp = obj + ".sha"
-        dig = _digest([src_path] + HEADERS, " ".join(COMMON + extra))
         objs.append(obj)
-        if not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == dig:
-            continue
-        cmd = [hipcc] + COMMON + extra + ["-c", src_path, "-o", obj]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
-        with open(stamp, "w") as fh:
-            fh.write(dig)
-        rebuilt = True
+        rebuilt |= _compile(hipcc, src, list(extra), obj, force, verbose)
     if rebuilt or force or not os.path.exists(lib_path):
-        cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-Wl,--version-script=" + EXPORTS_MAP, "-o", lib_path] + objs
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
+        _link(hipcc, lib_path, objs, verbose)
+    if not tag:
+        build_io(force=force, verbose=verbose)
     return lib_path
 
 
