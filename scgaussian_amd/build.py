@@ -1,4 +1,5 @@
-"""Build libscg_raster.so (the C-ABI HIP library) and libscg_io.so (scene files, IO_SOURCES) in-tree with hipcc for gfx950.
+"""Build libscg_raster.so (the C-ABI HIP library), libscg_io.so (scene files, IO_SOURCES) and libscg_img.so (camera images,
+IMG_SOURCES) in-tree with hipcc for gfx950.
 
     python -m scgaussian_amd.build [--force] [--verbose]
 
@@ -26,6 +27,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 OBJ_DIR = os.path.join(CSRC, "build")
 LIB_PATH = os.path.join(HERE, "libscg_raster.so")
 IO_LIB_PATH = os.path.join(HERE, "libscg_io.so")
+IMG_LIB_PATH = os.path.join(HERE, "libscg_img.so")
 EXPORTS_MAP = os.path.join(CSRC, "exports.map")           # global: scg_*; local: everything else
 
 ARCH = "gfx950"
@@ -57,8 +59,13 @@ SOURCES = {
 IO_SOURCES = {
     "plypack.hip": ["-ffp-contract=off"],         # save_ply / load_ply: x = rayo + rayd * zval and the colour bytes, one rounding per operation
 }
+# The third library, libscg_img.so (include/img/scg_resample.h): the camera images' resize.  Integer arithmetic; its one float
+# operation (byte / 255) is an explicitly rounded division, so it needs no flag.
+IMG_SOURCES = {
+    "resample.hip": [],
+}
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "*.h"))) + \
-    sorted(glob.glob(os.path.join(INCLUDE, "io", "*.h")))                                                 # every object depends on all
+    sorted(glob.glob(os.path.join(INCLUDE, "io", "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "img", "*.h")))                                               # every object depends on all
 
 
 def _hipcc() -> str:
@@ -111,23 +118,32 @@ def _link(hipcc: str, lib_path: str, objs, verbose: bool) -> None:
     subprocess.run(cmd, check=True)
 
 
-def build_io(force: bool = False, verbose: bool = False) -> str:
-    """libscg_io.so from IO_SOURCES: the same flags, the same export map, no variants."""
+def _build_side(sources, lib_path: str, force: bool, verbose: bool) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
     objs, rebuilt = [], False
-    for src, extra in IO_SOURCES.items():
+    for src, extra in sources.items():
         obj = os.path.join(OBJ_DIR, src.replace(".hip", ".o"))
         objs.append(obj)
         rebuilt |= _compile(hipcc, src, list(extra), obj, force, verbose)
-    if rebuilt or force or not os.path.exists(IO_LIB_PATH):
-        _link(hipcc, IO_LIB_PATH, objs, verbose)
-    return IO_LIB_PATH
+    if rebuilt or force or not os.path.exists(lib_path):
+        _link(hipcc, lib_path, objs, verbose)
+    return lib_path
+
+
+def build_io(force: bool = False, verbose: bool = False) -> str:
+    """libscg_io.so from IO_SOURCES: the same flags, the same export map, no variants."""
+    return _build_side(IO_SOURCES, IO_LIB_PATH, force, verbose)
+
+
+def build_img(force: bool = False, verbose: bool = False) -> str:
+    """libscg_img.so from IMG_SOURCES, as build_io."""
+    return _build_side(IMG_SOURCES, IMG_LIB_PATH, force, verbose)
 
 
 def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(), flags=(), only=None) -> str:
     """tag/defines build a VARIANT libscg_raster_<tag>.so (selected at run time with SCG_LIB_PATH); the default build has
-    neither and builds libscg_io.so behind the main library.  `only`: the sources the defines / flags apply to — the others are
+    neither and builds libscg_io.so and libscg_img.so behind the main library.  `only`: the sources the defines / flags apply to — the others are
     linked from the default build's objects."""
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
@@ -145,6 +161,7 @@ def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(),
         _link(hipcc, lib_path, objs, verbose)
     if not tag:
         build_io(force=force, verbose=verbose)
+        build_img(force=force, verbose=verbose)
     return lib_path
 
 
