@@ -215,7 +215,11 @@ int scg_binning(const ScgFrame* frame, int64_t num_rendered, const uint32_t* rec
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const FrameDev f = make_frame_dev(frame);
     const int n_tiles = f.gx * f.gy;
-    if (num_rendered == 0 || frame->P == 0) return launch_tile_ranges(nullptr, 0, ranges, n_tiles, s);
+    if (num_rendered == 0 || frame->P == 0) {                   // (nothing is binned: the count a caller looks at later is 0)
+        if (frame->num_rendered_out)
+            if ((rc = check_hip(hipMemsetAsync(frame->num_rendered_out, 0, sizeof(uint32_t), s), "memset num_rendered_out"))) return rc;
+        return launch_tile_ranges(nullptr, 0, ranges, n_tiles, s);
+    }
     if (!rects || !depth_keys || !point_list || !scratch) return fail(SCG_E_NULL, "binning pointer is NULL");
     const size_t need = scg_binning_scratch_bytes(frame->P, num_rendered, frame->width, frame->height, algo);
     if (scratch_bytes < need) return fail(SCG_E_SCRATCH, "binning scratch: %zu < %zu bytes", scratch_bytes, need);
@@ -230,7 +234,8 @@ int scg_binning(const ScgFrame* frame, int64_t num_rendered, const uint32_t* rec
     uint64_t* keys1 = reinterpret_cast<uint64_t*>(base + L.keys1);
     uint32_t* vals0 = reinterpret_cast<uint32_t*>(base + L.vals0);
     uint32_t* offsets = reinterpret_cast<uint32_t*>(base + L.offsets);
-    rc = launch_rect_counts_scan(rects, frame->P, offsets, reinterpret_cast<uint32_t*>(base + L.scan), s);
+    // (ScgFrame.num_rendered_out: the count of THIS path is the last inclusive offset of the tiles touched)
+    rc = launch_rect_counts_scan(rects, frame->P, offsets, reinterpret_cast<uint32_t*>(base + L.scan), f.nr_out, s);
     if (rc) return rc;
     const int end_bit = key_bits(n_tiles);
     const bool odd = (sort_num_passes(end_bit) & 1) != 0;

@@ -179,11 +179,11 @@ __global__ __launch_bounds__(kBlock) void rect_counts_kernel(const uint2* __rest
 }
 
 int launch_rect_counts_scan(const uint32_t* rects, int P, uint32_t* offsets_out, uint32_t* block_sums,
-                            hipStream_t stream) {
+                            uint32_t* total_out, hipStream_t stream) {
     const int blocks = (P + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(rect_counts_kernel, dim3(blocks), dim3(kBlock), 0, stream,
                        reinterpret_cast<const uint2*>(rects), P, offsets_out);
-    return launch_inclusive_scan(offsets_out, offsets_out, P, nullptr, block_sums, stream);
+    return launch_inclusive_scan(offsets_out, offsets_out, P, total_out, block_sums, stream);
 }
 
 // single workgroup: total of nb block sums -> *total_out (num_rendered)

@@ -905,7 +905,8 @@ __global__ __launch_bounds__(kBlock) void rebuild_keys_kernel(const uint32_t* __
                                                               const uint32_t* __restrict__ depth_keys, int64_t R,
                                                               uint64_t* __restrict__ keys_sorted) {
     const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (s >= R) return;
+    // (R may be an upper bound: the slots of point_list behind the counted total were never written, they hold no id to look up)
+    if (s >= R || (uint32_t)s >= tile_start[n_tiles]) return;
     int lo = 0, hi = n_tiles;            // invariant: tile_start[lo] <= s < tile_start[hi]
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;

@@ -102,6 +102,7 @@ int sort_num_passes(int end_bit);
 int launch_duplicate_keys(const FrameDev& f, const uint32_t* rects, const uint32_t* depth_keys,
                           const uint32_t* point_offsets, uint64_t* keys, uint32_t* vals, hipStream_t stream);
 int launch_rect_counts_scan(const uint32_t* rects, int P, uint32_t* offsets_out, uint32_t* block_sums,
+                            uint32_t* total_out /* device-accessible, or nullptr: receives the last offset = num_rendered */,
                             hipStream_t stream);
 int launch_total_from_block_sums(uint32_t* block_sums, int nb, uint32_t* total_out, hipStream_t stream);
 
