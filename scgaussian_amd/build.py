@@ -1,5 +1,6 @@
 """Build libscg_raster.so (the C-ABI HIP library), libscg_io.so (scene files, IO_SOURCES), libscg_img.so (camera images,
-IMG_SOURCES) and libscg_mp.so (the init stage's snapshot, MP_SOURCES) in-tree with hipcc for gfx950.
+IMG_SOURCES), libscg_mp.so (the init stage's snapshot, MP_SOURCES) and libscg_vw.so (the virtual-view warp loss and the depth
+smoothness with their backwards, VW_SOURCES) in-tree with hipcc for gfx950.
 
     python -m scgaussian_amd.build [--force] [--verbose]
 
@@ -9,7 +10,8 @@ optim.hip and initstage.hip are too: Adam rounded where torch rounds it.  So are
 seed.hip (the seeded points) and evalview.hip (the evaluation's masked images and error map) and geocheck.hip (fp64 as numpy rounds
 it) and depthviz.hip (the percentile's interpolation and the colour index as numpy and matplotlib round them) and mono.hip (the
 scene setup's sampler in fp32 and its ray chain in fp64, operation by operation) and plypack.hip of the second library (the saved
-position and the colour bytes) and matchpoint.hip of the fourth (the snapshot's positions, depths and normalised planes).  The 8-bit quantiser
+position and the colour bytes) and matchpoint.hip of the fourth (the snapshot's positions, depths and normalised planes) and virtualwarp.hip of the fifth (the projection, the
+sampler and the window statistics, one rounding per operation).  The 8-bit quantiser
 the image kernels share (csrc/pixel_rules.h) turns contraction off in its own body and does not depend on the flag.
 """
 from __future__ import annotations
@@ -29,6 +31,7 @@ LIB_PATH = os.path.join(HERE, "libscg_raster.so")
 IO_LIB_PATH = os.path.join(HERE, "libscg_io.so")
 IMG_LIB_PATH = os.path.join(HERE, "libscg_img.so")
 MP_LIB_PATH = os.path.join(HERE, "libscg_mp.so")
+VW_LIB_PATH = os.path.join(HERE, "libscg_vw.so")
 EXPORTS_MAP = os.path.join(CSRC, "exports.map")           # global: scg_*; local: everything else
 
 ARCH = "gfx950"
@@ -69,9 +72,13 @@ IMG_SOURCES = {
 MP_SOURCES = {
     "matchpoint.hip": ["-ffp-contract=off"],      # xyz = rays_o + rays_d * z, depth = z * cam_z, (d - min) / (max - min): one rounding per operation
 }
+# The fifth library, libscg_vw.so (include/vw/scg_virtualwarp.h): get_virtual_warp_loss and get_smooth_loss, forward and backward.
+VW_SOURCES = {
+    "virtualwarp.hip": ["-ffp-contract=off"],     # the warp, torch's bilinear sampler and the 5x5 statistics: every product and sum rounded on its own
+}
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "*.h"))) + \
     sorted(glob.glob(os.path.join(INCLUDE, "io", "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "img", "*.h"))) + \
-    sorted(glob.glob(os.path.join(INCLUDE, "mp", "*.h")))                                                # every object depends on all
+    sorted(glob.glob(os.path.join(INCLUDE, "mp", "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "vw", "*.h")))                                                # every object depends on all
 
 
 def _hipcc() -> str:
@@ -152,9 +159,14 @@ def build_mp(force: bool = False, verbose: bool = False) -> str:
     return _build_side(MP_SOURCES, MP_LIB_PATH, force, verbose)
 
 
+def build_vw(force: bool = False, verbose: bool = False) -> str:
+    """libscg_vw.so from VW_SOURCES, as build_io."""
+    return _build_side(VW_SOURCES, VW_LIB_PATH, force, verbose)
+
+
 def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(), flags=(), only=None) -> str:
     """tag/defines build a VARIANT libscg_raster_<tag>.so (selected at run time with SCG_LIB_PATH); the default build has
-    neither and builds libscg_io.so, libscg_img.so and libscg_mp.so behind the main library.  `only`: the sources the defines / flags apply to — the others are
+    neither and builds libscg_io.so, libscg_img.so, libscg_mp.so and libscg_vw.so behind the main library.  `only`: the sources the defines / flags apply to — the others are
     linked from the default build's objects."""
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
@@ -174,6 +186,7 @@ def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(),
         build_io(force=force, verbose=verbose)
         build_img(force=force, verbose=verbose)
         build_mp(force=force, verbose=verbose)
+        build_vw(force=force, verbose=verbose)
     return lib_path
 
 
