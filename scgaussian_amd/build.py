@@ -1,6 +1,7 @@
 """Build libscg_raster.so (the C-ABI HIP library), libscg_io.so (scene files, IO_SOURCES), libscg_img.so (camera images,
 IMG_SOURCES), libscg_mp.so (the init stage's snapshot, MP_SOURCES) and libscg_vw.so (the virtual-view warp loss and the depth
-smoothness with their backwards, VW_SOURCES) in-tree with hipcc for gfx950.
+smoothness with their backwards, VW_SOURCES) and libscg_lp.so (the LPIPS metric: VGG16 on the fp32 matrix pipe, LP_SOURCES) in-tree
+with hipcc for gfx950.
 
     python -m scgaussian_amd.build [--force] [--verbose]
 
@@ -32,6 +33,7 @@ IO_LIB_PATH = os.path.join(HERE, "libscg_io.so")
 IMG_LIB_PATH = os.path.join(HERE, "libscg_img.so")
 MP_LIB_PATH = os.path.join(HERE, "libscg_mp.so")
 VW_LIB_PATH = os.path.join(HERE, "libscg_vw.so")
+LP_LIB_PATH = os.path.join(HERE, "libscg_lp.so")
 EXPORTS_MAP = os.path.join(CSRC, "exports.map")           # global: scg_*; local: everything else
 
 ARCH = "gfx950"
@@ -76,9 +78,15 @@ MP_SOURCES = {
 VW_SOURCES = {
     "virtualwarp.hip": ["-ffp-contract=off"],     # the warp, torch's bilinear sampler and the 5x5 statistics: every product and sum rounded on its own
 }
+# The sixth library, libscg_lp.so (include/lp/scg_lpips.h): the LPIPS metric.  Its convolution sums are explicit fma chains (the
+# fp32 MFMA, fmaf), and the file turns contraction off for the rest, so it needs no flag.
+LP_SOURCES = {
+    "lpips.hip": [],
+}
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "*.h"))) + \
     sorted(glob.glob(os.path.join(INCLUDE, "io", "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "img", "*.h"))) + \
-    sorted(glob.glob(os.path.join(INCLUDE, "mp", "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "vw", "*.h")))                                                # every object depends on all
+    sorted(glob.glob(os.path.join(INCLUDE, "mp", "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "vw", "*.h"))) + \
+    sorted(glob.glob(os.path.join(INCLUDE, "lp", "*.h")))                                                # every object depends on all
 
 
 def _hipcc() -> str:
@@ -164,9 +172,14 @@ def build_vw(force: bool = False, verbose: bool = False) -> str:
     return _build_side(VW_SOURCES, VW_LIB_PATH, force, verbose)
 
 
+def build_lp(force: bool = False, verbose: bool = False) -> str:
+    """libscg_lp.so from LP_SOURCES, as build_io."""
+    return _build_side(LP_SOURCES, LP_LIB_PATH, force, verbose)
+
+
 def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(), flags=(), only=None) -> str:
     """tag/defines build a VARIANT libscg_raster_<tag>.so (selected at run time with SCG_LIB_PATH); the default build has
-    neither and builds libscg_io.so, libscg_img.so, libscg_mp.so and libscg_vw.so behind the main library.  `only`: the sources the defines / flags apply to — the others are
+    neither and builds libscg_io.so, libscg_img.so, libscg_mp.so, libscg_vw.so and libscg_lp.so behind the main library.  `only`: the sources the defines / flags apply to — the others are
     linked from the default build's objects."""
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
@@ -187,6 +200,7 @@ def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(),
         build_img(force=force, verbose=verbose)
         build_mp(force=force, verbose=verbose)
         build_vw(force=force, verbose=verbose)
+        build_lp(force=force, verbose=verbose)
     return lib_path
 
 

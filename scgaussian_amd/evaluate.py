@@ -8,7 +8,8 @@
 The reference makes a few dozen small launches and five synchronising copies per view, and a second process uploads the same pixels
 again.  PNG is lossless, so what metrics.py computes is a function of the quantised pixels; here a view is at most six launches
 (include/scg_eval.h) that read nothing on the host, and a whole set is ONE host read of a (views, 3) record buffer.  LPIPS needs
-VGG weights this project does not carry: a caller who has the metric passes it as `lpips_fn`.  CPU tensors raise ScgError."""
+VGG weights this project does not carry: a caller who has them builds the metric with scgaussian_amd.lpips.Lpips (or brings any
+other) and passes it as `lpips_fn`.  CPU tensors raise ScgError."""
 from __future__ import annotations
 
 import json
