@@ -7,7 +7,8 @@ with hipcc for gfx950.
 
 hipcc cross-compiles without a GPU.  The .so is git-ignored but travels to the GPU box with the
 gpurun snapshot.  geometry.hip is compiled with -ffp-contract=off (bit-exact tile assignment).
-optim.hip and initstage.hip are too: Adam rounded where torch rounds it.  So are densify.hip (the clone's xyz, the / 1.6) and
+optim.hip and initstage.hip are too: Adam in torch's order with one rounding per operation (bits may differ from torch's where
+torch fuses).  So are densify.hip (the clone's xyz, the / 1.6) and
 seed.hip (the seeded points) and evalview.hip (the evaluation's masked images and error map) and geocheck.hip (fp64 as numpy rounds
 it) and depthviz.hip (the percentile's interpolation and the colour index as numpy and matplotlib round them) and mono.hip (the
 scene setup's sampler in fp32 and its ray chain in fp64, operation by operation) and plypack.hip of the second library (the saved
@@ -53,7 +54,7 @@ SOURCES = {
     # (the 8-bit quantiser pins its own contraction, csrc/pixel_rules.h: in the next two files the flag is there for the rest)
     "evalview.hip": ["-ffp-contract=off"],        # test-set evaluation (scg_eval.h): the masked images and the error map's products as torch rounds them
     "matchloss.hip": [],
-    "optim.hip": ["-ffp-contract=off"],           # Adam in torch's rounding order (no fused multiply-adds)
+    "optim.hip": ["-ffp-contract=off"],           # Adam in torch's order, one rounding per operation (no fused multiply-adds; torch itself fuses its lerp)
     "initstage.hip": ["-ffp-contract=off"],       # the init stage's Adam: the same arithmetic (csrc/adam_math.h)
     "densify.hip": ["-ffp-contract=off"],         # clone xyz = rayo + rayd * zval and the / 1.6 rounded as torch rounds them
     "seed.hip": ["-ffp-contract=off"],            # create_from_pcd: points = rays_o + rays_d * z as torch's two operators round it

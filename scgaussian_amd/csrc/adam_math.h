@@ -1,5 +1,7 @@
 // adam_math.h — one element of torch's single-tensor Adam (weight_decay 0, no amsgrad, no maximize), shared by optim.hip and
-// initstage.hip.  Both are compiled with -ffp-contract=off: every operation is rounded where torch rounds it.
+// initstage.hip.  Both are compiled with -ffp-contract=off: fp32 throughout, torch's order of operations, one rounding per
+// operation.  That is the contract (tests/optim_refs.py restates it bit for bit); torch's own bits may differ in the last place
+// where torch fuses, as its lerp does.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -13,7 +13,7 @@
 //     adam_step_kernel forms them) and the next step's pair is fetched while this step's chain runs;
 //   * the progress scalar (sum of wgt * ml per iteration) costs the loop one LDS store per iteration: every 64 iterations thread j
 //     adds up row j of a 64 x 64 tile in lane order and writes partials[k][workgroup].  Fixed order, no atomics.
-// Compiled with -ffp-contract=off, like optim.hip: Adam is rounded where torch rounds it.
+// Compiled with -ffp-contract=off, like optim.hip: Adam in torch's order, one rounding per operation (csrc/adam_math.h).
 #include "scg_common.h"
 #include "adam_math.h"
 #include "../../include/scg_matchloss.h"

@@ -3,7 +3,8 @@
 // adam_step_kernel: torch's single-tensor Adam (weight_decay 0, no amsgrad, no maximize) over up to SCG_ADAM_MAX_SEGMENTS
 // parameter tensors in ONE launch.  The segment table travels by value in the kernel arguments; each workgroup owns one chunk of
 // kAdamChunk elements of one segment and streams it as float4 (scalar when a segment's pointers are not 16-byte aligned, and for
-// the numel % 4 elements at its end).  Compiled with -ffp-contract=off: every operation is rounded where torch rounds it.
+// the numel % 4 elements at its end).  Compiled with -ffp-contract=off: torch's order of operations, every operation rounded on
+// its own.  The bits may differ from torch's where torch fuses (its lerp); tests/optim_refs.py restates what is computed here.
 //
 // Step counters live on the device (state['step']): every workgroup reads s and uses s+1; the LAST workgroup to finish writes
 // s+1 back.  It learns that it is last from a device-scope ticket (release fence before the ticket add, acquire fence in the
