@@ -1,6 +1,6 @@
 """Build libscg_raster.so (the C-ABI HIP library), libscg_io.so (scene files, IO_SOURCES), libscg_img.so (camera images,
 IMG_SOURCES), libscg_mp.so (the init stage's snapshot, MP_SOURCES) and libscg_vw.so (the virtual-view warp loss and the depth
-smoothness with their backwards, VW_SOURCES) and libscg_lp.so (the LPIPS metric: VGG16 on the fp32 matrix pipe, LP_SOURCES) in-tree
+smoothness with their backwards, VW_SOURCES) and libscg_lp.so (the LPIPS metric: VGG16 on the fp32 matrix pipe, LP_SOURCES) and libscg_png.so (PNG files' zlib streams, PNG_SOURCES) in-tree
 with hipcc for gfx950.
 
     python -m scgaussian_amd.build [--force] [--verbose]
@@ -35,6 +35,7 @@ IMG_LIB_PATH = os.path.join(HERE, "libscg_img.so")
 MP_LIB_PATH = os.path.join(HERE, "libscg_mp.so")
 VW_LIB_PATH = os.path.join(HERE, "libscg_vw.so")
 LP_LIB_PATH = os.path.join(HERE, "libscg_lp.so")
+PNG_LIB_PATH = os.path.join(HERE, "libscg_png.so")
 EXPORTS_MAP = os.path.join(CSRC, "exports.map")           # global: scg_*; local: everything else
 
 ARCH = "gfx950"
@@ -84,10 +85,14 @@ VW_SOURCES = {
 LP_SOURCES = {
     "lpips.hip": [],
 }
+# The seventh library, libscg_png.so (include/png/scg_png.h): PNG files' zlib streams.  Integer arithmetic only: no flag.
+PNG_SOURCES = {
+    "pngpack.hip": [],
+}
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "*.h"))) + \
     sorted(glob.glob(os.path.join(INCLUDE, "io", "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "img", "*.h"))) + \
     sorted(glob.glob(os.path.join(INCLUDE, "mp", "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "vw", "*.h"))) + \
-    sorted(glob.glob(os.path.join(INCLUDE, "lp", "*.h")))                                                # every object depends on all
+    sorted(glob.glob(os.path.join(INCLUDE, "lp", "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "png", "*.h")))                                                # every object depends on all
 
 
 def _hipcc() -> str:
@@ -178,9 +183,14 @@ def build_lp(force: bool = False, verbose: bool = False) -> str:
     return _build_side(LP_SOURCES, LP_LIB_PATH, force, verbose)
 
 
+def build_png(force: bool = False, verbose: bool = False) -> str:
+    """libscg_png.so from PNG_SOURCES, as build_io."""
+    return _build_side(PNG_SOURCES, PNG_LIB_PATH, force, verbose)
+
+
 def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(), flags=(), only=None) -> str:
     """tag/defines build a VARIANT libscg_raster_<tag>.so (selected at run time with SCG_LIB_PATH); the default build has
-    neither and builds libscg_io.so, libscg_img.so, libscg_mp.so, libscg_vw.so and libscg_lp.so behind the main library.  `only`: the sources the defines / flags apply to — the others are
+    neither and builds libscg_io.so, libscg_img.so, libscg_mp.so, libscg_vw.so, libscg_lp.so and libscg_png.so behind the main library.  `only`: the sources the defines / flags apply to — the others are
     linked from the default build's objects."""
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
@@ -202,6 +212,7 @@ def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(),
         build_mp(force=force, verbose=verbose)
         build_vw(force=force, verbose=verbose)
         build_lp(force=force, verbose=verbose)
+        build_png(force=force, verbose=verbose)
     return lib_path
 
 

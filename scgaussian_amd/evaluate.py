@@ -168,7 +168,7 @@ def _save_png(path, arr):
 
 
 def render_set(views, gaussians, pipe, background, out_dir=None, name="test", iteration=0, render=_render.render, lpips_fn=None,
-               color_depth=False):
+               color_depth=False, png="pillow"):
     """render.py:133-162 and metrics.py's evaluate over `views` under torch.no_grad().  A view needs what render() needs plus
     `original_image` and, optionally, `dtumask`.  Returns (full, per_view, images): the two dicts in the shape of results.json /
     per_view.json — keyed by the method "ours_<iteration>", the views named "<idx:05d>.png" — and per view the dict of uint8 device
@@ -176,7 +176,10 @@ def render_set(views, gaussians, pipe, background, out_dir=None, name="test", it
     written with PIL from those tensors, copied to the host after the loop.  With `color_depth` every view's dict also holds
     `depth_color`, render.py:162's `visualization` of the normalised depth as an (H,W,3) uint8 device tensor (video.DepthColorizer),
     written as depth/color_<idx:05d>.png; the default leaves every result, file and key as without it.  The colour point cloud of
-    render.py is not part of this."""
+    render.py is not part of this.  png="device" writes the same tree with the files encoded on the GPU (png.py): all images of
+    the call in one batch after the loop, two host reads; every file decodes to the pixels that the default, "pillow", writes."""
+    from . import png as _png
+    on_device = _png.check_route(png)
     views = list(views)
     method = f"ours_{iteration}"
     images = []
@@ -198,7 +201,19 @@ def render_set(views, gaussians, pipe, background, out_dir=None, name="test", it
             base = os.path.join(out_dir, name, method)
             for sub in SUBDIRS:
                 os.makedirs(os.path.join(base, sub), exist_ok=True)
-            host = [{k: None if v is None else v.to("cpu", non_blocking=True) for k, v in im.items()} for im in images]
+            if on_device:
+                paths, batch = [], []
+                for idx, im in enumerate(images):
+                    for sub, key in zip(SUBDIRS, ("renders", "gt", "depth", "error_map", "dtumask")):
+                        if im[key] is not None:
+                            paths.append(os.path.join(base, sub, f"{idx:05d}.png"))
+                            batch.append(im[key])
+                    if color_depth:
+                        paths.append(os.path.join(base, "depth", f"color_{idx:05d}.png"))
+                        batch.append(im["depth_color"])
+                _png.write_batch(paths, [t.contiguous() for t in batch])
+            host = [] if on_device else [{k: None if v is None else v.to("cpu", non_blocking=True) for k, v in im.items()}
+                                         for im in images]
             torch.cuda.synchronize(background.device)
             for idx, im in enumerate(host):
                 for sub, key in zip(SUBDIRS, ("renders", "gt", "depth", "error_map", "dtumask")):

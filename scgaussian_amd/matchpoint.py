@@ -194,10 +194,14 @@ class MatchpointSnapshot:
         body, planes, byte_planes, ranges = self._carve(self.to_host())
         return body.numpy(), [p.numpy() for p in planes], [b.numpy() for b in byte_planes], ranges.numpy()
 
-    def write(self, path: str) -> None:
+    def write(self, path: str, png: str = "pillow") -> None:
         """`path` receives the point cloud (scene.save_init passes .../point_cloud_matchpoint.ply); <key>.npy and
-        sparsedepth_<key>.png of every view go next to it, as the reference places them.  The directory is created if missing."""
+        sparsedepth_<key>.png of every view go next to it, as the reference places them.  The directory is created if missing.
+        png="device" encodes the views' byte planes on the GPU in one batch (png.py) where the default, "pillow", encodes them on
+        the host; both decode to the same pixels."""
+        from . import png as _png
         from .evaluate import _save_png
+        on_device = _png.check_route(png)
         body, planes, byte_planes, _ranges = self.host_views()
         folder = os.path.dirname(os.path.abspath(path))
         os.makedirs(folder, exist_ok=True)
@@ -206,7 +210,11 @@ class MatchpointSnapshot:
             fh.write(memoryview(body))
         for key, plane, q in zip(self.keys, planes, byte_planes):
             np.save(os.path.join(folder, f"{key}.npy"), plane)
-            _save_png(os.path.join(folder, f"sparsedepth_{key}.png"), q)
+            if not on_device:
+                _save_png(os.path.join(folder, f"sparsedepth_{key}.png"), q)
+        if on_device:
+            _png.write_batch([os.path.join(folder, f"sparsedepth_{key}.png") for key in self.keys],
+                             [p.contiguous() for p in self.byte_planes])
 
 
 @torch.no_grad()

@@ -157,7 +157,7 @@ VIDEO_KEYS = ("renders", "depth", "depth_color", "frames_bgr", "depth_frames_bgr
 
 
 def render_video(views, gaussians, pipe, background, out_dir=None, name="video", iteration=0, render=_render.render,
-                 frame_sink=None, depth_sink=None, lut=TURBO, percentile: float = 98.0):
+                 frame_sink=None, depth_sink=None, lut=TURBO, percentile: float = 98.0, png="pillow"):
     """render_video.py:129-152 over `views` under torch.no_grad().  Per frame: render, the depth's range, the select and the frame
     kernel — at most eight launches behind the rasteriser's and no host read —, written into buffers allocated before the loop;
     after the loop ONE copy to the host.  Returns a dict of uint8 numpy arrays over the F frames:
@@ -168,8 +168,12 @@ def render_video(views, gaussians, pipe, background, out_dir=None, name="video",
         depth_frames_bgr (F,H,W,3)   depth_color[..., ::-1]: the frames of depth_video.mp4
     With `out_dir` the three PNGs per frame are written under <out_dir>/<name>/ours_<iteration>/{renders,depth}/.  `frame_sink` and
     `depth_sink` are called with each frame's B, G, R array in order (cv2.VideoWriter.write fits them); no video library is
-    imported and no .mp4 is written here.  All views must have one size, as the reference's single VideoWriter size implies."""
+    imported and no .mp4 is written here.  All views must have one size, as the reference's single VideoWriter size implies.
+    png="device" encodes the 3 F files on the GPU in one batch behind the loop (png.py; two more host reads) and writes the same
+    tree; every file decodes to the pixels that the default, "pillow", writes."""
+    from . import png as _png
     from .evaluate import _save_png
+    on_device = _png.check_route(png)
     views = list(views)
     if not views:
         raise ValueError("render_video needs at least one view")
@@ -193,13 +197,19 @@ def render_video(views, gaussians, pipe, background, out_dir=None, name="video",
             viz.frame(depth, viz.depth_range(depth), render=pkg["render"], depth_color=buf["depth_color"][idx],
                       depth_color_bgr=buf["depth_frames_bgr"][idx], depth_u8=buf["depth"][idx], render_u8=buf["renders"][idx],
                       frame_bgr=buf["frames_bgr"][idx])
+        packed = None
+        if out_dir is not None and on_device:
+            packed = _png.encode([buf[k][idx] for idx in range(F) for k in ("renders", "depth", "depth_color")])
         host = flat.cpu().numpy()          # the video's one host read
     out = {k: host[o:o + s].reshape((F, H, W) if k == "depth" else (F, H, W, 3)) for k, o, s in zip(VIDEO_KEYS, starts, sizes)}
     if out_dir is not None:
         base = os.path.join(out_dir, name, f"ours_{iteration}")
         for sub in ("renders", "depth"):
             os.makedirs(os.path.join(base, sub), exist_ok=True)
-        for idx in range(F):
+        if packed is not None:
+            packed.write([os.path.join(base, sub, f"{pre}{idx:05d}.png") for idx in range(F)
+                          for sub, pre in (("renders", ""), ("depth", ""), ("depth", "color_"))])
+        for idx in range(0 if packed is None else F, F):
             _save_png(os.path.join(base, "renders", f"{idx:05d}.png"), out["renders"][idx])
             _save_png(os.path.join(base, "depth", f"{idx:05d}.png"), out["depth"][idx])
             _save_png(os.path.join(base, "depth", f"color_{idx:05d}.png"), out["depth_color"][idx])
