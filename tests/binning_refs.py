@@ -507,10 +507,11 @@ def _sync_or_exit(what):
         pytest.exit(f"GPU fault in {what}: {e}", returncode=3)
 
 
-def run_binning(fr, algo=AUTO, keys=True, tile_cost_in=None, bwd_cost_in=None):
+def run_binning(fr, algo=AUTO, keys=True, tile_cost_in=None, bwd_cost_in=None, scratch_byte=0x5A):
     """lib.scg_binning on the frame's buffers, pointers passed the way the binding passes them.  Every output starts as PATTERN
-    and is GUARD words longer than the stage may write.  The frame's bound (if any) is passed as num_rendered and sizes
-    point_list, keys_sorted and the scratch.  Returns numpy arrays + `accepts` (scg_binning_accepts_bound)."""
+    and is GUARD words longer than the stage may write; every byte of the scratch starts as `scratch_byte` (the binding hands over
+    whatever torch.empty gave it).  The frame's bound (if any) is passed as num_rendered and sizes point_list, keys_sorted and the
+    scratch.  Returns numpy arrays + `accepts` (scg_binning_accepts_bound)."""
     import torch
     from scgaussian_amd import _lib
     from scgaussian_amd import rasterizer as R
@@ -531,7 +532,7 @@ def run_binning(fr, algo=AUTO, keys=True, tile_cost_in=None, bwd_cost_in=None):
     ks = torch.full((cap + GUARD,), int(np.uint64(PATTERN64).view(np.int64)), dtype=torch.int64, device=dev) if keys else None
     nr = torch.full((1 + GUARD,), pat32, dtype=torch.int32, device=dev)
     sbytes = int(lib.scg_binning_scratch_bytes(fr.P, cap, fr.W, fr.H, algo))
-    scratch = torch.full((sbytes + 256,), 0x5A, dtype=torch.uint8, device=dev)
+    scratch = torch.full((sbytes + 256,), int(scratch_byte), dtype=torch.uint8, device=dev)
     tci = None if tile_cost_in is None else up(np.asarray(tile_cost_in, np.uint32).view(np.int32))
     bci = None if bwd_cost_in is None else up(np.asarray(bwd_cost_in, np.uint32).view(np.int32))
     assert tci is None or tci.numel() == fr.T
@@ -663,9 +664,10 @@ def oracle_rects(sc):
     return pre["rect"].numpy().astype(np.int64), pre["depth"].numpy().astype(np.float32), pre["visible"].numpy()
 
 
-def run_forward(sc, capacity, options):
-    """lib.scg_forward through ctypes on a Scene: the workspace starts as PATTERN bytes; rects, depth_keys, point_list (up to the
-    next buffer of the workspace), the ranges words (likewise) are read back through scg_workspace_layout."""
+def run_forward(sc, capacity, options, ws_byte=None):
+    """lib.scg_forward through ctypes on a Scene: the workspace starts as PATTERN words (ws_byte: every byte of it as that byte
+    instead); rects, depth_keys, point_list (up to the next buffer of the workspace), the ranges words (likewise) are read back
+    through scg_workspace_layout."""
     import ctypes as C
     import torch
     from scgaussian_amd import _lib
@@ -681,7 +683,10 @@ def run_forward(sc, capacity, options):
     L = _lib.ScgWorkspaceLayout()
     R.check(lib.scg_workspace_layout(P, capacity, W, H, C.byref(L)), "scg_workspace_layout")
     ws = torch.empty(int(L.total) + 256, dtype=torch.uint8, device=dev)
-    ws.view(torch.int32)[:] = int(np.uint32(PATTERN).view(np.int32))
+    if ws_byte is None:
+        ws.view(torch.int32)[:] = int(np.uint32(PATTERN).view(np.int32))
+    else:
+        ws.fill_(int(ws_byte))
     radii = torch.zeros(P, dtype=torch.int32, device=dev)
     color, depth, alpha = (torch.zeros(n, H, W, device=dev) for n in (3, 1, 1))
     sums = torch.zeros(int(L.partial_words) + 8, dtype=torch.int32, device=dev)
@@ -704,7 +709,8 @@ def run_forward(sc, capacity, options):
     at = lambda off, n: w32[int(off) // 4: int(off) // 4 + n]
     nw = ranges_words(sc.T)
     assert (int(L.ranges) - int(L.point_list)) // 4 >= capacity and (int(L.final_T) - int(L.ranges)) // 4 >= nw
-    return dict(rects=at(L.rects, 2 * P).reshape(P, 2).copy(), depth_keys=at(L.depth_keys, P).copy(),
+    image = {k: v.cpu().numpy() for k, v in (("color", color), ("depth", depth), ("alpha", alpha), ("radii", radii))}
+    return dict(image, rects=at(L.rects, 2 * P).reshape(P, 2).copy(), depth_keys=at(L.depth_keys, P).copy(),
                 point_list=at(L.point_list, (int(L.ranges) - int(L.point_list)) // 4).copy(),
                 words=at(L.ranges, (int(L.final_T) - int(L.ranges)) // 4).copy(),
                 long_lists=long_words.numpy().copy(), num_rendered_out=int(nr.cpu().numpy().view(np.uint32)[0]),

@@ -882,13 +882,17 @@ REQUIRED = tuple(f"n={n}" for n in (0, 1, 2, 63, 64, 65, 127, 128, 129, 200)) + 
 
 # ------------------------------------------------------------------------------------------------------- the two staged calls
 
-def run_staged(fr, cull=True, order="identity", depth=True, alpha=True, clear="memset", prefill=None, costs=False, order_seed=0):
+def run_staged(fr, cull=True, order="identity", depth=True, alpha=True, clear="memset", prefill=None, costs=False, order_seed=0,
+               start=None):
     """lib.scg_blend_forward and lib.scg_blend_backward on the frame's buffers, pointers passed the way the binding passes them.
     Every output starts as NaN (n_contrib: -1), so an element the kernels leave unwritten shows.
       depth / alpha   True: the frame's upstream; None: a NULL pointer; "zero": a zero tensor
       clear           "memset": prezeroed = 0 on a NaN-filled record buffer; "forward": the buffer is handed to the forward as
                       dsplats_zero, then prezeroed = 1; "prefill": prezeroed = 1 on a buffer holding `prefill` (P, 16)
       costs           hand tile_cost_out (zeroed: the forward takes a maximum) and bwd_cost_out (all ones) to the frame
+      start           None, or a fill of tests/guarded_alloc.py: every buffer the two calls write or add into (the five images,
+                      the gradient records unless prefilled, bwd_cost_out) starts from that fill's bytes instead of NaN / -1 —
+                      what torch.empty hands the binding.  tile_cost_out stays zeroed: that is its contract
     Returns numpy arrays.  (Imports torch and the package here: the references above need neither.)"""
     import torch
     from scgaussian_amd import _lib
@@ -911,6 +915,11 @@ def run_staged(fr, cull=True, order="identity", depth=True, alpha=True, clear="m
     assert (clear == "prefill") == (prefill is not None)
     tile_cost = torch.zeros(fr.T, dtype=torch.int32, device=dev) if costs else None
     bwd_cost = torch.full((4 * fr.T,), -1, dtype=torch.int32, device=dev) if costs else None
+    if start is not None:
+        import guarded_alloc
+        for t in (color, dimg, aimg, final_T, n_contrib, bwd_cost) + (() if prefill is not None else (dsplats,)):
+            if t is not None:
+                guarded_alloc.poison_(t, start)
     pick = lambda sel, a: None if sel is None else (torch.zeros(H, W, dtype=torch.float32, device=dev) if sel == "zero" else up(a))
     dC, dD, dA = up(fr.dL_dcolor), pick(depth, fr.dL_ddepth), pick(alpha, fr.dL_dalpha)
     c = frame_.c

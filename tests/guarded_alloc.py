@@ -21,16 +21,29 @@ Two fills (FILL_A, FILL_B) exist so that a stray write of a value that happens t
 that a result which depends on bytes outside its inputs differs between the two runs.  The fills of wider integers are the small
 valid indices 1 and 2: a kernel that reads an index one element too far is not steered to a wild address.
 
+Poison.  The caching allocator recycles blocks, so the first bytes of a torch.empty / torch.empty_like request are whatever was there
+last — usually zeros or the previous call's values, which is exactly what a kernel that reads a scratch word before anyone wrote it,
+leaves part of an output unwritten or assumes that a counter starts at 0 needs in order to pass.  Under guarded(fill) — poison=True
+is the default — the BODY of such a request starts from the same fill as its bands: every byte 0xFF (A) or 0x3C (B) for floating
+and 8-bit types, the indices 1 (A) and 2 (B) for int16/32/64, and True (A) / False (B) for bool, whose bytes torch defines only as
+0 and 1.  A result that depends on an unwritten word then differs between the A run and the B run.  zeros, ones, full, tensor and
+arange hold what was asked for, and Registry.like / rehome are followed by a copy_: none of them is poisoned.  A pinned host
+empty(..., pin_memory=True) stays unguarded (no bands, in no body) but gets the same fill: the wrappers fill such buffers with
+device-to-host copies and then write them to files or upload them, and a byte the copy does not cover must not look written.
+guarded(fill, poison=False) leaves every body as the allocator gave it.
+
 Nothing here reads or changes the environment, the allocator's settings or how Python starts; the patched names are restored when the
 context ends, also after an exception.
 """
 import contextlib
 import ctypes as C
 import functools
+import math
 import sys
 import types
 from collections import namedtuple
 
+import numpy as np
 import torch
 
 BAND = 4096                    # bytes of each band: a multiple of every alignment the libraries ask for (16, 64, 256)
@@ -59,6 +72,40 @@ Call = namedtuple("Call", "name pointers")     # pointers: [(path, value)], path
 
 def fill_class(dtype):
     return "wide" if dtype in _WIDE_INTS else "byte"
+
+
+def fill_byte(fill):
+    """The byte every floating and 8-bit band and poisoned body holds under `fill`."""
+    return _BYTE[fill]
+
+
+def poison_(t, fill):
+    """Fill every byte the dense tensor `t` owns with the fill of its dtype, in place; returns t."""
+    if t.numel() == 0:
+        return t
+    if t.dtype == torch.bool:
+        return t.fill_(fill == FILL_A)
+    if fill_class(t.dtype) == "wide":
+        return t.fill_(_WIDE[fill])
+    flat = torch.as_strided(t, (_span(t.shape, t.stride()),), (1,), t.storage_offset())      # complex, bfloat16, ...: bytes all the same
+    flat.view(torch.uint8).fill_(_BYTE[fill])
+    return t
+
+
+def same_bits(a, b):
+    """Whether two results (tensors, arrays, numbers, bytes, or dicts and lists of them) are equal bit for bit; two NaN floats are."""
+    if isinstance(a, torch.Tensor):
+        return isinstance(b, torch.Tensor) and a.shape == b.shape and a.dtype == b.dtype and \
+            torch.equal(a.contiguous().reshape(-1).view(torch.uint8), b.contiguous().reshape(-1).view(torch.uint8))
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(same_bits(a[k], b[k]) for k in a)
+    if isinstance(a, (list, tuple)):
+        return isinstance(b, (list, tuple)) and len(a) == len(b) and all(same_bits(x, y) for x, y in zip(a, b))
+    if isinstance(a, float) and isinstance(b, float) and math.isnan(a) and math.isnan(b):
+        return True
+    if isinstance(a, np.ndarray):
+        return isinstance(b, np.ndarray) and a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+    return a == b
 
 
 def band_bytes(dtype, fill, device="cpu"):
@@ -102,8 +149,8 @@ def _requester():
 class Registry:
     """Every raw buffer of one guarded() context, kept alive until the registry itself goes."""
 
-    def __init__(self, fill, devices):
-        self.fill, self.devices = fill, tuple(devices)
+    def __init__(self, fill, devices, poison=True):
+        self.fill, self.devices, self.poison = fill, tuple(devices), bool(poison)
         self.allocations = []
 
     # ---- allocation
@@ -115,8 +162,10 @@ class Registry:
             device = torch.get_default_device() if hasattr(torch, "get_default_device") else "cpu"
         return torch.device(device).type in self.devices
 
-    def allocate(self, shape, dtype, device, strides=None):
-        """An uninitialised tensor of this shape, dtype and (dense or overlapping-free) strides between two bands."""
+    def allocate(self, shape, dtype, device, strides=None, undefined=False):
+        """A tensor of this shape, dtype and (dense or overlapping-free) strides between two bands.  undefined: the request leaves
+        the content to chance (empty, empty_like), so under poison the whole body starts from the fill; otherwise the caller writes
+        every element next and the body is left as the allocator gave it."""
         shape = tuple(int(s) for s in shape)
         if strides is None:
             strides, acc = [], 1
@@ -133,6 +182,8 @@ class Registry:
         a.band("front").copy_(fill)
         a.band("back").copy_(fill)
         self.allocations.append(a)
+        if undefined and self.poison:
+            poison_(raw[start:start + nbytes].view(dtype), self.fill)
         body = raw[start:start + nbytes].view(dtype)
         return body.as_strided(shape, strides, body.storage_offset())
 
@@ -230,12 +281,19 @@ def _make_patches(reg, orig):
     def finish(t, kwargs):
         return t.requires_grad_() if kwargs.get("requires_grad") else t
 
+    def pinned(name, t, kwargs):
+        """A pinned host empty / empty_like passes through unguarded whatever `devices` says, and is poisoned all the same."""
+        if reg.poison and name in ("empty", "empty_like") and kwargs.get("pin_memory") and kwargs.get("out") is None \
+                and isinstance(t, torch.Tensor) and t.layout == torch.strided and t.device.type == "cpu":
+            poison_(t, reg.fill)
+        return t
+
     def plain(name):
         def fn(*args, **kwargs):
             if not reg.wants(kwargs.get("device"), kwargs):
-                return orig[name](*args, **kwargs)
+                return pinned(name, orig[name](*args, **kwargs), kwargs)
             m = orig[name](*args, **_meta(kwargs))
-            t = reg.allocate(m.shape, m.dtype, kwargs.get("device") or _default_device(), m.stride())
+            t = reg.allocate(m.shape, m.dtype, kwargs.get("device") or _default_device(), m.stride(), undefined=name == "empty")
             if name == "zeros":
                 t.zero_()
             elif name == "ones":
@@ -250,9 +308,9 @@ def _make_patches(reg, orig):
             src = args[0] if args else kwargs["input"]
             device = kwargs.get("device")
             if not reg.wants(src.device if device is None else device, kwargs) or src.layout != torch.strided:
-                return orig[name](*args, **kwargs)
+                return pinned(name, orig[name](*args, **kwargs), kwargs)
             m = orig[name](*args, **_meta(kwargs))
-            t = reg.allocate(m.shape, m.dtype, src.device if device is None else device, m.stride())
+            t = reg.allocate(m.shape, m.dtype, src.device if device is None else device, m.stride(), undefined=name == "empty_like")
             if name == "zeros_like":
                 t.zero_()
             elif name == "ones_like":
@@ -283,13 +341,14 @@ def _default_device():
 
 
 @contextlib.contextmanager
-def guarded(fill, devices=("cuda",)):
+def guarded(fill, devices=("cuda",), poison=True):
     """Replace torch.<name> for every name in PATCHED while the context is active; yields the Registry.  Allocations on a device
-    type outside `devices` (the default: GPU only), pinned ones and those with `out=` pass through unchanged."""
+    type outside `devices` (the default: GPU only), pinned ones and those with `out=` get no bands and lie in no body.  poison: the
+    body of an empty / empty_like request, and a pinned host one, starts from the fill (the module's docstring)."""
     if fill not in (FILL_A, FILL_B):
         raise ValueError(f"fill is FILL_A or FILL_B, not {fill!r}")
     orig = {n: getattr(torch, n) for n in PATCHED}
-    reg = Registry(fill, devices)
+    reg = Registry(fill, devices, poison)
     patches = _make_patches(reg, _REAL)
     try:
         for n in PATCHED:

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import binning_refs as BR
+import guarded_alloc as G
 
 pytestmark = pytest.mark.gpu
 
@@ -85,6 +86,51 @@ def test_two_runs_of_a_frame_give_the_same_bits(name):
     a, b = BR.run_binning(fr, BR.AUTO), BR.run_binning(fr, BR.AUTO)
     assert np.array_equal(a["point_list"], b["point_list"]) and np.array_equal(a["words"][:2 * fr.T], b["words"][:2 * fr.T])
     assert np.array_equal(a["keys_sorted"], b["keys_sorted"])
+
+
+# one frame per internal path of scg_binning — every lengths frame holds lists of each sort size, work lists and global scratch
+# included: equal keys (the radix / bitonic fallbacks), the dense 8-wave sort with the bucket limit reached, a large grid (bands,
+# padded order slots), spread keys (the bucket sorts) — and the global 64-bit key sort
+START_FRAMES = (("lengths:equal/sparse", "auto"), ("lengths:bucket_ties/dense", "auto"), ("grid:129x128", "auto"),
+                ("lengths:spread/sparse", "auto"), ("lengths:equal/sparse", "global"))
+
+
+@pytest.mark.parametrize("name, algo", START_FRAMES, ids=[f"{n}-{a}" for n, a in START_FRAMES])
+def test_what_the_scratch_held_before_the_call_changes_no_bit(name, algo):
+    """The runner's scratch starts as one fixed byte, 0x5A; the binding's comes from torch.empty.  A word of it that a kernel reads,
+    or adds to, before anybody wrote it — class_counts, len_hist, a row of the slice table, the sort's counters — gives another
+    list, another range or a broken order table when the scratch starts from other bytes: here from the two fills of
+    tests/guarded_alloc.py (0xFF and 0x3C in every byte: guarded_alloc.fill_byte).  Every output is compared bit for bit, guards included; of the two order
+    tables only what compare_run holds (permutations, every entry in its band, longer classes first): the order inside a length
+    class is whatever the LDS atomics give, from run to run."""
+    fr, ref = BR.frame(name), BR.reference(name)
+    a, b = (BR.run_binning(fr, ALGOS[algo], scratch_byte=G.fill_byte(fill)) for fill in (G.FILL_A, G.FILL_B))
+    assert a.keys() == b.keys()
+    nw = BR.ranges_words(fr.T)
+    for out in (a, b):
+        BR.compare_run(ref, out)
+        out["ranges"], out["behind_the_words"] = out["words"][:2 * fr.T], out["words"][nw:]
+        del out["words"]
+    for k in a:
+        assert G.same_bits(a[k], b[k]), (name, algo, k)
+
+
+@pytest.mark.parametrize("options", (0, BR.SKIP_RARE_SORT, BR.RARE_8WAVE | BR.SPLIT_LONG_LISTS, BR.DEBUG_SEPARATE_SORT | BR.DEBUG_SEPARATE_HIST),
+                         ids=("fused", "skip_rare", "split", "separate"))
+def test_what_the_workspace_held_before_scg_forward_changes_no_bit(options):
+    """The same for the one-call path's workspace (every plane of the frame and the binning scratch in one allocation), on the
+    scene of tied depths, sparse and dense capacity: the images, radii, rectangles, keys, the lists up to the counted total, the
+    ranges and order words, the long-list counts and num_rendered."""
+    sc = BR.forward_scene("ties")
+    for capacity in (sc.P, sc.T * BR.DENSE_MEAN):
+        a, b = (BR.run_forward(sc, capacity, options, ws_byte=G.fill_byte(fill)) for fill in (G.FILL_A, G.FILL_B))
+        nw, R = BR.ranges_words(sc.T), a["num_rendered_out"]
+        assert R == b["num_rendered_out"] == sc.P <= capacity
+        for out in (a, b):                                       # (behind the counted total and behind the words: nobody's; the
+            BR.check_order_bands(out["words"][:nw], sc.T)        #  order inside a length class: the LDS atomics')
+            out["point_list"], out["words"] = out["point_list"][:R], out["words"][:2 * sc.T]
+        for k in a:
+            assert G.same_bits(a[k], b[k]), (options, capacity, k)
 
 
 # ------------------------------------------------------------------------------------------- the same edges through scg_forward

@@ -185,6 +185,24 @@ def test_clearing_the_records(key):
     assert memset["dsplats"].any() and np.array_equal(added["dsplats"][:, UNUSED], prior[:, UNUSED])
 
 
+@pytest.mark.parametrize("clear, costs", [("memset", False), ("forward", False), ("memset", True)], ids=["memset", "by_forward", "costs"])
+def test_what_the_buffers_held_before_the_calls_changes_no_bit(clear, costs):
+    """The runner starts every buffer the two calls write or add into from ONE pattern (NaN; -1).  The binding's come from
+    torch.empty: here they start from the two fills of tests/guarded_alloc.py, per way of clearing the records and with the cost
+    words on, and every output must come out with the same bits — a record that is added to before it was cleared, a pixel or a
+    cost word that is left as it was, differs.  (Single-atomic frames: the records' sums have no order.)"""
+    import guarded_alloc as G
+    for key in ("b", "translation-e", "padding-127"):
+        ref = B.reference(key)
+        fr = ref["frame"]
+        assert B.single_atomic(ref)
+        a, b = (B.run_staged(fr, clear=clear, costs=costs, start=fill) for fill in (G.FILL_A, G.FILL_B))
+        plain = B.run_staged(fr, clear=clear, costs=costs)
+        assert a.keys() == b.keys() == plain.keys()
+        for k in a:
+            assert G.same_bits(a[k], b[k]) and G.same_bits(a[k], plain[k]), (key, clear, costs, k)
+
+
 @pytest.mark.parametrize("key", B.BASE_FRAMES + ("padding-127",))
 def test_cost_hints_count_what_the_walks_do(key):
     """With the cull switched off every quadrant walks every entry until all its pixels have terminated: tile_cost_out[t] is the

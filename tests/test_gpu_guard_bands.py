@@ -11,10 +11,18 @@ little, changes nothing those tests look at.  Here every case runs three times â
      itself derives with torch arithmetic or uploads â€” never an output or a scratch buffer in device memory);
   3. every output / scratch parameter of the header was seen non-NULL at least once (a case's `not_passed` names the optional ones
      it leaves out, `fields` the outputs inside struct arguments);
-  4. the public results of the three runs are bit-identical â€” except where float atomics sum them, held to the module's own bar.
+  4. the public results of the three runs are bit-identical â€” except where float atomics sum them, held to the module's own bar;
+  5. under A and under B the body of every torch.empty / torch.empty_like request of the binding (outputs, scratch, workspaces,
+     arenas, the pinned staging buffers) starts from the fill instead of what the allocator last held there (guarded_alloc:
+     "Poison"), the third run stays unpoisoned as the baseline, and condition 4 is the detector: a scratch float read before
+     anything wrote it is a NaN under A and 0.0115 under B, an output element nobody wrote has different bits under A and B, a
+     counter assumed to start at 0 starts at 0xFFFFFFFF and at 0x3C3C3C3C (1 and 2 in an int16/32/64 tensor).
 
 A difference between A and B means bytes outside an input reached a result: a finding of the same rank as a touched band.  No case
-plants an out-of-range value; every call is one the wrappers make today at sizes the suite already uses.
+plants an out-of-range value; every call is one the wrappers make today at sizes the suite already uses â€” the second half of the
+table at the paths that write least (everything culled, one tile, nothing kept, nothing selected, nothing in bounds, all NaN, the
+smallest image), where a "nothing to do" return would leave an output as it was.  Where the module's own test knows the exact
+answer of such a path (zeros, the background, NaN), the case asserts it inside run() as well.
 
 Index reads, audited by reading the kernels before the first guarded run (the wider-integer fills are the valid indices 1 and 2 all
 the same; none needed a fix): the segment tables of seed.hip and matchpoint.hip are copied to LDS with s < nseg and searched inside
@@ -23,6 +31,50 @@ segment and view tables at blockIdx (the launch dimensions are their lengths) an
 pngpack.hip checks a chunk's image index against the image count; resample.hip clamps the column index to wout - 1 and a bound to
 [0, win - 1]; the geocheck pair table is written by scg_geocheck_setup itself; scg_sort_pairs and scg_inclusive_scan_u32 take
 their integers as values, never as addresses; scg_densify_stats compares radii with 0.
+
+Scratch words, audited by reading before the first poisoned run â€” per family: the words a kernel reads or updates atomically, and
+who wrote or cleared them earlier in the same call (K: the kernel itself or an earlier launch of the call; M: a hipMemsetAsync on
+the call's stream; W: the wrapper).  No dependence on an unwritten word was found and no product code changed; that "none" rests
+on this reading and on the cases below, not on a proof.
+  binning_tiles.hip   class_counts[4] and len_hist[1024]: K, cleared by workgroup 0 of tile_hist_kernel or geometry_hist_kernel
+                      (one launch before the first atomic on them); table[B][Tn]: K, every one of the B workgroups stores its whole
+                      row, also one that owns no Gaussian; tile_total / tile_part / tile_class / tile_start: K, table_colscan_kernel
+                      and the eight publishing workgroups write every tile; mid_tiles / big_tiles / segments: read up to the counts
+                      in class_counts only; seg_count is class_counts[2]; the scatter's cursors are LDS; spill: written by the
+                      list's own workgroup before it is read; ranges / order / order_q: K, every slot (padding slots n_tiles)
+  binning.hip         counts[256][blocks] and totals[256]: K (sort_hist_kernel stores every word, sort_rowscan_kernel the totals);
+                      the scan's block sums: K; ranges on the global-sort and the empty path: M, the two order tables K
+  geometry.hip        next_chunk and the block sums of geometry_hist_kernel are LDS, cleared behind a barrier; block_sums /
+                      partial_sums: K, one store per 256-Gaussian block (armed by the host on the one-call path); splats, rects,
+                      depth_keys, clamped, radii: K, flush_stage writes culled Gaussians too
+  blend.hip           cost_out: K (publish_tile_starts stores 0 per tile before the forward's atomicMax; the hint buffers come from
+                      torch.zeros); bcost_out: K, stored per (tile, quadrant), 0 on an empty walk; dsplats: K (the forward blend's
+                      zero_fill, every record, before any tile test) or M (not prezeroed); final_T / n_contrib: K, every pixel
+                      inside the image; the record planes of the fused forward are LDS
+  the rasterizer's workspace (scg_forward / scg_backward, _launch_forward's `ws`, forward_stages' two _Arena.buf): the planes
+                      above carved from one allocation; the padding between them and point_list beyond the counted total are
+                      never read; the gradient arena (_grads.py): K, every row of every segment (zeros for a culled Gaussian;
+                      the SH tail when the arena carries no promise yet), its <= 3 padding floats per segment belong to nobody
+  matchloss.hip       loss, grad_depth: W (one torch.zeros for both)
+  optim.hip           ws: W, zero by contract (torch.zeros once, the kernel returns every word to 0 or to the watermark)
+  initstage.hip       partials: K, rows [0, n_steps) x every workgroup, flushed before the kernel ends; loss_state / grad: K
+  dtumask.hip         count: M; the partial sums of the masked mean and of the metrics: K, one word per workgroup, all read
+  evalview.hip        sk[2]: M; the range's partial (min, max): K; mask_u8 is not written without a mask and not returned
+  depthviz.hip        all kSelWords words (three histograms, max of ~key, NaN count): M
+  loss.hip, knn.hip   partials / partial (splits, n, 3): K, every word the fold reads
+  geocheck.hip        workspace, votes, masks, filtered: W (torch.zeros); the kernel skips a record whose source is no view
+  compact.h, densify.hip, seed.hip: counts: K, one store per workgroup, carry_scan reads groups words; head: K (scan kernel);
+                      fate / keep: K for i < P; winner: K, seed_classify_kernel / mp_clear_kernel store -1 in every pixel before
+                      the atomicMax launches; the new statistics rows: K, zeroed whole by the scatter
+  matchpoint.hip      partial (min, max): K per resolve workgroup; the gaps behind the four regions of the buffer: K (mp_clear)
+  virtualwarp.hip     y, dyd: K, every (view, channel, pixel) whether in bounds or not; coef, loss_map, winner: K per pixel;
+                      partial: K per tile; the smoothness partials (2, groups): K
+  lpips.hip           taps, the two activation buffers, partial [tap][pb]: K, each layer writes what the next one reads
+  resample.hip        mid: K, whole dwords of every row; the bytes of a row's pitch behind its last dword are never read
+  pngpack.hip         lengths, info, base, ioff, table: K for every chunk and image; the image table is uploaded by _bind before
+                      the first launch; the gaps between the streams in `out` belong to nobody and reach no file
+  plypack.hip, mono.hip: no scratch; every byte of the buffer / arena region an entry owns is written by it; the tables the mono
+                      kernels index are uploaded from the host copy
 """
 import contextlib
 import glob
@@ -36,7 +88,7 @@ import pytest
 import torch
 
 import abi_text
-from guarded_alloc import FILL_A, FILL_B, guarded, traced
+from guarded_alloc import FILL_A, FILL_B, guarded, same_bits as _same_bits, traced
 from scgaussian_amd import _lib_lp, _lib_mp, _lib_vw, ply as _ply_module
 
 pytestmark = pytest.mark.gpu
@@ -152,21 +204,6 @@ def _run_once(case, fill):
     return out, calls, reg
 
 
-def _same_bits(a, b):
-    if isinstance(a, torch.Tensor):
-        return isinstance(b, torch.Tensor) and a.shape == b.shape and a.dtype == b.dtype and \
-            torch.equal(a.reshape(-1).view(torch.uint8), b.reshape(-1).view(torch.uint8))
-    if isinstance(a, dict):
-        return isinstance(b, dict) and a.keys() == b.keys() and all(_same_bits(a[k], b[k]) for k in a)
-    if isinstance(a, list):
-        return isinstance(b, list) and len(a) == len(b) and all(_same_bits(x, y) for x, y in zip(a, b))
-    if isinstance(a, float) and isinstance(b, float) and math.isnan(a) and math.isnan(b):
-        return True
-    if isinstance(a, np.ndarray):
-        return isinstance(b, np.ndarray) and a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-    return a == b
-
-
 SEEN = set()                                                      # every entry a case of this file reached (the coverage test)
 TIMES = {}
 # the entries that write device memory through the pointer fields of a struct argument (the headers' comments say which fields):
@@ -278,16 +315,21 @@ def _image_loss(shape, lam):
                 ["scg_image_loss_forward_combined", "scg_image_loss_backward_combined"])
 
 
-def _image_loss_pair(shape):
+def _image_loss_pair(shape, same=False):
     def run(home):
         import test_image_loss as T
         from scgaussian_amd import losses
         x, y = T._content("hdr", shape, seed=sum(shape) + 1)
+        if same:
+            y = x.clone()                                         # identical images: no pixel has anything to add to the L1 sum
         xd, yd = home(x.to(DEV).requires_grad_(True)), home(y.to(DEV))
         l1, ss = losses.l1_and_ssim(xd, yd)
         torch.autograd.backward([l1, ss], [_scalar(0.8), _scalar(-0.2)])
+        if same:
+            assert float(l1.detach()) == 0.0 and bool(torch.isfinite(xd.grad).all()) and math.isfinite(float(ss.detach()))
         return dict(l1=l1, ssim=ss, grad=xd.grad)
-    return Case(f"image_loss_pair-{'x'.join(map(str, shape))}", run, ["scg_image_loss_forward", "scg_image_loss_backward"],
+    return Case(f"image_loss_pair-{'x'.join(map(str, shape))}{'-identical' if same else ''}", run,
+                ["scg_image_loss_forward", "scg_image_loss_backward"],
                 excused={"scg_image_loss_backward": {"weights": "two words the wrapper forms with torch.stack(...) * (1 / n)"}})
 
 
@@ -308,6 +350,26 @@ def _match_loss(M):
         return dict(loss=out, grad=d.grad)
     # the loss word and the gradient image are summed over matches and pairs by float atomics: the module's own bars
     return Case(f"match_loss-M{M}", run, ["scg_match_loss_pair"], close={"loss": _rel(1e-6), "grad": _rel(1e-4)}.get)
+
+
+def _match_loss_outside(M):
+    """Every match projects outside the second view (the scene of test_match_loss_with_no_counting_match_is_exactly_zero): no
+    match counts, nothing is added to the loss word or to the gradient image."""
+    def run(home):
+        import test_match_loss as T
+        from scgaussian_amd.match_loss import match_loss_from_depth
+        cam0, cams = T._cams(T.MW, T.MH)
+        depth = T._depth(T.MW, T.MH, 5)
+        w2c1 = cams[0].world_view_transform.t().contiguous().clone()
+        w2c1[0, 3] += 1000.0
+        p = T._pair_from_uv0(cam0, cams[0], depth, T._random_uv0(T.MW, T.MH, M, 3), 4, w2c1=w2c1)
+        p["mask0"], p["mask1"] = torch.ones(M), torch.ones(M)
+        d = home(depth.clone().to(DEV)[None].requires_grad_(True))
+        out = match_loss_from_depth(d, [home(T._to_cuda(p))], float(T.MW), float(T.MH))
+        out.backward(_scalar(0.3))
+        assert float(out.detach()) == 0.0 and not bool(d.grad.any())
+        return dict(loss=out, grad=d.grad)
+    return Case(f"match_loss-M{M}-all-outside", run, ["scg_match_loss_pair"])
 
 
 # ---- kNN (scg_knn.h) ----------------------------------------------------------------------------------------------------------------
@@ -378,19 +440,44 @@ def _dtu(n):
     return Case(f"dtu-{n}", run, ["scg_dtu_bg_mask", "scg_masked_mean_forward", "scg_masked_mean_backward", "scg_eval_metrics"])
 
 
+def _dtu_empty(n):
+    """A ground truth without a dark pixel: the mask is empty, the count 0, the alpha term the mean of nothing (NaN, gradient 0);
+    and metrics over an empty selection (NaN)."""
+    def run(home):
+        import test_gpu_dtu as T
+        from scgaussian_amd import dtu
+        H, W = T.SIZES[n]
+        g = torch.Generator().manual_seed(n)
+        bright = torch.rand(3, H, W, generator=g) * 0.4 + 0.5
+        view = dtu.DtuView(home(bright.to(DEV)))
+        alpha = home(torch.rand(1, H, W, generator=g).to(DEV).requires_grad_(True))
+        term = dtu.alpha_term(alpha, view)
+        term.backward(_scalar(0.7))
+        img, gt = (home((torch.rand(3, H, W, generator=g) * 1.8 - 0.4).to(DEV)) for _ in range(2))
+        l1, psnr, mse = dtu.eval_metrics_all(img, gt, home(torch.zeros(H, W).to(DEV)))
+        assert int(view.count) == 0 and not bool(view.mask.any()) and torch.equal(view.gt.cpu(), bright)
+        assert math.isnan(float(term.detach())) and not bool(alpha.grad.any())
+        assert math.isnan(float(l1)) and math.isnan(float(psnr)) and bool(torch.isnan(mse).all())
+        return dict(mask=view.mask, gt=view.gt, count=view.count, term=term, grad=alpha.grad, l1=l1, psnr=psnr, mse=mse)
+    return Case(f"dtu-{n}-empty", run, ["scg_dtu_bg_mask", "scg_masked_mean_forward", "scg_masked_mean_backward", "scg_eval_metrics"])
+
+
 # ---- the evaluation view (scg_eval.h) -------------------------------------------------------------------------------------------------
 
-def _eval_view(masked):
+def _eval_view(masked, nan_depth=False):
     def run(home):
         import eval_refs as ER
         import test_gpu_eval as T
         from scgaussian_amd import evaluate
         H, W = T.TH + 1, T.TW + 1
         render, gt, depth = ER.images(H, W, seed=100 * H + W, outside=True)
+        if nan_depth:
+            depth = torch.full_like(depth, float("nan"))          # no finite depth: the range is (NaN, NaN)
         mask = home(T._mask(H, W, 7 * H + W).to(DEV)) if masked else None
         out = evaluate.evaluate_view(home(render.to(DEV)), home(gt.to(DEV)), home(depth.to(DEV)), mask)
         return {k: v for k, v in out.items() if v is not None}
-    return Case(f"eval_view-{'masked' if masked else 'plain'}", run, ["scg_eval_depth_range", "scg_eval_view", "scg_image_loss_forward"],
+    return Case(f"eval_view-{'masked' if masked else 'plain'}{'-nan-depth' if nan_depth else ''}", run,
+                ["scg_eval_depth_range", "scg_eval_view", "scg_image_loss_forward"],
                 not_passed={"scg_image_loss_forward": {"dmaps"}, "scg_eval_view": set() if masked else {"mask_u8"}})
 
 
@@ -408,13 +495,33 @@ def _geocheck(n, H, W):
     return Case(f"geocheck-{n}x{H}x{W}", run, ["scg_geocheck_setup", "scg_geocheck"])
 
 
+def _geocheck_singular(n, H, W):
+    """View 2 has a focal length of 0 (no inverse): it finds no source and is nobody's source â€” no votes
+    (test_singular_intrinsic_gives_no_votes_and_no_fault)."""
+    def run(home):
+        import test_gpu_geocheck as T
+        from scgaussian_amd import geo_check as gc
+        intrs, exts, depths = T._close_scene(n, H, W, seed=100 + 7 * H + W)
+        intrs = intrs.copy()
+        intrs[2] = np.array([[0.0, 0, W / 2], [0, 0.0, H / 2], [0, 0, 1]])
+        chk = gc.GeoCheck(n, H, W, num_src=2, device=torch.device(DEV, 0))
+        chk.setup(home(torch.from_numpy(intrs).to(DEV)), home(torch.from_numpy(exts).to(DEV)))
+        fd, fm = chk.run(home(torch.from_numpy(depths).to(DEV)), view_thresh=0)
+        assert not bool(chk.votes[2].any()) and not bool(fm[2].any())
+        return dict(filtered=fd, masks=fm, votes=chk.votes, pairs=chk.pairs)
+    return Case(f"geocheck-{n}x{H}x{W}-singular", run, ["scg_geocheck_setup", "scg_geocheck"])
+
+
 # ---- depth colour maps (scg_viz.h) ---------------------------------------------------------------------------------------------------
 
-def _viz(H, W):
+def _viz(H, W, all_nan=False):
     def run(home):
         from scgaussian_amd import video
         rng = np.random.default_rng(H * 2000 + W)
-        x = home(torch.from_numpy(rng.random((H, W), dtype=np.float32) * 5 + 1).to(DEV))
+        plane = rng.random((H, W), dtype=np.float32) * 5 + 1
+        if all_nan:
+            plane[:] = np.nan                                     # every key is the NaN key: one bin, H * W NaNs counted
+        x = home(torch.from_numpy(plane).to(DEV))
         render = home(torch.from_numpy(rng.random((3, H, W), dtype=np.float32) * 1.4 - 0.2).to(DEV))
         viz = home(video.DepthColorizer(H, W))                    # (its table is uploaded with .to(device): moved too)
         r = viz.depth_range(x)
@@ -422,8 +529,11 @@ def _viz(H, W):
                 for k in ("depth_color", "depth_color_bgr", "depth_u8", "render_u8", "frame_bgr")}
         viz.frame(x, r, render=render, **outs)
         stats = viz.stats(x).clone()
+        if all_nan:                                               # matplotlib's "bad" colour everywhere, numpy's NaN percentiles
+            assert int(viz._nan) == H * W and bool(torch.isnan(stats[:2]).all())
+            assert not bool(outs["depth_color"].any()) and not bool(outs["depth_color_bgr"].any())
         return dict(outs, range=r, stats=stats, nan=viz._nan)
-    return Case(f"viz-{H}x{W}", run, ["scg_eval_depth_range", "scg_viz_select", "scg_viz_frame"])
+    return Case(f"viz-{H}x{W}{'-all-nan' if all_nan else ''}", run, ["scg_eval_depth_range", "scg_viz_select", "scg_viz_frame"])
 
 
 # ---- densify, reset-opacity, densification statistics (scg_raster.h) -------------------------------------------------------------
@@ -439,21 +549,32 @@ def _model_results(m):
     return out
 
 
-def _densify(nr, nb):
+def _densify(nr, nb, mode="mixed"):
+    """mode (test_gpu_densify.make_inputs): "none" â€” no gradient is hot, nothing is cloned, split or pruned, the background set is
+    copied as it is; "prune_all" â€” every background row is pruned and none is created: no new row at all."""
     def run(home):
         import test_gpu_densify as T
         from scgaussian_amd import densify
-        t, states, noise = T.make_inputs(nr, nb, 100 + nr, "mixed")
+        t, states, noise = T.make_inputs(nr, nb, 100 + nr, mode)
         m = home(T.build(t, states, DEV, torch.optim.Adam))       # the model, both optimizers and their moments, moved together
+        before = m.bg_xyz.detach().clone()
         densify.install(m)
         m.densify_and_prune(T.MAX_GRAD, T.MIN_OPACITY, T.EXTENT, 20, noise=home(noise.to(DEV)))
         mid = {k: v.detach().clone() for k, v in _model_results(m).items()}
+        if mode == "none":
+            assert torch.equal(m.bg_xyz.detach(), before)
+        if mode == "prune_all":
+            assert m.bg_xyz.shape == (0, 3) and m.xyz_gradient_accum.shape == (nr, 1)
+        if mode != "mixed":                                       # the statistics of every row that is left start from zero
+            assert not bool(m.xyz_gradient_accum.any()) and not bool(m.denom.any()) and not bool(m.max_radii2D.any())
         m.reset_opacity()
         return dict(after_densify=mid, after_reset=_model_results(m))
-    bg = ["args.out." + f for f in ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation")] if nb else []
-    return Case(f"densify-{nr}+{nb}", run, ["scg_densify_classify", "scg_densify_scatter", "scg_reset_opacity"],
+    left = nb and mode != "prune_all"
+    bg = ["args.out." + f for f in ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation")] if left else []
+    return Case(f"densify-{nr}+{nb}" + ("" if mode == "mixed" else "-" + mode), run,
+                ["scg_densify_classify", "scg_densify_scatter", "scg_reset_opacity"],
                 fields={"scg_densify_scatter": bg + ["args.accum", "args.denom", "args.max_radii2D", "args.ray_scaling"]},
-                not_passed={"scg_reset_opacity": set() if nb else {"bg_opacity", "bg_exp_avg", "bg_exp_avg_sq"}})
+                not_passed={"scg_reset_opacity": set() if left else {"bg_opacity", "bg_exp_avg", "bg_exp_avg_sq"}})
 
 
 def _densify_stats(P):
@@ -489,6 +610,32 @@ def _seed(N):
                 fields={"scg_seed_scatter": outs}, excused={"scg_seed_scatter": {"args.segments": "host copy of the segment table"}})
 
 
+def _seed_edges():
+    """Two calls of the scenes of tests/test_gpu_seed.py: no match under the threshold (nothing is scattered, no kNN launch, every
+    pixel of the sparse depth is 0) and a view no segment belongs to (its planes are zero whatever the other views receive)."""
+    def run(home):
+        import test_gpu_seed as T
+        from scgaussian_amd import seed
+        out = {}
+        for name, V, seg_view, loss in (("none_kept", 3, [0, 1, 2, 0], 0.5), ("untouched_view", 4, [0, 3, 0, 1], 0.01)):
+            arena = T.random_arena(32, [8, 8, 8, 8], seg_view, V, H=12, W=16, seed_=5)
+            arena["min_loss"] = torch.full((32,), loss).to(DEV)
+            arena = {k: home(v) if torch.is_tensor(v) else v for k, v in arena.items()}
+            got = seed.seed_arrays(home(T.inputs_of(arena)), arena["min_loss"])
+            if name == "none_kept":
+                assert got["n"] == 0 and not bool(got["masks"].any()) and not bool(got["sparse_depths"].any())
+            else:
+                assert got["n"] == 32 and not bool(got["masks"][2].any()) and not bool(got["sparse_depths"][2].any())
+                assert bool(got["masks"].any())
+            out[name] = got
+        return out
+    outs = ["args." + f for f in ("zval", "rayo", "rayd", "points", "features_dc", "features_rest", "rotation", "opacity_out",
+                                  "max_radii2D")]
+    return Case("seed-none-kept-and-untouched-view", run,
+                ["scg_seed_classify", "scg_seed_scatter", "scg_knn3_mean_dist2_ws", "scg_seed_finish"],
+                fields={"scg_seed_scatter": outs}, excused={"scg_seed_scatter": {"args.segments": "host copy of the segment table"}})
+
+
 # ---- scene setup (scg_mono.h) ------------------------------------------------------------------------------------------------------
 
 MONO_OUTPUTS = ["a." + n for n in ("image_color", "uv", "color", "blender_mask", "rays_o", "rays_d", "cam_rays_d", "cam_z", "z", "uv_t",
@@ -515,16 +662,19 @@ def _mono(which):
 
 # ---- the init stage's snapshot (mp/scg_matchpoint.h) ---------------------------------------------------------------------------------
 
-def _matchpoint(N):
+def _matchpoint(N, empty_view=False):
     def run(home):
         import matchpoint_refs as MR
         import test_gpu_matchpoint as T
         from scgaussian_amd import matchpoint
-        arena = MR.random_arena([N], [0], [(5, 6)], seed=N)
+        if empty_view:                                            # three views, the middle one without a match: a plane of zeros
+            arena = MR.random_arena([N, N + 2], [0, 2], [(5, 6), (3, 7), (4, 5)], seed=N)
+        else:
+            arena = MR.random_arena([N], [0], [(5, 6)], seed=N)
         inputs = home(T.inputs_of(arena, home(T.tensors(arena))))  # (the two device tables are uploaded by the constructor: moved too)
         snap = matchpoint.pack(inputs)
         return dict(buffer=snap.buffer)
-    return Case(f"matchpoint-{N}", run, ["scg_mp_pack"],
+    return Case(f"matchpoint-{N}{'-empty-view' if empty_view else ''}", run, ["scg_mp_pack"],
                 excused={"scg_mp_pack": {"args.segments": "host copy of the segment table", "args.views": "host copy of the view table"}})
 
 
@@ -548,6 +698,11 @@ def _ply(nr, nb):
                     out[f"color{deg}"] = fh.read()
             path = os.path.join(folder, "point_cloud.ply")
             packed.write(path)
+            for name in sorted(os.listdir(folder)):               # the files themselves: point_cloud(.ply, _bg.ply, _color.ply)
+                if name.endswith(".ply"):
+                    with open(os.path.join(folder, name), "rb") as fh:
+                        out["file_" + name] = fh.read()
+            assert ("file_point_cloud_bg.ply" in out) == bool(nb)
             loaded = ply_io.RayBoundModel(**{k: torch.zeros((1,) + R.TAILS[k]) for k in R.RAY_KEYS})
             took = ply.load_ply(loaded, path)
             assert took == ({"ray": True, "bg": True} if nb else {"ray": True})
@@ -561,7 +716,7 @@ def _ply(nr, nb):
 
 # ---- the bicubic resize (img/scg_resample.h) ------------------------------------------------------------------------------------------
 
-def _resize(win, hin, wout, hout, c, shift=1):
+def _resize(win, hin, wout, hout, c, shift=1, float_from="full"):
     def run(home):
         import test_gpu_resize as T
         from scgaussian_amd import images
@@ -575,14 +730,19 @@ def _resize(win, hin, wout, hout, c, shift=1):
         dev = view.device
         plan._device_tables[dev] = home(torch.from_numpy(np.array(plan.tables)).to(dev))      # the plan's cached upload, in a body
         try:
-            out_float = torch.full((channels, hout, wout), -1.0, dtype=torch.float32, device=DEV)
+            if float_from == "full":
+                out_float = torch.full((channels, hout, wout), -1.0, dtype=torch.float32, device=DEV)
+            else:                                                 # undefined content, as the binding's own callers hand it over
+                out_float = torch.empty((channels, hout, wout), dtype=torch.float32, device=DEV)
             got = images.resize_u8(view, (wout, hout), out_float=out_float)
             torch.cuda.synchronize()
         finally:
             plan._device_tables.pop(dev, None)
         assert np.array_equal(got.cpu().numpy(), want) and np.array_equal(out_float.cpu().numpy().view(np.uint32), fl.view(np.uint32))
         return dict(out=got, out_float=out_float)
-    return Case(f"resize-{win}x{hin}-to-{wout}x{hout}-{'L' if c == 0 else 'RGB'}", run, ["scg_resample_u8"])
+    # (the width unchanged: no horizontal pass, no intermediate image)
+    return Case(f"resize-{win}x{hin}-to-{wout}x{hout}-{'L' if c == 0 else 'RGB'}{'' if float_from == 'full' else '-' + float_from}", run,
+                ["scg_resample_u8"], not_passed={"scg_resample_u8": {"mid"} if win == wout else set()})
 
 
 # ---- virtual-view warp and smoothness (vw/scg_virtualwarp.h) -----------------------------------------------------------------------------
@@ -601,6 +761,29 @@ def _warp(H, W, nv):
         loss.backward(_scalar(0.75))
         return dict(loss=loss, loss_map=warp.loss_map, winner=warp.winner, in_bounds=warp.in_bounds, d_img=img.grad, d_depth=depth.grad)
     return Case(f"vw_warp-{H}x{W}x{nv}", run, ["scg_vw_warp_forward", "scg_vw_warp_backward"])
+
+
+def _warp_blind(kind):
+    """The two scenes of test_a_frame_no_view_sees_is_exactly_zero: every source view 100 units aside (nothing in bounds), and a
+    mask that is false everywhere: no winner, a loss of exactly 0 and gradients of exactly 0 in every pixel."""
+    def run(home):
+        import virtualwarp_refs as VR
+        from scgaussian_amd import virtual
+        sc = VR.make_scene(VW_T + 1, VW_T + 3, 3, 5)
+        if kind == "unseen":
+            sc["w2cs"][:, 0, 3] += 100.0
+        else:
+            sc["vir_mask"][:] = False
+        t = home(VR.tensors(sc, device=DEV))
+        warp = virtual.VirtualWarp(t["intrs"], t["w2cs"], t["img_colors"])
+        warp.set_pose(sc["vir_c2w"])
+        img, depth = t["virtual_img"].requires_grad_(True), t["virtual_depth"].requires_grad_(True)
+        loss = warp.loss(img, depth, t["vir_mask"])
+        loss.backward(_scalar(0.75))
+        assert float(loss.detach()) == 0.0 and bool((warp.winner == -1).all()) and not bool(warp.loss_map.any())
+        assert not bool(img.grad.any()) and not bool(depth.grad.any()) and bool(warp.in_bounds.any()) == (kind != "unseen")
+        return dict(loss=loss, loss_map=warp.loss_map, winner=warp.winner, in_bounds=warp.in_bounds, d_img=img.grad, d_depth=depth.grad)
+    return Case(f"vw_warp-{kind}", run, ["scg_vw_warp_forward", "scg_vw_warp_backward"])
 
 
 def _smooth(H, W, form):
@@ -631,20 +814,25 @@ def _lp_layer(cin, cout, h, w, pool):
     return Case(f"lp_conv3x3-{cin}-{cout}-{h}x{w}{'-pooled' if pool else ''}", run, ["scg_lp_conv3x3"])
 
 
-def _lp_metric(H, W):
+def _lp_metric(H, W, equal=False):
     def run(home):
         import lpips_refs as LR
         import test_gpu_lpips as T
         from scgaussian_amd import lpips
         lp = home(lpips.Lpips.from_state_dicts(*LR.state_dicts(T.WEIGHTS), device=DEV))      # (the weights are re-laid with torch.cat)
         x, y = LR.make_images(H, W, seed=H + W)
+        if equal:
+            y = x.copy()                                          # every difference of normalised features is exactly 0
         xd, yd = home(torch.from_numpy(x).to(DEV)), home(torch.from_numpy(y).to(DEV))
         value = lp(xd, yd)
         terms = lp.terms.clone()
+        if equal:
+            assert float(value) == 0.0 and not bool(terms.any())
         fx, fy = lp.features(xd, yd)
         head = lp.head(H, W)
         return dict(value=value, terms=terms, head=head, head_terms=lp.terms, fx=list(fx), fy=list(fy))
-    return Case(f"lp_forward-{H}x{W}", run, ["scg_lp_forward", "scg_lp_head"], not_passed={"scg_lp_head": {"features"}})
+    return Case(f"lp_forward-{H}x{W}{'-equal' if equal else ''}", run, ["scg_lp_forward", "scg_lp_head"],
+                not_passed={"scg_lp_head": {"features"}})
 
 
 # ---- PNG (png/scg_png.h) ----------------------------------------------------------------------------------------------------------------
@@ -665,6 +853,27 @@ def _png(gray):
         T.check_files(files, arrays, png.UP, gray, "guarded")
         return dict(files=files)                                  # (the buffer's gaps between the streams belong to nobody)
     return Case(f"png-{'rgb' if gray else 'gray'}", run, ["scg_png_encode"],
+                excused={"scg_png_encode": {"args.images_host": "host copy of the image table"}})
+
+
+def _png_edges(gray):
+    """1 x 1 alone (one chunk of two bytes), an all-zero image (the longest runs: a handful of tokens per chunk), and an odd-sized
+    image of more than one chunk whose last chunk is short; the files are the restatement's byte for byte."""
+    def run(home):
+        import test_gpu_png as T
+        from scgaussian_amd import png
+        rng = np.random.default_rng(3)
+        arrays = [np.full((1, 1), 7, np.uint8), np.zeros((37, 45, 3), np.uint8), np.zeros((1, 1, 3), np.uint8),
+                  T.noise(rng, 131, 251), T.smooth(87, 127, 3)]      # 131 x 252 = 33 012 and 87 x 382 = 33 234 bytes: 32 768 + a rest
+        out = {}
+        for name, part in (("one_pixel", arrays[:1]), ("batch", arrays[1:])):
+            imgs = [home(T._t(a)) for a in part]
+            plan = home(png.PngPlan([t.shape for t in imgs], DEV, png.UP, gray, own_inputs=False))
+            files = plan.encode(imgs).files()
+            T.check_files(files, part, png.UP, gray, "poisoned " + name)
+            out[name] = files
+        return out
+    return Case(f"png-edges-{'rgb' if gray else 'gray'}", run, ["scg_png_encode"],
                 excused={"scg_png_encode": {"args.images_host": "host copy of the image table"}})
 
 
@@ -709,7 +918,45 @@ def _absent_gradients(mode):
     return out | ({"dL_dcov3D_precomp"} if cov == "sr" else {"dL_dscales", "dL_drotations"})
 
 
-def _raster(mode, deg, P):
+BG_RASTER = (0.2, 0.4, 0.6)
+ONE_TILE = (1, 1)                                                 # the tile the "one_tile" scenes put every Gaussian into
+
+
+def _sparse_scene(kind, P, seed):
+    """(scene, camera) of the table's frame.  "random": the frame the older cases render.  "culled": the same Gaussians behind a
+    camera that looks the other way â€” every radius is 0, no tile has a list, the image is the background.  "one_tile": small
+    Gaussians whose centres lie in the middle of tile ONE_TILE â€” every other tile's list is empty."""
+    from scgaussian_amd import synthetic as syn
+    W, H = W_RASTER, H_RASTER
+    if kind == "random":
+        return syn.make_scene(P, W, H, seed=seed, log_scale_mean=-3.0), syn.orbit_camera(W, H, 8.0, 4.0, 7.0)
+    if kind == "culled":
+        return syn.make_scene(P, W, H, seed=seed, log_scale_mean=-3.0), syn.orbit_camera(W, H, 180.0, 0.0, 7.0, target=(0.0, 0.0, -7.0))
+    assert kind == "one_tile"
+    sc = syn.make_scene(P, W, H, seed=seed, log_scale_mean=-5.5)
+    g = torch.Generator().manual_seed(seed + 1)
+    px, py = (16.0 * t + 5.0 + 6.0 * torch.rand(P, generator=g) for t in ONE_TILE)      # 5 .. 11 pixels inside the tile
+    tany = math.tan(math.radians(50.0) / 2)
+    z = sc.means3D[:, 2]
+    sc.means3D[:, 0] = ((2 * px + 1) / W - 1) * (tany * W / H) * z
+    sc.means3D[:, 1] = ((2 * py + 1) / H - 1) * tany * z
+    return sc, syn.default_camera(W, H)
+
+
+def _assert_sparse(kind, color, depth, alpha, radii):
+    """What the module's own tests know of these frames: the background wherever no tile has a list."""
+    bg = torch.tensor(BG_RASTER, device=color.device)[:, None, None]
+    if kind == "culled":
+        assert not bool(radii.any()) and torch.equal(color, bg.expand_as(color)) and not bool(depth.any()) and not bool(alpha.any())
+    if kind == "one_tile":
+        outside = torch.ones(color.shape[-2:], dtype=torch.bool, device=color.device)
+        outside[16 * ONE_TILE[1]:16 * ONE_TILE[1] + 16, 16 * ONE_TILE[0]:16 * ONE_TILE[0] + 16] = False
+        assert bool((radii > 0).all()) and bool((radii <= 5).all()), radii.max()
+        assert torch.equal(color[:, outside], bg[:, 0].expand(3, int(outside.sum()))) and not bool(alpha[:, outside].any())
+        assert bool(alpha[:, ~outside].any())
+
+
+def _raster(mode, deg, P, scene="random"):
     def run(home):
         import parity_utils as pu
         import test_gpu_geometry_edges as TG
@@ -717,9 +964,8 @@ def _raster(mode, deg, P):
         from scgaussian_amd import rasterizer as R
         from scgaussian_amd import synthetic as syn
         W, H = W_RASTER, H_RASTER
-        sc = syn.make_scene(P, W, H, seed=P, log_scale_mean=-3.0)
-        cam = syn.orbit_camera(W, H, 8.0, 4.0, 7.0)
-        st = home(pu.hip_settings(cam, deg, (0.2, 0.4, 0.6)))
+        sc, cam = _sparse_scene(scene, P, P)
+        st = home(pu.hip_settings(cam, deg, BG_RASTER))
         leaves = {k: home(v.detach().to(DEV).contiguous().requires_grad_(True)) for k, v in pu.run_oracle_inputs(sc, cam, deg, 1.0, mode).items()}
         ups = [home(g.to(DEV)) for g in syn.make_upstream_grads(W, H, seed=P + 50)]
         ins = {k: v.detach() for k, v in leaves.items() if k != "means2D"}
@@ -730,6 +976,7 @@ def _raster(mode, deg, P):
                               prepare_backward=True)
         out.update(color=fs["color"], depth=fs["depth"], alpha=fs["alpha"], radii=fs["radii"], splats=fs["splats"], rects=fs["rects"],
                    depth_keys=fs["depth_keys"], clamped=fs["clamped"])
+        _assert_sparse(scene, fs["color"], fs["depth"], fs["alpha"], fs["radii"])
         g1 = R.backward_stages(st, fs["inputs"], fs, *ups, want_dsplats=True)
         records = g1.pop("dsplats")
         for k, v in g1.items():
@@ -748,73 +995,96 @@ def _raster(mode, deg, P):
         for _ in range(2):                                        # (the second forward has the first one's per-tile costs as its hint)
             c, radii, d, a = rast(means3D=leaves["means3D"], means2D=leaves["means2D"], opacities=leaves["opacities"], **kw)
         torch.autograd.backward([c, d, a], ups)
+        _assert_sparse(scene, c, d, a, radii)
         out.update(one_color=c, one_depth=d, one_alpha=a, one_radii=radii)
         for k, v in leaves.items():
             out["grad_" + k] = v.grad
+            if scene == "culled":                                 # every gradient row is written, and a culled Gaussian's is zero
+                assert v.grad is not None and not bool(v.grad.any()), k
+                assert not bool(out["staged_" + k].any()) and not bool(out["added_" + k].any()), k
+        if scene == "culled":
+            # no Gaussian at all, where the binding takes it (the staged forward; the operator itself refuses empty inputs):
+            # nothing is launched on the Gaussians, the image is the background
+            none = {k: v[:0] for k, v in ins.items()}
+            f0 = R.forward_stages(st, none["means3D"], none["opacities"], shs=none.get("shs"), colors_precomp=none.get("colors_precomp"),
+                                  scales=none.get("scales"), rotations=none.get("rotations"), cov3D_precomp=none.get("cov3D_precomp"))
+            _assert_sparse(scene, f0["color"], f0["depth"], f0["alpha"], f0["radii"])
+            out.update(none_color=f0["color"], none_depth=f0["depth"], none_alpha=f0["alpha"])
         return out
     absent = _absent_gradients(mode)
-    return Case(f"raster-{mode}-d{deg}-P{P}", run,
+    return Case(f"raster-{mode}-d{deg}-P{P}" + ("" if scene == "random" else "-" + scene), run,
                 ["scg_geometry_forward", "scg_geometry_backward", "scg_forward", "scg_backward"], excused=RASTER_EXCUSED,
                 not_passed={"scg_geometry_backward": absent, "scg_backward": absent, "scg_binning": {"keys_sorted"}},
                 fields={"scg_forward": ["frame.tile_cost_out"], "scg_backward": ["frame.bwd_cost_out"]}, close=_raster_comparator)
 
 
-def _model_path(nr, nb, deg):
+def _model_path(nr, nb, deg, scene="random"):
     def run(home):
         from scgaussian_amd import model_path as mp
         from scgaussian_amd import render as rmod
         from scgaussian_amd import synthetic as syn
         W, H, P = W_RASTER, H_RASTER, nr + nb
-        sc = syn.make_scene(P, W, H, seed=2 + P, log_scale_mean=-3.0)
+        sc, cam_cpu = _sparse_scene(scene, P, 2 + P)
         model = syn.make_raw_model(sc, ray_fraction=nr / P, seed=5)
         md = home(model.to(DEV))
         md.requires_grad_()
         md.active_sh_degree = deg
         assert (md.zval.shape[0], md.bg_xyz.shape[0]) == (nr, nb)
         act = mp.activate(**mp.tensors_of(md))
-        cam = home(syn.orbit_camera(W, H, -4.0, 2.0, 7.0).to(DEV))
-        bg = torch.tensor((0.1, 0.2, 0.3), device=DEV)
+        cam = home((syn.orbit_camera(W, H, -4.0, 2.0, 7.0) if scene == "random" else cam_cpu).to(DEV))
+        bg = torch.tensor((0.1, 0.2, 0.3) if scene == "random" else BG_RASTER, device=DEV)
         ups = [home(g.to(DEV)) for g in syn.make_upstream_grads(W, H, seed=5)]
         assert rmod.model_fast_path_available(md, rmod.PipelineParams())
         for _ in range(2):
             res = rmod.render(cam, md, rmod.PipelineParams(), bg)
         torch.autograd.backward([res["render"], res["rendered_depth"], res["rendered_alpha"]], ups)
+        _assert_sparse(scene, res["render"], res["rendered_depth"], res["rendered_alpha"], res["radii"])
         out = dict(render=res["render"], depth=res["rendered_depth"], alpha=res["rendered_alpha"], radii=res["radii"], act=list(act),
                    grad_means2D=res["viewspace_points"].grad)
         for n in ("zval", "features_dc", "features_rest", "opacity", "scaling", "rotation", "bg_xyz", "bg_features_dc",
                   "bg_features_rest", "bg_opacity", "bg_scaling", "bg_rotation"):
             if getattr(md, n).shape[0]:
                 out["grad_" + n] = getattr(md, n).grad
+                if scene == "culled":                             # every row of every raw-parameter gradient is written: zeros
+                    assert getattr(md, n).grad is not None and not bool(getattr(md, n).grad.any()), n
         return out
     fields = (["grads.ray." + f for f in ("zval", "features_dc", "features_rest", "opacity", "scaling", "rotation")] if nr else []) + \
         (["grads.bg." + f for f in ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation")] if nb else [])
-    return Case(f"model_path-{nr}+{nb}-d{deg}", run, ["scg_model_activate", "scg_forward_model", "scg_backward_model"],
+    return Case(f"model_path-{nr}+{nb}-d{deg}" + ("" if scene == "random" else "-" + scene), run,
+                ["scg_model_activate", "scg_forward_model", "scg_backward_model"],
                 excused=RASTER_EXCUSED, close=_raster_comparator,
                 fields={"scg_backward_model": fields + ["frame.bwd_cost_out"], "scg_forward_model": ["frame.tile_cost_out"]})
 
 
 CASES = (
     [_image_loss(s, lam) for s, lam in (((3, 1, 1), 0.2), ((3, 5, 7), 0.2), ((3, 33, 65), 1.0))]
-    + [_image_loss_pair(s) for s in ((3, 1, 1), (3, 33, 65))]
-    + [_match_loss(M) for M in (1, 37)]
+    + [_image_loss_pair(s) for s in ((3, 1, 1), (3, 33, 65))] + [_image_loss_pair((3, 33, 65), same=True)]
+    + [_match_loss(M) for M in (1, 37)] + [_match_loss_outside(37)]
     + [_knn(n) for n in (1, 4, 65, 257)]
     + [_sort(n) for n in (1, 255, 257)] + [_scan(n) for n in (1, 255, 257)]
-    + [_dtu(n) for n in (1, 63)]
-    + [_eval_view(False), _eval_view(True)]
-    + [_geocheck(3, 1, 1)]
-    + [_viz(H, W) for H, W in ((1, 1), (1, 3), (5, 7), (17, 65), (1, 1025))]
-    + [_densify(nr, nb) for nr, nb in ((1, 0), (33, 32), (129, 128))] + [_densify_stats(P) for P in (1, 257)]
-    + [_seed(N) for N in (1, 65, 257)]
-    + [_mono("two_views"), _mono("edge_scene")]
-    + [_matchpoint(N) for N in (1, 5, MP_T + 1)]
-    + [_ply(nr, nb) for nr, nb in ((1, 0), (0, 1), (PLY_T + 1, 3))]
+    + [_dtu(n) for n in (1, 63)] + [_dtu_empty(63)]
+    + [_eval_view(False), _eval_view(True), _eval_view(True, nan_depth=True)]
+    + [_geocheck(3, 1, 1), _geocheck_singular(3, 5, 7)]
+    + [_viz(H, W) for H, W in ((1, 1), (1, 3), (5, 7), (17, 65), (1, 1025))] + [_viz(5, 7, all_nan=True)]
+    + [_densify(nr, nb) for nr, nb in ((1, 0), (33, 32), (129, 128))] + [_densify(33, 32, "none"), _densify(33, 32, "prune_all")]
+    + [_densify_stats(P) for P in (1, 257)]
+    + [_seed(N) for N in (1, 65, 257)] + [_seed_edges()]
+    + [_mono("two_views"), _mono("edge_scene")]      # (edge_scene holds the segments without a valid match: pair (2, 4), pair (1, 3) but one)
+    + [_matchpoint(N) for N in (1, 5, MP_T + 1)] + [_matchpoint(5, empty_view=True)]
+    + [_ply(nr, nb) for nr, nb in ((1, 0), (0, 1), (PLY_T + 1, 3), (33, 0))]
     + [_resize(*a, c) for a in ((1, 7, 3, 5), (5, 7, 3, 5), (17, 7, 6, 5), (7, 5, 20, 9), (1, 1, 3, 2)) for c in (0, 3)]
-    + [_warp(3, 3, 3), _warp(VW_T + 1, VW_T - 1, 3), _warp(7, 9, 1)] + [_smooth(2, 2, "chw"), _smooth(1, 1, "none")]
+    + [_resize(*a, c, float_from="empty") for a in ((7, 5, 7, 5), (2, 2, 5, 5)) for c in (0, 3)]      # the copy, an upscale
+    + [_warp(3, 3, 3), _warp(VW_T + 1, VW_T - 1, 3), _warp(7, 9, 1)] + [_warp_blind("unseen"), _warp_blind("masked")]
+    + [_smooth(2, 2, "chw"), _smooth(1, 1, "none"), _smooth(1, 9, "chw")]
     + [_lp_layer(3, 64, 1, LP_TM + 1, False), _lp_layer(64, 128, 3, 2 * LP_TM + 3, True)] + [_lp_metric(16, 16), _lp_metric(17, 16)]
-    + [_png(True), _png(False)]
+    + [_lp_metric(16, 16, equal=True)]
+    + [_png(True), _png(False)] + [_png_edges(True), _png_edges(False)]
     + [_raster("sh_sr", 0, 1), _raster("sh_sr", 3, 63), _raster("col_cov", 3, 65), _raster("sh_sr", 0, 257), _raster("sh_sr", 3, 257),
        _raster("col_cov", 3, 257)]
+    + [_raster("sh_sr", 3, 65, "culled"), _raster("col_cov", 3, 65, "culled"), _raster("sh_sr", 3, 65, "one_tile"),
+       _raster("col_cov", 3, 65, "one_tile")]
     + [_model_path(1, 0, 0), _model_path(0, 1, 3), _model_path(61, 59, 3), _model_path(64, 65, 0)]
+    + [_model_path(33, 32, 3, "culled"), _model_path(33, 32, 3, "one_tile")]
 )
 
 
@@ -833,6 +1103,7 @@ def test_the_helper_sees_device_memory():
             idx = torch.arange(4, dtype=torch.int32, device=DEV)
             assert all(reg.covers(x.data_ptr()) for x in (t, u, idx)) and not reg.covers(torch.randn(4, device=DEV).data_ptr())
             assert reg.check() == []
+            assert bool(u.eq(0xFF if fill == FILL_A else 0x3C).all())      # the body of a device `empty` reads back as the fill
             torch.as_strided(t, (1,), (1,), t.storage_offset() + 5).fill_(7.5)
             torch.as_strided(idx, (1,), (1,), idx.storage_offset() - 1).fill_(9)
             torch.cuda.synchronize()
@@ -844,7 +1115,10 @@ def test_the_helper_sees_device_memory():
 
 # ---- coverage: every compute entry of every header is reached by a case above, or named here with its reason --------------------------
 
-# families whose own edge tests already place guard values around their buffers
+# families whose own edge tests already place guard values around their buffers â€” and start what their runners hand over as
+# scratch from both fills of the helper (test_what_the_scratch_held_... / _workspace_held_... in test_gpu_binning_edges.py,
+# test_what_the_buffers_held_... in test_gpu_blend_edges.py, test_4f_... in test_gpu_init_stage_edges.py).  scg_adam_step has no
+# scratch but `ws`, which is zero by contract (zeroed once, kept) and stays zero in its runner
 ALREADY_GUARDED = {
     "scg_binning": "tests/test_gpu_binning_edges.py", "scg_blend_forward": "tests/test_gpu_blend_edges.py",
     "scg_blend_backward": "tests/test_gpu_blend_edges.py", "scg_init_stage_run": "tests/test_gpu_init_stage_edges.py",

@@ -286,6 +286,39 @@ def test_4e_a_launch_past_the_step_limit_is_refused(fe):
     assert st.iteration == 2
 
 
+def test_4f_what_the_partial_sums_held_before_a_launch_changes_no_bit(fx):
+    """InitStage takes its partial sums, and evaluate() its loss_state and gradient, from torch.empty: under the two fills of
+    tests/guarded_alloc.py those buffers start as NaN and as 0.0115.  One stage per path of the kernel — the evaluation alone
+    (n_steps = 0), a launch across the 64-row flush with the loss rows recorded, one that ends off the tile, and the same launches
+    without a partials buffer — must leave the same bits in the state, in every row of partial sums and in evaluate()'s outputs as
+    with buffers that start from whatever the allocator held."""
+    import guarded_alloc as G
+
+    def path(record):
+        st, _ = _stage(fx, "A", record_losses=record)
+        first = [t.clone() for t in st.evaluate()]
+        st.run(65)
+        st.lr *= 0.5
+        st.run(3)
+        torch.cuda.synchronize()
+        out = dict(_state(st), it0_loss_state=first[0], it0_grad=first[1], it0_partials=first[2])
+        if record:
+            out.update(partials=st.partials(), losses=st.losses())
+        return {k: v.cpu() for k, v in out.items()}
+
+    for record in (True, False):
+        runs = {}
+        for fill in (G.FILL_A, G.FILL_B):
+            with G.guarded(fill) as reg:
+                runs[fill] = path(record)
+                assert any(a.module == "scgaussian_amd.init_stage" for a in reg.allocations)      # the stage's own torch.empty calls
+            assert reg.check() == []
+        plain = path(record)
+        for k in plain:
+            assert G.same_bits(runs[G.FILL_A][k], runs[G.FILL_B][k]) and G.same_bits(runs[G.FILL_A][k], plain[k]), (record, k)
+        assert not record or (plain["partials"].shape == (68, 11) and bool(torch.isfinite(plain["partials"]).all()))
+
+
 # ------------------------------------------------------------------------------------------------- (5) the best-state rule
 
 @pytest.mark.parametrize("iteration", [0, 1, 2])

@@ -1,6 +1,9 @@
 """The teeth of tests/guarded_alloc.py, on CPU tensors: a stand-in "kernel" written in torch writes or reads through a raw, larger
-view of the same storage, and the helper has to say where.  tests/test_gpu_guard_bands.py relies on every property held here."""
+view of the same storage, and the helper has to say where; and stand-in "entries" that read a scratch word nobody wrote, leave an
+output's tail unwritten or index through an unwritten word give different results under the two fills, because the body of an
+empty / empty_like request starts from the fill.  tests/test_gpu_guard_bands.py relies on every property held here."""
 import ctypes as C
+import math
 
 import pytest
 import torch
@@ -231,6 +234,176 @@ def test_rehome_moves_tensors_made_by_other_means():
         assert holder.opt.param_groups[0]["params"][0] is q and holder.twice[0] is q and list(holder.opt.state) == [q]
         assert all(reg.covers(holder.opt.state[q][k].data_ptr()) for k in ("exp_avg", "exp_avg_sq"))
     assert reg.check() == []
+
+
+# ---- poison: the body of an empty / empty_like request starts from the fill
+
+ALL_DTYPES = DTYPES + [torch.bool, torch.bfloat16]
+
+
+def poison_of(dtype, fill, n):
+    """The n elements a poisoned body of `dtype` holds under `fill`, built here from the rule's own words."""
+    if dtype == torch.bool:
+        return torch.tensor([fill == FILL_A] * n, dtype=torch.bool)
+    if dtype in (torch.int16, torch.int32, torch.int64):
+        return torch.tensor([{FILL_A: 1, FILL_B: 2}[fill]] * n, dtype=dtype)
+    byte = {FILL_A: 0xFF, FILL_B: 0x3C}[fill]
+    return torch.tensor([byte] * (n * dtype.itemsize), dtype=torch.uint8).view(dtype)
+
+
+@pytest.mark.parametrize("fill", [FILL_A, FILL_B])
+@pytest.mark.parametrize("dtype", ALL_DTYPES, ids=str)
+def test_an_empty_body_reads_back_as_the_fill(dtype, fill):
+    with guarded(fill, CPU) as reg:
+        src = G._REAL["zeros"](4, 6, dtype=dtype).t()              # (empty_like keeps the transposed strides)
+        made = [torch.empty(7, dtype=dtype), torch.empty((3, 5), dtype=dtype), torch.empty_like(src),
+                torch.empty_like(G._REAL["zeros"](9), dtype=dtype), torch.empty(0, dtype=dtype)]
+        for t in made:
+            assert reg.covers(t.data_ptr()) or t.numel() == 0
+            assert G.same_bits(t.contiguous().reshape(-1), poison_of(dtype, fill, t.numel())), (dtype, fill, t.shape)
+        assert made[2].stride() == src.stride()
+        # what was asked for is what the body holds, and a rehomed tensor is its source: none of them is poisoned
+        three = 1 if dtype == torch.bool else 3
+        assert torch.zeros(7, dtype=dtype).eq(0).all() and torch.zeros_like(src).eq(0).all()
+        assert torch.ones(7, dtype=dtype).eq(1).all() and torch.full((7,), three, dtype=dtype).eq(three).all()
+        assert torch.ones_like(src).eq(1).all() and torch.full_like(src, three).eq(three).all()
+        assert torch.tensor([0, 1, 0], dtype=dtype).tolist() == [0, 1, 0] and torch.arange(3).tolist() == [0, 1, 2]
+        moved = reg.rehome(G._REAL["zeros"](5, dtype=dtype))
+        assert reg.covers(moved.data_ptr()) and moved.eq(0).all() and reg.like(src).shape == src.shape
+    assert reg.check() == []                                     # the poison stops where the body ends
+    if dtype.is_floating_point and fill == FILL_A:
+        assert made[0].isnan().all()                             # every floating format reads all-ones bytes as a NaN
+    if dtype == torch.float32 and fill == FILL_B:
+        assert ((made[0] - 0.0115).abs() < 1e-4).all()
+
+
+def test_poison_off_leaves_bodies_alone(monkeypatch):
+    marker = G._REAL["full"]((1 << 16,), 0x5A, dtype=torch.uint8)
+
+    real = G._REAL["empty"]
+
+    def recycled(*args, **kwargs):                               # the allocator's leftovers, made visible: every raw buffer is 0x5A
+        if str(kwargs.get("device")) == "meta":                     # (the patched names ask a meta tensor for the shape and strides)
+            return real(*args, **kwargs)
+        assert kwargs["dtype"] == torch.uint8
+        return marker[:args[0]].clone()
+    monkeypatch.setitem(G._REAL, "empty", recycled)
+    for fill in (FILL_A, FILL_B):
+        with guarded(fill, CPU, poison=False) as reg:
+            assert not reg.poison
+            for dtype in (torch.float32, torch.uint8, torch.int32):
+                for t in (torch.empty(6, dtype=dtype), torch.empty_like(G._REAL["zeros"](6, dtype=dtype))):
+                    assert t.view(torch.uint8).eq(0x5A).all() and reg.covers(t.data_ptr())
+            assert torch.zeros(3).eq(0).all()
+        assert reg.check() == []                                 # (the bands are filled as ever)
+        with guarded(fill, CPU) as reg:
+            assert reg.poison and not torch.empty(6, dtype=torch.uint8).eq(0x5A).any()
+
+
+@pytest.mark.parametrize("fill", [FILL_A, FILL_B])
+def test_a_pinned_empty_is_poisoned_and_lies_in_no_body(fill, monkeypatch):
+    """Pinned memory needs a GPU runtime, so the unpatched names are stood in for here by ones that accept pin_memory and hand out
+    ordinary host memory holding a marker: the patched name has to pass the request through (no body, no bands) and fill it."""
+    asked = []
+
+    def stand_in(real):
+        def fn(*args, **kwargs):
+            asked.append(bool(kwargs.pop("pin_memory", False)))
+            return real(*args, **kwargs).view(torch.uint8).fill_(0x5A).view(kwargs.get("dtype") or torch.float32) if asked[-1] \
+                else real(*args, **kwargs)
+        return fn
+    monkeypatch.setitem(G._REAL, "empty", stand_in(G._REAL["empty"]))
+    monkeypatch.setitem(G._REAL, "empty_like", stand_in(G._REAL["empty_like"]))
+    monkeypatch.setitem(G._REAL, "zeros", stand_in(G._REAL["zeros"]))
+    for devices in (CPU, ("cuda",)):                             # a host buffer: poisoned whichever device type is guarded
+        del asked[:]
+        with guarded(fill, devices) as reg:
+            before = len(reg.allocations)
+            made = [torch.empty(9, dtype=torch.uint8, pin_memory=True), torch.empty((3, 2), dtype=torch.int32, pin_memory=True),
+                    torch.empty(4, dtype=torch.float32, pin_memory=True),
+                    torch.empty_like(G._REAL["zeros"](5, dtype=torch.float32), pin_memory=True)]
+            kept = torch.zeros(4, dtype=torch.uint8, pin_memory=True)
+            assert len(reg.allocations) == before and not any(reg.covers(t.data_ptr()) for t in made)
+        assert sum(asked) == 5                                   # every pinned request reached the unpatched name as a pinned one
+        for t in made:
+            assert G.same_bits(t.reshape(-1), poison_of(t.dtype, fill, t.numel())), (t.dtype, fill)
+        assert kept.eq(0x5A).all()                               # not an `empty`: passed through as it came
+        with guarded(fill, devices, poison=False):
+            assert torch.empty(9, dtype=torch.uint8, pin_memory=True).eq(0x5A).all()
+
+
+# Three toy "entries" in plain torch, each with one of the faults the poison is for; `scratch` and `out` come from torch.empty, as in
+# the bindings.  tests/test_gpu_guard_bands.py compares its runs with G.same_bits, the comparison used here.
+
+def _sums_a_scratch_it_never_wrote(x):
+    scratch = torch.empty(4, dtype=torch.float32)
+    scratch[:2] = x[:2]                                          # two of the four partial sums are written ...
+    return dict(total=scratch.sum())                             # ... and four are read
+
+
+def _leaves_an_output_tail_unwritten(x):
+    out = torch.empty_like(x)
+    out[:-1] = x[:-1] * 2                                        # the "nothing to do" path forgets the last element
+    return dict(out=out)
+
+
+def _gathers_through_an_unwritten_index(x):
+    index = torch.empty(3, dtype=torch.int32)
+    index[:2] = torch.tensor([0, 3], dtype=torch.int32)          # the third word is whatever was there: 1 or 2, inside the table
+    return dict(picked=x[index.long()])
+
+
+def _honest(x):
+    scratch, out = torch.empty(4, dtype=torch.float32), torch.empty_like(x)
+    scratch[:] = x[:4]
+    out[:] = x * 2
+    return dict(total=scratch.sum(), out=out)
+
+
+@pytest.mark.parametrize("entry", [_sums_a_scratch_it_never_wrote, _leaves_an_output_tail_unwritten,
+                                   _gathers_through_an_unwritten_index], ids=lambda f: f.__name__.strip("_"))
+def test_a_dependence_on_unwritten_memory_differs_between_the_fills(entry):
+    x = torch.tensor([1.0, 2.0, 3.0, 4.0, 5.0])
+    runs = {}
+    for fill in (FILL_A, FILL_B):
+        with guarded(fill, CPU) as reg:
+            runs[fill] = entry(reg.rehome(x.clone()))
+        assert reg.check() == []                                 # nothing outside a body was touched: only the A/B comparison sees it
+    assert not G.same_bits(runs[FILL_A], runs[FILL_B])
+    if entry is _gathers_through_an_unwritten_index:             # the fills are valid indices: the read stayed inside its table
+        assert runs[FILL_A]["picked"].tolist() == [1.0, 4.0, 2.0] and runs[FILL_B]["picked"].tolist() == [1.0, 4.0, 3.0]
+    if entry is _sums_a_scratch_it_never_wrote:
+        assert math.isnan(float(runs[FILL_A]["total"])) and abs(float(runs[FILL_B]["total"]) - (3 + 2 * 0.0115)) < 1e-3
+    off = {}
+    for fill in (FILL_A, FILL_B):                                # without the poison both runs start from the same bytes: nothing shows
+        with guarded(fill, CPU, poison=False) as reg:
+            reg.allocate = _from_zeros(reg.allocate)
+            off[fill] = entry(reg.rehome(x.clone()))
+    assert G.same_bits(off[FILL_A], off[FILL_B])
+
+
+def _from_zeros(allocate):
+    """Registry.allocate with the body cleared: a recycled block that happens to hold zeros, the case that hides these faults."""
+    def fn(*args, **kwargs):
+        return allocate(*args, **kwargs).zero_()
+    return fn
+
+
+def test_an_entry_that_writes_what_it_reads_is_the_same_under_both_fills():
+    x = torch.tensor([1.0, 2.0, 3.0, 4.0, 5.0])
+    runs = {}
+    for fill in (FILL_A, FILL_B):
+        with guarded(fill, CPU) as reg:
+            runs[fill] = _honest(reg.rehome(x.clone()))
+    assert G.same_bits(runs[FILL_A], runs[FILL_B]) and float(runs[FILL_A]["total"]) == 10.0
+
+
+def test_same_bits_tells_what_equality_does_not():
+    nan, t = float("nan"), torch.tensor
+    assert G.same_bits(nan, nan) and G.same_bits(t([nan, 1.0]), t([nan, 1.0])) and G.same_bits({"a": [t([1]), b"x"]}, {"a": [t([1]), b"x"]})
+    assert not G.same_bits(t([0.0]), t([-0.0])) and not G.same_bits(t([1]), t([1], dtype=torch.int32))
+    assert not G.same_bits(t([1.0, 2.0]), t([[1.0, 2.0]])) and not G.same_bits({"a": 1}, {"b": 1}) and not G.same_bits([1], [1, 2])
+    assert not G.same_bits(b"ab", b"ac") and not G.same_bits(t([nan]), t([1.0]))
 
 
 # ---- traced()
