@@ -227,9 +227,13 @@ class ScgError(RuntimeError):
     pass
 
 
-def open_library(path: str) -> C.CDLL:
-    """dlopen + type + version-check one build of the library (the product loads exactly one: load(); tools/ab_inproc.py opens
-    several variants side by side for same-process A/B runs)."""
+def open_library(path: str, symbols=None, version=("scg_abi_version", ABI_VERSION), size_checked=None, name="library") -> C.CDLL:
+    """dlopen + type + version-check one library.  The defaults are the main library's (the product loads exactly one build of
+    it: load(); tools/ab_inproc.py opens several variants side by side for same-process A/B runs).  A side binding passes its own
+    SYMBOLS, (version query, value), {size query: structs} and the file name its messages use.  A size query that takes no
+    argument reports its one struct."""
+    symbols = SYMBOLS if symbols is None else symbols
+    size_checked = SIZE_CHECKED if size_checked is None else size_checked
     if not os.path.exists(path):
         raise ScgError(f"{path} not found: the HIP extension is required (python -m scgaussian_amd.build); "
                        "there is no CPU fallback")
@@ -237,21 +241,30 @@ def open_library(path: str) -> C.CDLL:
         lib = C.CDLL(path)
     except OSError as e:  # pragma: no cover
         raise ScgError(f"cannot load {path}: {e}") from e
-    for name, (res, args) in SYMBOLS.items():
+    for sym, (res, args) in symbols.items():
         try:
-            fn = getattr(lib, name)
+            fn = getattr(lib, sym)
         except AttributeError as e:
-            raise ScgError(f"{path} does not export {name}") from e
+            raise ScgError(f"{path} does not export {sym}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.scg_abi_version() != ABI_VERSION:
-        raise ScgError(f"ABI version mismatch: library {lib.scg_abi_version()} != binding {ABI_VERSION}")
-    for query, structs in SIZE_CHECKED.items():
+    query, want = version
+    if getattr(lib, query)() != want:
+        raise ScgError(f"ABI version mismatch: {name} {getattr(lib, query)()} != binding {want}")
+    for query, structs in size_checked.items():
+        fn = getattr(lib, query)
         for which, struct in enumerate(structs):
-            if getattr(lib, query)(which) != C.sizeof(struct):
-                raise ScgError(f"struct layout mismatch: {struct.__name__} is {getattr(lib, query)(which)} bytes in the library, "
+            got = fn(which) if fn.argtypes else fn()
+            if got != C.sizeof(struct):
+                raise ScgError(f"struct layout mismatch: {struct.__name__} is {got} bytes in the library, "
                                f"{C.sizeof(struct)} in the binding")
     return lib
+
+
+def raise_last_error(rc: int, what: str, last_error) -> None:
+    """The ScgError of a non-zero return code of `what`, with the text of the library's own *_last_error function."""
+    msg = last_error()
+    raise ScgError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
 
 
 def load() -> C.CDLL:
@@ -265,8 +278,7 @@ def load() -> C.CDLL:
 
 def check(rc: int, what: str) -> None:
     if rc != 0:
-        msg = load().scg_last_error()
-        raise ScgError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
+        raise_last_error(rc, what, load().scg_last_error)
 
 
 def ptr(t) -> int:

@@ -2,7 +2,7 @@
 
 A second library next to libscg_raster.so with a version and an error string of its own; the raw model it reads and writes is
 _lib.ScgModel.  As there: a missing library raises, there is no CPU or PyTorch stand-in for a kernel.
-tests/test_ply_cpu.py holds SYMBOLS, the struct and the constants to the header's text.
+tests/test_ply_cpu.py holds SYMBOLS, the struct and the constants to the header's text (tests/abi_compare.py check_side_library).
 """
 from __future__ import annotations
 
@@ -11,7 +11,7 @@ import os
 
 import torch  # noqa: F401  (first, so that torch's HIP runtime is the one the library binds to)
 
-from ._lib import ScgError, ScgModel
+from ._lib import ScgModel, open_library, raise_last_error
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libscg_io.so")
@@ -26,6 +26,8 @@ class ScgPlyLayout(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("ray_offset", "ray_bytes", "bg_offset", "bg_bytes", "color_offset", "color_bytes",
                                           "total")]
 
+
+STRUCTS = (ScgPlyLayout,)           # the one scg_ply_layout_bytes() reports
 
 _P = C.c_void_p
 SYMBOLS = {
@@ -45,30 +47,10 @@ def load() -> C.CDLL:
     """Load (once), type and version-check the library.  Raises ScgError when it is absent (python -m scgaussian_amd.build)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ScgError(f"{LIB_PATH} not found: the HIP extension is required (python -m scgaussian_amd.build); "
-                           "there is no CPU fallback")
-        try:
-            lib = C.CDLL(LIB_PATH)
-        except OSError as e:  # pragma: no cover
-            raise ScgError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in SYMBOLS.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise ScgError(f"{LIB_PATH} does not export {name}") from e
-            fn.restype = res
-            fn.argtypes = args
-        if lib.scg_io_abi_version() != ABI_VERSION:
-            raise ScgError(f"ABI version mismatch: libscg_io.so {lib.scg_io_abi_version()} != binding {ABI_VERSION}")
-        if lib.scg_ply_layout_bytes() != C.sizeof(ScgPlyLayout):
-            raise ScgError(f"struct layout mismatch: ScgPlyLayout is {lib.scg_ply_layout_bytes()} bytes in the library, "
-                           f"{C.sizeof(ScgPlyLayout)} in the binding")
-        _lib = lib
+        _lib = open_library(LIB_PATH, SYMBOLS, ("scg_io_abi_version", ABI_VERSION), {"scg_ply_layout_bytes": STRUCTS}, "libscg_io.so")
     return _lib
 
 
 def check(rc: int, what: str) -> None:
     if rc != 0:
-        msg = load().scg_io_last_error()
-        raise ScgError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
+        raise_last_error(rc, what, load().scg_io_last_error)

@@ -2,7 +2,8 @@
 backward, on the GPU.
 
 A fifth library next to libscg_raster.so with a version and an error string of its own.  As there: a missing library raises, there
-is no quiet stand-in for a kernel.  tests/test_virtualwarp_cpu.py holds SYMBOLS and the constants to the header's text.
+is no quiet stand-in for a kernel.  tests/test_virtualwarp_cpu.py holds SYMBOLS and the constants to the header's text (tests/abi_compare.py
+check_side_library).
 """
 from __future__ import annotations
 
@@ -11,7 +12,7 @@ import os
 
 import torch  # noqa: F401  (first, so that torch's HIP runtime is the one the library binds to)
 
-from ._lib import ScgError
+from ._lib import open_library, raise_last_error
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libscg_vw.so")
@@ -41,27 +42,10 @@ def load() -> C.CDLL:
     """Load (once), type and version-check the library.  Raises ScgError when it is absent (python -m scgaussian_amd.build)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ScgError(f"{LIB_PATH} not found: the HIP extension is required (python -m scgaussian_amd.build); "
-                           "there is no CPU fallback")
-        try:
-            lib = C.CDLL(LIB_PATH)
-        except OSError as e:  # pragma: no cover
-            raise ScgError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in SYMBOLS.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise ScgError(f"{LIB_PATH} does not export {name}") from e
-            fn.restype = res
-            fn.argtypes = args
-        if lib.scg_vw_abi_version() != ABI_VERSION:
-            raise ScgError(f"ABI version mismatch: libscg_vw.so {lib.scg_vw_abi_version()} != binding {ABI_VERSION}")
-        _lib = lib
+        _lib = open_library(LIB_PATH, SYMBOLS, ("scg_vw_abi_version", ABI_VERSION), {}, "libscg_vw.so")
     return _lib
 
 
 def check(rc: int, what: str) -> None:
     if rc != 0:
-        msg = load().scg_vw_last_error()
-        raise ScgError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
+        raise_last_error(rc, what, load().scg_vw_last_error)

@@ -1,20 +1,19 @@
-"""Build libscg_raster.so (the C-ABI HIP library), libscg_io.so (scene files, IO_SOURCES), libscg_img.so (camera images,
-IMG_SOURCES), libscg_mp.so (the init stage's snapshot, MP_SOURCES) and libscg_vw.so (the virtual-view warp loss and the depth
-smoothness with their backwards, VW_SOURCES) and libscg_lp.so (the LPIPS metric: VGG16 on the fp32 matrix pipe, LP_SOURCES) and libscg_png.so (PNG files' zlib streams, PNG_SOURCES) in-tree
-with hipcc for gfx950.
+"""Build the HIP libraries in-tree with hipcc for gfx950: libscg_raster.so (SOURCES) and, behind it, one side library per entry
+of SIDE_LIBRARIES, each with a header directory, an ABI version and an error string of its own.
 
     python -m scgaussian_amd.build [--force] [--verbose]
 
-hipcc cross-compiles without a GPU.  The .so is git-ignored but travels to the GPU box with the
-gpurun snapshot.  geometry.hip is compiled with -ffp-contract=off (bit-exact tile assignment).
-optim.hip and initstage.hip are too: Adam in torch's order with one rounding per operation (bits may differ from torch's where
-torch fuses).  So are densify.hip (the clone's xyz, the / 1.6) and
-seed.hip (the seeded points) and evalview.hip (the evaluation's masked images and error map) and geocheck.hip (fp64 as numpy rounds
-it) and depthviz.hip (the percentile's interpolation and the colour index as numpy and matplotlib round them) and mono.hip (the
-scene setup's sampler in fp32 and its ray chain in fp64, operation by operation) and plypack.hip of the second library (the saved
-position and the colour bytes) and matchpoint.hip of the fourth (the snapshot's positions, depths and normalised planes) and virtualwarp.hip of the fifth (the projection, the
-sampler and the window statistics, one rounding per operation).  The 8-bit quantiser
-the image kernels share (csrc/pixel_rules.h) turns contraction off in its own body and does not depend on the flag.
+    libscg_io.so    include/io    scene files (save_ply / load_ply)
+    libscg_img.so   include/img   camera images (Pillow's bicubic resize)
+    libscg_mp.so    include/mp    the init stage's snapshot (save_ply_at_matchpoint)
+    libscg_vw.so    include/vw    the virtual-view warp loss and the depth smoothness, forward and backward
+    libscg_lp.so    include/lp    the LPIPS metric (VGG16 on the fp32 matrix pipe)
+    libscg_png.so   include/png   PNG files' zlib streams
+
+hipcc cross-compiles without a GPU; the libraries are git-ignored.  A source whose results are held to another
+implementation's bits is compiled with -ffp-contract=off, one rounding per operation: the comment next to each such source in the
+tables says what is held to what.  The 8-bit quantiser the image kernels share (csrc/pixel_rules.h) turns contraction off in its
+own body and does not depend on the flag.
 """
 from __future__ import annotations
 
@@ -30,12 +29,6 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 OBJ_DIR = os.path.join(CSRC, "build")
 LIB_PATH = os.path.join(HERE, "libscg_raster.so")
-IO_LIB_PATH = os.path.join(HERE, "libscg_io.so")
-IMG_LIB_PATH = os.path.join(HERE, "libscg_img.so")
-MP_LIB_PATH = os.path.join(HERE, "libscg_mp.so")
-VW_LIB_PATH = os.path.join(HERE, "libscg_vw.so")
-LP_LIB_PATH = os.path.join(HERE, "libscg_lp.so")
-PNG_LIB_PATH = os.path.join(HERE, "libscg_png.so")
 EXPORTS_MAP = os.path.join(CSRC, "exports.map")           # global: scg_*; local: everything else
 
 ARCH = "gfx950"
@@ -43,7 +36,7 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=
           "-Wno-unused-function", "-I", INCLUDE]
 SOURCES = {
     "api.hip": [],
-    "geometry.hip": ["-ffp-contract=off"],
+    "geometry.hip": ["-ffp-contract=off"],        # bit-exact tile assignment
     "binning.hip": [],
     "binning_tiles.hip": [],
     # measured (tools/probes/valu_rate.hip): v_pk_*_f32 costs 1.67 issue slots, so the SLP vectoriser's packing of the
@@ -63,36 +56,40 @@ SOURCES = {
     "mono.hip": ["-ffp-contract=off"],            # create_from_mono (scg_mono.h): torch's grid_sample in fp32 and the ray chain in fp64, none fused
     "depthviz.hip": ["-ffp-contract=off"],        # depth colour maps and video frames (scg_viz.h): numpy's percentile, matplotlib's Normalize
 }
-# The second library, libscg_io.so (include/io/scg_ply.h): scene files.  Its entry points are not part of libscg_raster.so's ABI.
-IO_SOURCES = {
-    "plypack.hip": ["-ffp-contract=off"],         # save_ply / load_ply: x = rayo + rayd * zval and the colour bytes, one rounding per operation
+# The side libraries: short name -> (header directory under include/, {source: extra flags}).  The library is libscg_<name>.so;
+# its entry points are not part of libscg_raster.so's ABI.  The same COMMON flags, the same export map, no variants.
+SIDE_LIBRARIES = {
+    "io": ("io", {      # include/io/scg_ply.h
+        "plypack.hip": ["-ffp-contract=off"],     # save_ply / load_ply: x = rayo + rayd * zval and the colour bytes, one rounding per operation
+    }),
+    "img": ("img", {    # include/img/scg_resample.h
+        "resample.hip": [],                       # integer arithmetic; its one float operation (byte / 255) is an explicitly rounded division
+    }),
+    "mp": ("mp", {      # include/mp/scg_matchpoint.h
+        "matchpoint.hip": ["-ffp-contract=off"],  # xyz = rays_o + rays_d * z, depth = z * cam_z, (d - min) / (max - min): one rounding per operation
+    }),
+    "vw": ("vw", {      # include/vw/scg_virtualwarp.h
+        "virtualwarp.hip": ["-ffp-contract=off"],  # the warp, torch's bilinear sampler and the 5x5 statistics: every product and sum rounded on its own
+    }),
+    "lp": ("lp", {      # include/lp/scg_lpips.h
+        "lpips.hip": [],                          # its convolution sums are explicit fma chains (the fp32 MFMA, fmaf); the file turns contraction off for the rest
+    }),
+    "png": ("png", {    # include/png/scg_png.h
+        "pngpack.hip": [],                        # integer arithmetic only
+    }),
 }
-# The third library, libscg_img.so (include/img/scg_resample.h): the camera images' resize.  Integer arithmetic; its one float
-# operation (byte / 255) is an explicitly rounded division, so it needs no flag.
-IMG_SOURCES = {
-    "resample.hip": [],
-}
-# The fourth library, libscg_mp.so (include/mp/scg_matchpoint.h): save_ply_at_matchpoint.
-MP_SOURCES = {
-    "matchpoint.hip": ["-ffp-contract=off"],      # xyz = rays_o + rays_d * z, depth = z * cam_z, (d - min) / (max - min): one rounding per operation
-}
-# The fifth library, libscg_vw.so (include/vw/scg_virtualwarp.h): get_virtual_warp_loss and get_smooth_loss, forward and backward.
-VW_SOURCES = {
-    "virtualwarp.hip": ["-ffp-contract=off"],     # the warp, torch's bilinear sampler and the 5x5 statistics: every product and sum rounded on its own
-}
-# The sixth library, libscg_lp.so (include/lp/scg_lpips.h): the LPIPS metric.  Its convolution sums are explicit fma chains (the
-# fp32 MFMA, fmaf), and the file turns contraction off for the rest, so it needs no flag.
-LP_SOURCES = {
-    "lpips.hip": [],
-}
-# The seventh library, libscg_png.so (include/png/scg_png.h): PNG files' zlib streams.  Integer arithmetic only: no flag.
-PNG_SOURCES = {
-    "pngpack.hip": [],
-}
-HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "*.h"))) + \
-    sorted(glob.glob(os.path.join(INCLUDE, "io", "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "img", "*.h"))) + \
-    sorted(glob.glob(os.path.join(INCLUDE, "mp", "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "vw", "*.h"))) + \
-    sorted(glob.glob(os.path.join(INCLUDE, "lp", "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "png", "*.h")))                                                # every object depends on all
+
+
+def side_library(key: str):
+    """(path of libscg_<key>.so, its {source: extra flags}) of one entry of SIDE_LIBRARIES."""
+    return os.path.join(HERE, f"libscg_{key}.so"), SIDE_LIBRARIES[key][1]
+
+
+def _h(*parts):
+    return sorted(glob.glob(os.path.join(*parts, "*.h")))
+
+
+HEADERS = _h(CSRC) + _h(INCLUDE) + [h for d, _ in SIDE_LIBRARIES.values() for h in _h(INCLUDE, d)]    # every object depends on all
 
 
 def _hipcc() -> str:
@@ -145,7 +142,9 @@ def _link(hipcc: str, lib_path: str, objs, verbose: bool) -> None:
     subprocess.run(cmd, check=True)
 
 
-def _build_side(sources, lib_path: str, force: bool, verbose: bool) -> str:
+def build_side(key: str, force: bool = False, verbose: bool = False) -> str:
+    """libscg_<key>.so from its entry of SIDE_LIBRARIES."""
+    lib_path, sources = side_library(key)
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
     objs, rebuilt = [], False
@@ -158,40 +157,10 @@ def _build_side(sources, lib_path: str, force: bool, verbose: bool) -> str:
     return lib_path
 
 
-def build_io(force: bool = False, verbose: bool = False) -> str:
-    """libscg_io.so from IO_SOURCES: the same flags, the same export map, no variants."""
-    return _build_side(IO_SOURCES, IO_LIB_PATH, force, verbose)
-
-
-def build_img(force: bool = False, verbose: bool = False) -> str:
-    """libscg_img.so from IMG_SOURCES, as build_io."""
-    return _build_side(IMG_SOURCES, IMG_LIB_PATH, force, verbose)
-
-
-def build_mp(force: bool = False, verbose: bool = False) -> str:
-    """libscg_mp.so from MP_SOURCES, as build_io."""
-    return _build_side(MP_SOURCES, MP_LIB_PATH, force, verbose)
-
-
-def build_vw(force: bool = False, verbose: bool = False) -> str:
-    """libscg_vw.so from VW_SOURCES, as build_io."""
-    return _build_side(VW_SOURCES, VW_LIB_PATH, force, verbose)
-
-
-def build_lp(force: bool = False, verbose: bool = False) -> str:
-    """libscg_lp.so from LP_SOURCES, as build_io."""
-    return _build_side(LP_SOURCES, LP_LIB_PATH, force, verbose)
-
-
-def build_png(force: bool = False, verbose: bool = False) -> str:
-    """libscg_png.so from PNG_SOURCES, as build_io."""
-    return _build_side(PNG_SOURCES, PNG_LIB_PATH, force, verbose)
-
-
 def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(), flags=(), only=None) -> str:
     """tag/defines build a VARIANT libscg_raster_<tag>.so (selected at run time with SCG_LIB_PATH); the default build has
-    neither and builds libscg_io.so, libscg_img.so, libscg_mp.so, libscg_vw.so, libscg_lp.so and libscg_png.so behind the main library.  `only`: the sources the defines / flags apply to — the others are
-    linked from the default build's objects."""
+    neither and builds every side library behind the main one.  `only`: the sources the defines / flags apply to — the others
+    are linked from the default build's objects."""
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
     objs = []
@@ -207,12 +176,8 @@ def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(),
     if rebuilt or force or not os.path.exists(lib_path):
         _link(hipcc, lib_path, objs, verbose)
     if not tag:
-        build_io(force=force, verbose=verbose)
-        build_img(force=force, verbose=verbose)
-        build_mp(force=force, verbose=verbose)
-        build_vw(force=force, verbose=verbose)
-        build_lp(force=force, verbose=verbose)
-        build_png(force=force, verbose=verbose)
+        for key in SIDE_LIBRARIES:
+            build_side(key, force=force, verbose=verbose)
     return lib_path
 
 

@@ -7,6 +7,8 @@
 
 #include "scg_common.h"
 #include "scg_debug.h"
+#include "host_align.h"
+#include "host_error.h"
 #include "../../include/scg_matchloss.h"
 
 #include <atomic>
@@ -15,21 +17,17 @@
 
 namespace scg {
 
-static thread_local char g_err[512] = "";
+static thread_local ErrorText g_err = {};      // the main library's; the other files reach it through the two functions below
 
 int fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    g_err.vfail(code, fmt, ap);
     va_end(ap);
     return code;
 }
 
-int check_hip(hipError_t e, const char* what) {
-    if (e == hipSuccess) return 0;
-    snprintf(g_err, sizeof(g_err), "%s: %s (hipError %d)", what, hipGetErrorString(e), (int)e);
-    return (int)e;
-}
+int check_hip(hipError_t e, const char* what) { return g_err.check_hip(e, what); }
 
 int check_workspace(const char* who, const void* ws, size_t bytes, size_t need) {
     if (!ws) return fail(SCG_E_NULL, "%s: workspace is NULL", who);
@@ -50,9 +48,6 @@ int validate_frame(const ScgFrame* f, bool need_bg) {
     return 0;
 }
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static inline bool aligned64(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 63u) == 0; }
 int validate_model(const ScgFrame* f, const ScgModel* m);
 
 static int validate_inputs(const ScgFrame* f, const float* means3D, const float* opacities, const float* shs,
@@ -102,7 +97,7 @@ using namespace scg;
 
 extern "C" {
 
-const char* scg_last_error(void) { return g_err; }
+const char* scg_last_error(void) { return g_err.text; }
 int32_t scg_abi_version(void) { return SCG_ABI_VERSION; }
 
 size_t scg_struct_bytes(int32_t which) {

@@ -5,6 +5,7 @@
 // HBM-bound streaming / scatter kernels: 16-byte lane-contiguous loads, wave64 ballot ranking, LDS
 // histograms.  No MFMA (nothing here is a contraction).
 #include "scg_common.h"
+#include "host_align.h"
 #include "reduce.h"
 
 namespace scg {
@@ -336,8 +337,6 @@ __global__ __launch_bounds__(kBlock) void sort_scatter_kernel(const KeyT* __rest
 }
 
 int sort_num_passes(int end_bit) { return (end_bit + 7) / 8; }
-
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 size_t sort_scratch_bytes(int64_t n) {
     const int64_t nblocks = (n + kSortTile - 1) / kSortTile;

@@ -26,6 +26,7 @@
 // LDS does the work a global sort would do through HBM: a tile's list (a few hundred to a few thousand entries)
 // fits the 160 KiB LDS of a CU with room to spare.
 #include "scg_common.h"
+#include "host_align.h"
 #include "tile_sort.h"
 #include "tile_walk.h"
 
@@ -918,8 +919,6 @@ __global__ __launch_bounds__(kBlock) void rebuild_keys_kernel(const uint32_t* __
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // Per-DEVICE one-time setup (a process may rasterize on several GPUs, from several threads): the dynamic-LDS
 // attributes of the two big-LDS kernels are a property of the (kernel, device) pair, and the rare-sort grid is sized
 // by that device's CU count.

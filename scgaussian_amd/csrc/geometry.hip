@@ -14,6 +14,7 @@
 // One thread per Gaussian, 256-thread workgroups (4 waves).  Loads of the (P,3)/(P,4) arrays are
 // lane-contiguous; the 192-byte SH record is read with 16-byte loads (12 per lane at degree 3).
 #include "scg_common.h"
+#include "host_align.h"
 #include "reduce.h"
 #include "tile_walk.h"
 #include "sh_eval.h"
@@ -1308,8 +1309,6 @@ __global__ __launch_bounds__(kBlock) void model_activate_kernel(ScgModel m, int 
 // ---------------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------------
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // degree -> kernel instantiation (-1: precomputed colours)
 template <class F>
 static inline void by_degree(int deg, F&& f) {

@@ -17,10 +17,8 @@
 //
 // No atomics, no allocation, no host read.  Every sum starts at +0 and every step is one fma or one add: a product with a zero
 // operand leaves it as it is, so a pixel's value does not depend on its neighbours in the tile.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "../../include/lp/scg_lpips.h"
+#include "host_error.h"
 #include "reduce.h"
 
 #pragma clang fp contract(off)
@@ -45,27 +43,7 @@ constexpr int kCout[SCG_LP_LAYERS] = {64, 64, 128, 128, 256, 256, 256, 512, 512,
 constexpr bool kPoolIn[SCG_LP_LAYERS] = {false, false, true, false, true, false, false, true, false, false, true, false, false};
 constexpr int kTapC[SCG_LP_TAPS] = {64, 128, 256, 512, 512};
 
-thread_local char g_lp_err[512] = "";
-
-int lp_fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_lp_err, sizeof(g_lp_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int lp_check_hip(hipError_t e, const char* what) {
-    if (e == hipSuccess) return 0;
-    snprintf(g_lp_err, sizeof(g_lp_err), "%s: %s (hipError %d)", what, hipGetErrorString(e), (int)e);
-    return (int)e;
-}
-
-int check_ptr(const char* who, const void* p, const char* name, unsigned align) {
-    if (!p) return lp_fail(SCG_E_NULL, "%s: %s is NULL", who, name);
-    if (reinterpret_cast<uintptr_t>(p) % align) return lp_fail(SCG_E_ALIGN, "%s: %s is not %u-byte aligned", who, name, align);
-    return 0;
-}
+thread_local ErrorText g_err = {};
 
 // torch's relu: a NaN stays, -0 and everything below become +0
 __device__ __forceinline__ float relu_keep_nan(float v) { return (v > 0.f || v != v) ? v : 0.f; }
@@ -260,7 +238,7 @@ __global__ __launch_bounds__(kBlock) void lp_conv_kernel(ConvArgs a) {
 
 int launch_first(const FirstArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(lp_first_kernel, dim3((unsigned)((a.M + kFirstPix - 1) / kFirstPix)), dim3(kBlock), 0, st, a);
-    return lp_check_hip(hipGetLastError(), "lp_first");
+    return g_err.check_hip(hipGetLastError(), "lp_first");
 }
 
 // n images of (hin, win, cin), pooled first when `pool`
@@ -283,7 +261,7 @@ int launch_conv(int n, int cin, int cout, int hin, int win, bool pool, const flo
         if (pool) hipLaunchKernelGGL((lp_conv_kernel<2, true>), grid, dim3(kBlock), 0, st, a);
         else hipLaunchKernelGGL((lp_conv_kernel<2, false>), grid, dim3(kBlock), 0, st, a);
     }
-    return lp_check_hip(hipGetLastError(), "lp_conv");
+    return g_err.check_hip(hipGetLastError(), "lp_conv");
 }
 
 // ---- the head ----------------------------------------------------------------------------------------------------------------
@@ -409,9 +387,9 @@ int launch_head(const Layout& l, char* s, const float* params, float* value, flo
     }
     a.partial = reinterpret_cast<double*>(s + l.partial); a.pb = l.pb; a.value = value; a.terms = terms;
     hipLaunchKernelGGL(lp_head_kernel, dim3((unsigned)l.pb, SCG_LP_TAPS), dim3(kBlock), 0, st, a);
-    if (int rc = lp_check_hip(hipGetLastError(), "lp_head")) return rc;
+    if (int rc = g_err.check_hip(hipGetLastError(), "lp_head")) return rc;
     hipLaunchKernelGGL(lp_fold_kernel, dim3(1), dim3(kBlock), 0, st, a);
-    return lp_check_hip(hipGetLastError(), "lp_fold");
+    return g_err.check_hip(hipGetLastError(), "lp_fold");
 }
 
 }  // namespace
@@ -421,7 +399,7 @@ using namespace scg;
 
 extern "C" {
 
-const char* scg_lp_last_error(void) { return g_lp_err; }
+const char* scg_lp_last_error(void) { return g_err.text; }
 int32_t scg_lp_abi_version(void) { return SCG_LP_ABI_VERSION; }
 
 size_t scg_lp_scratch_bytes(int32_t H, int32_t W) {
@@ -439,19 +417,19 @@ int scg_lp_conv3x3(int32_t n, int32_t cin, int32_t cout, int32_t h, int32_t w, c
     const char* who = "scg_lp_conv3x3";
     bool pair = false;
     for (int l = 0; l < SCG_LP_LAYERS; ++l) pair |= (cin == kCin[l] && cout == kCout[l]);
-    if (!pair) return lp_fail(SCG_E_RANGE, "%s: (cin, cout) = (%d, %d) is not a layer of the network", who, cin, cout);
-    if (flags & ~(SCG_LP_RELU | SCG_LP_POOL | SCG_LP_ZSCORE)) return lp_fail(SCG_E_RANGE, "%s: unknown flags %d", who, flags);
+    if (!pair) return g_err.fail(SCG_E_RANGE, "%s: (cin, cout) = (%d, %d) is not a layer of the network", who, cin, cout);
+    if (flags & ~(SCG_LP_RELU | SCG_LP_POOL | SCG_LP_ZSCORE)) return g_err.fail(SCG_E_RANGE, "%s: unknown flags %d", who, flags);
     const bool pool = flags & SCG_LP_POOL, zs = flags & SCG_LP_ZSCORE;
     if (cin == 3 ? pool : zs)
-        return lp_fail(SCG_E_EXCLUSIVE, "%s: the z-score belongs to cin = 3, the pool to cin >= 64", who);
+        return g_err.fail(SCG_E_EXCLUSIVE, "%s: the z-score belongs to cin = 3, the pool to cin >= 64", who);
     const int lo = pool ? 2 : 1;
     if (n < 1 || n > SCG_LP_MAX_BATCH || h < lo || w < lo || h > SCG_LP_MAX_DIM || w > SCG_LP_MAX_DIM ||
         (int64_t)h * w > SCG_LP_MAX_PIXELS)
-        return lp_fail(SCG_E_RANGE, "%s: n = %d, h = %d, w = %d out of range", who, n, h, w);
-    if (int rc = check_ptr(who, in, "in", 16)) return rc;
-    if (int rc = check_ptr(who, weights, "weights", 16)) return rc;
-    if (int rc = check_ptr(who, bias, "bias", 16)) return rc;
-    if (int rc = check_ptr(who, out, "out", 16)) return rc;
+        return g_err.fail(SCG_E_RANGE, "%s: n = %d, h = %d, w = %d out of range", who, n, h, w);
+    if (int rc = g_err.check_ptr(who, in, "in", 16)) return rc;
+    if (int rc = g_err.check_ptr(who, weights, "weights", 16)) return rc;
+    if (int rc = g_err.check_ptr(who, bias, "bias", 16)) return rc;
+    if (int rc = g_err.check_ptr(who, out, "out", 16)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (cin == 3) {
         FirstArgs a = {};
@@ -468,17 +446,17 @@ int scg_lp_forward(int32_t H, int32_t W, const float* x, const float* y, const f
     const char* who = "scg_lp_forward";
     Layout l;
     if (!layout(H, W, &l))
-        return lp_fail(SCG_E_RANGE, "%s: H = %d, W = %d: both must be in [%d, %d] and H * W <= %d", who, H, W, SCG_LP_MIN_DIM,
+        return g_err.fail(SCG_E_RANGE, "%s: H = %d, W = %d: both must be in [%d, %d] and H * W <= %d", who, H, W, SCG_LP_MIN_DIM,
                        SCG_LP_MAX_DIM, SCG_LP_MAX_PIXELS);
-    if (int rc = check_ptr(who, x, "x", 4)) return rc;
-    if (int rc = check_ptr(who, y, "y", 4)) return rc;
-    if (int rc = check_ptr(who, params, "params", 16)) return rc;
-    if (int rc = check_ptr(who, value, "value", 4)) return rc;
-    if (int rc = check_ptr(who, terms, "terms", 4)) return rc;
-    if (features) if (int rc = check_ptr(who, features, "features", 16)) return rc;
-    if (!scratch) return lp_fail(SCG_E_NULL, "%s: scratch is NULL", who);
-    if (scratch_bytes < l.total) return lp_fail(SCG_E_SCRATCH, "%s: scratch of %zu bytes < %zu", who, scratch_bytes, l.total);
-    if (reinterpret_cast<uintptr_t>(scratch) % 16) return lp_fail(SCG_E_ALIGN, "%s: scratch is not 16-byte aligned", who);
+    if (int rc = g_err.check_ptr(who, x, "x", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, y, "y", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, params, "params", 16)) return rc;
+    if (int rc = g_err.check_ptr(who, value, "value", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, terms, "terms", 4)) return rc;
+    if (features) if (int rc = g_err.check_ptr(who, features, "features", 16)) return rc;
+    if (!scratch) return g_err.fail(SCG_E_NULL, "%s: scratch is NULL", who);
+    if (scratch_bytes < l.total) return g_err.fail(SCG_E_SCRATCH, "%s: scratch of %zu bytes < %zu", who, scratch_bytes, l.total);
+    if (reinterpret_cast<uintptr_t>(scratch) % 16) return g_err.fail(SCG_E_ALIGN, "%s: scratch is not 16-byte aligned", who);
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* s = static_cast<char*>(scratch);
@@ -513,15 +491,15 @@ int scg_lp_head(int32_t H, int32_t W, const float* params, float* value, float* 
     const char* who = "scg_lp_head";
     Layout l;
     if (!layout(H, W, &l))
-        return lp_fail(SCG_E_RANGE, "%s: H = %d, W = %d: both must be in [%d, %d] and H * W <= %d", who, H, W, SCG_LP_MIN_DIM,
+        return g_err.fail(SCG_E_RANGE, "%s: H = %d, W = %d: both must be in [%d, %d] and H * W <= %d", who, H, W, SCG_LP_MIN_DIM,
                        SCG_LP_MAX_DIM, SCG_LP_MAX_PIXELS);
-    if (int rc = check_ptr(who, params, "params", 16)) return rc;
-    if (int rc = check_ptr(who, value, "value", 4)) return rc;
-    if (int rc = check_ptr(who, terms, "terms", 4)) return rc;
-    if (features) if (int rc = check_ptr(who, features, "features", 16)) return rc;
-    if (!scratch) return lp_fail(SCG_E_NULL, "%s: scratch is NULL", who);
-    if (scratch_bytes < l.total) return lp_fail(SCG_E_SCRATCH, "%s: scratch of %zu bytes < %zu", who, scratch_bytes, l.total);
-    if (reinterpret_cast<uintptr_t>(scratch) % 16) return lp_fail(SCG_E_ALIGN, "%s: scratch is not 16-byte aligned", who);
+    if (int rc = g_err.check_ptr(who, params, "params", 16)) return rc;
+    if (int rc = g_err.check_ptr(who, value, "value", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, terms, "terms", 4)) return rc;
+    if (features) if (int rc = g_err.check_ptr(who, features, "features", 16)) return rc;
+    if (!scratch) return g_err.fail(SCG_E_NULL, "%s: scratch is NULL", who);
+    if (scratch_bytes < l.total) return g_err.fail(SCG_E_SCRATCH, "%s: scratch of %zu bytes < %zu", who, scratch_bytes, l.total);
+    if (reinterpret_cast<uintptr_t>(scratch) % 16) return g_err.fail(SCG_E_ALIGN, "%s: scratch is not 16-byte aligned", who);
     return launch_head(l, static_cast<char*>(scratch), params, value, terms, features, static_cast<hipStream_t>(stream));
 }
 

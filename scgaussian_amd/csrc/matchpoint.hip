@@ -24,10 +24,9 @@
 //
 // No float atomics, no host read, no allocation.  Min and max are exact in any order once zeros are ordered by sign and a NaN wins
 // (ordered_min / ordered_max below).  Compiled with -ffp-contract=off: the position is a product and a sum.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "../../include/mp/scg_matchpoint.h"
+#include "host_align.h"
+#include "host_error.h"
 #include "pixel_rules.h"
 #include "reduce.h"
 
@@ -44,39 +43,22 @@ static_assert(kGroup == kBlock && kGroup % SCG_MP_TILE_RECORDS == 0 && (SCG_MP_T
               "a workgroup's records are whole tiles and a tile is a whole number of dwords");
 static_assert(SCG_MP_RESOLVE_PIXELS == kBlock && SCG_MP_QUANT_PIXELS == 4 * kBlock, "one and four pixels per thread");
 
-thread_local char g_mp_err[512] = "";
-
-int mp_fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_mp_err, sizeof(g_mp_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int mp_check_hip(hipError_t e, const char* what) {
-    if (e == hipSuccess) return 0;
-    snprintf(g_mp_err, sizeof(g_mp_err), "%s: %s (hipError %d)", what, hipGetErrorString(e), (int)e);
-    return (int)e;
-}
-
-uint64_t align256(uint64_t v) { return (v + 255u) & ~(uint64_t)255u; }
-uint64_t pad4(uint64_t v) { return (v + 3u) & ~(uint64_t)3u; }
+thread_local ErrorText g_err = {};
 
 // The layout and the view table from the sizes; who == nullptr: no message.  Host only.
 int layout_of(const char* who, int64_t N, int64_t V, const int32_t* hw, ScgMpLayout* l, ScgMpView* views) {
-    if (N < 0 || N > SCG_MP_MAX_MATCHES) return who ? mp_fail(SCG_E_RANGE, "%s: N = %lld is outside 0..2^31 - 1", who, (long long)N) : SCG_E_RANGE;
-    if (V < 1 || V > SCG_MP_MAX_VIEWS) return who ? mp_fail(SCG_E_RANGE, "%s: V = %lld is outside 1..%d", who, (long long)V, SCG_MP_MAX_VIEWS) : SCG_E_RANGE;
-    if (!hw) return who ? mp_fail(SCG_E_NULL, "%s: hw is NULL", who) : SCG_E_NULL;
+    if (N < 0 || N > SCG_MP_MAX_MATCHES) return who ? g_err.fail(SCG_E_RANGE, "%s: N = %lld is outside 0..2^31 - 1", who, (long long)N) : SCG_E_RANGE;
+    if (V < 1 || V > SCG_MP_MAX_VIEWS) return who ? g_err.fail(SCG_E_RANGE, "%s: V = %lld is outside 1..%d", who, (long long)V, SCG_MP_MAX_VIEWS) : SCG_E_RANGE;
+    if (!hw) return who ? g_err.fail(SCG_E_NULL, "%s: hw is NULL", who) : SCG_E_NULL;
     uint64_t pixels = 0, bytes = 0, rg = 0, qg = 0;
     for (int64_t v = 0; v < V; ++v) {
         const int32_t H = hw[2 * v], W = hw[2 * v + 1];
         if (H < 1 || W < 1 || H > SCG_MP_MAX_DIM || W > SCG_MP_MAX_DIM)
-            return who ? mp_fail(SCG_E_RANGE, "%s: view %lld of %d x %d pixels (H, W must be 1..%d)", who, (long long)v, W, H, SCG_MP_MAX_DIM)
+            return who ? g_err.fail(SCG_E_RANGE, "%s: view %lld of %d x %d pixels (H, W must be 1..%d)", who, (long long)v, W, H, SCG_MP_MAX_DIM)
                        : SCG_E_RANGE;
         const uint64_t n = (uint64_t)H * (uint64_t)W;
-        if (bytes + pad4(n) > SCG_MP_MAX_PIXELS)
-            return who ? mp_fail(SCG_E_RANGE, "%s: the views hold more than 2^31 - 1 pixels", who) : SCG_E_RANGE;
+        if (bytes + align_to<4>(n) > SCG_MP_MAX_PIXELS)
+            return who ? g_err.fail(SCG_E_RANGE, "%s: the views hold more than 2^31 - 1 pixels", who) : SCG_E_RANGE;
         if (views) {
             views[v].H = H;
             views[v].W = W;
@@ -86,19 +68,19 @@ int layout_of(const char* who, int64_t N, int64_t V, const int32_t* hw, ScgMpLay
             views[v].quant_group = (int32_t)qg;
         }
         pixels += n;
-        bytes += pad4(n);
+        bytes += align_to<4>(n);
         rg += (n + SCG_MP_RESOLVE_PIXELS - 1) / SCG_MP_RESOLVE_PIXELS;
         qg += (n + SCG_MP_QUANT_PIXELS - 1) / SCG_MP_QUANT_PIXELS;
     }
     l->body_offset = 0;
-    l->body_bytes = pad4((uint64_t)N * kRec);
-    l->depth_offset = align256(l->body_offset + l->body_bytes);
+    l->body_bytes = align_to<4>((uint64_t)N * kRec);
+    l->depth_offset = align_to<256>(l->body_offset + l->body_bytes);
     l->depth_bytes = pixels * 4;
-    l->byte_offset = align256(l->depth_offset + l->depth_bytes);
+    l->byte_offset = align_to<256>(l->depth_offset + l->depth_bytes);
     l->byte_bytes = bytes;
-    l->range_offset = align256(l->byte_offset + l->byte_bytes);
+    l->range_offset = align_to<256>(l->byte_offset + l->byte_bytes);
     l->range_bytes = (uint64_t)V * 8;
-    l->total = align256(l->range_offset + l->range_bytes);
+    l->total = align_to<256>(l->range_offset + l->range_bytes);
     l->pixels = pixels;
     l->resolve_groups = rg;
     l->quant_groups = qg;
@@ -313,7 +295,7 @@ using namespace scg;
 
 extern "C" {
 
-const char* scg_mp_last_error(void) { return g_mp_err; }
+const char* scg_mp_last_error(void) { return g_err.text; }
 int32_t scg_mp_abi_version(void) { return SCG_MP_ABI_VERSION; }
 
 size_t scg_mp_struct_bytes(int32_t which) {
@@ -326,7 +308,7 @@ size_t scg_mp_struct_bytes(int32_t which) {
 }
 
 int scg_mp_layout(int32_t N, int32_t V, const int32_t* hw, ScgMpLayout* out, ScgMpView* views_out) {
-    if (!out) return mp_fail(SCG_E_NULL, "scg_mp_layout: out is NULL");
+    if (!out) return g_err.fail(SCG_E_NULL, "scg_mp_layout: out is NULL");
     ScgMpLayout l;
     if (int rc = layout_of("scg_mp_layout", N, V, hw, &l, views_out)) return rc;
     *out = l;
@@ -340,27 +322,27 @@ size_t scg_mp_workspace_bytes(int32_t V, const int32_t* hw) {
 
 int scg_mp_pack(const ScgMpPack* p, void* buffer, size_t buffer_bytes, void* workspace, size_t workspace_bytes, void* stream) {
     const char* who = "scg_mp_pack";
-    if (!p) return mp_fail(SCG_E_NULL, "%s: args is NULL", who);
+    if (!p) return g_err.fail(SCG_E_NULL, "%s: args is NULL", who);
     if (p->struct_bytes != (int32_t)sizeof(ScgMpPack))
-        return mp_fail(SCG_E_RANGE, "%s: struct_bytes = %d, the library's ScgMpPack has %zu", who, p->struct_bytes, sizeof(ScgMpPack));
-    if (p->N < 1) return mp_fail(SCG_E_RANGE, "%s: N = %d: a snapshot needs at least one match", who, p->N);
-    if (p->V < 1 || p->V > SCG_MP_MAX_VIEWS) return mp_fail(SCG_E_RANGE, "%s: V = %d is outside 1..%d", who, p->V, SCG_MP_MAX_VIEWS);
+        return g_err.fail(SCG_E_RANGE, "%s: struct_bytes = %d, the library's ScgMpPack has %zu", who, p->struct_bytes, sizeof(ScgMpPack));
+    if (p->N < 1) return g_err.fail(SCG_E_RANGE, "%s: N = %d: a snapshot needs at least one match", who, p->N);
+    if (p->V < 1 || p->V > SCG_MP_MAX_VIEWS) return g_err.fail(SCG_E_RANGE, "%s: V = %d is outside 1..%d", who, p->V, SCG_MP_MAX_VIEWS);
     if (p->nseg < 1 || p->nseg > SCG_MP_MAX_SEGMENTS)
-        return mp_fail(SCG_E_RANGE, "%s: nseg = %d is outside 1..%d", who, p->nseg, SCG_MP_MAX_SEGMENTS);
-    if (!p->segments || !p->segments_dev) return mp_fail(SCG_E_NULL, "%s: a segment table is NULL", who);
-    if (!p->views || !p->views_dev) return mp_fail(SCG_E_NULL, "%s: a view table is NULL", who);
+        return g_err.fail(SCG_E_RANGE, "%s: nseg = %d is outside 1..%d", who, p->nseg, SCG_MP_MAX_SEGMENTS);
+    if (!p->segments || !p->segments_dev) return g_err.fail(SCG_E_NULL, "%s: a segment table is NULL", who);
+    if (!p->views || !p->views_dev) return g_err.fail(SCG_E_NULL, "%s: a view table is NULL", who);
     const int N = p->N, V = p->V;
     int64_t at = 0;
     for (int s = 0; s < p->nseg; ++s) {
         const ScgSeedSegment& g = p->segments[s];
-        if (g.view < 0 || g.view >= V) return mp_fail(SCG_E_RANGE, "%s: segment %d has view %d outside [0, %d)", who, s, g.view, V);
-        if (g.count < 0 || g.offset < 0) return mp_fail(SCG_E_RANGE, "%s: segment %d has offset %d, count %d", who, s, g.offset, g.count);
+        if (g.view < 0 || g.view >= V) return g_err.fail(SCG_E_RANGE, "%s: segment %d has view %d outside [0, %d)", who, s, g.view, V);
+        if (g.count < 0 || g.offset < 0) return g_err.fail(SCG_E_RANGE, "%s: segment %d has offset %d, count %d", who, s, g.offset, g.count);
         if (g.offset != at)
-            return mp_fail(SCG_E_RANGE, "%s: segment %d starts at %d, the one before it ends at %lld", who, s, g.offset, (long long)at);
+            return g_err.fail(SCG_E_RANGE, "%s: segment %d starts at %d, the one before it ends at %lld", who, s, g.offset, (long long)at);
         at += g.count;
-        if (at > N) return mp_fail(SCG_E_RANGE, "%s: segment %d runs past N = %d", who, s, N);
+        if (at > N) return g_err.fail(SCG_E_RANGE, "%s: segment %d runs past N = %d", who, s, N);
     }
-    if (at != N) return mp_fail(SCG_E_RANGE, "%s: the segments cover %lld of N = %d matches", who, (long long)at, N);
+    if (at != N) return g_err.fail(SCG_E_RANGE, "%s: the segments cover %lld of N = %d matches", who, (long long)at, N);
     // the view table: the one the layout gives for its own H and W, record by record
     int32_t hw[2 * SCG_MP_MAX_VIEWS];
     for (int v = 0; v < V; ++v) {
@@ -374,20 +356,20 @@ int scg_mp_pack(const ScgMpPack* p, void* buffer, size_t buffer_bytes, void* wor
         const ScgMpView &x = p->views[v], &y = want[v];
         if (x.first_pixel != y.first_pixel || x.first_byte != y.first_byte || x.resolve_group != y.resolve_group ||
             x.quant_group != y.quant_group)
-            return mp_fail(SCG_E_RANGE, "%s: view %d is (pixel %d, byte %d, groups %d, %d), the layout gives (%d, %d, %d, %d)", who, v,
+            return g_err.fail(SCG_E_RANGE, "%s: view %d is (pixel %d, byte %d, groups %d, %d), the layout gives (%d, %d, %d, %d)", who, v,
                            x.first_pixel, x.first_byte, x.resolve_group, x.quant_group, y.first_pixel, y.first_byte, y.resolve_group,
                            y.quant_group);
     }
-    if (!buffer) return mp_fail(SCG_E_NULL, "%s: buffer is NULL", who);
-    if (buffer_bytes < l.total) return mp_fail(SCG_E_SCRATCH, "%s: buffer of %zu bytes < %llu", who, buffer_bytes, (unsigned long long)l.total);
-    if (reinterpret_cast<uintptr_t>(buffer) % 16) return mp_fail(SCG_E_ALIGN, "%s: buffer not 16-byte aligned", who);
-    if (!workspace) return mp_fail(SCG_E_NULL, "%s: workspace is NULL", who);
+    if (!buffer) return g_err.fail(SCG_E_NULL, "%s: buffer is NULL", who);
+    if (buffer_bytes < l.total) return g_err.fail(SCG_E_SCRATCH, "%s: buffer of %zu bytes < %llu", who, buffer_bytes, (unsigned long long)l.total);
+    if (reinterpret_cast<uintptr_t>(buffer) % 16) return g_err.fail(SCG_E_ALIGN, "%s: buffer not 16-byte aligned", who);
+    if (!workspace) return g_err.fail(SCG_E_NULL, "%s: workspace is NULL", who);
     if (workspace_bytes < workspace_of(l))
-        return mp_fail(SCG_E_SCRATCH, "%s: workspace of %zu bytes < %zu", who, workspace_bytes, workspace_of(l));
-    if (reinterpret_cast<uintptr_t>(workspace) % 4) return mp_fail(SCG_E_ALIGN, "%s: workspace not 4-byte aligned", who);
-    if (!p->rays_o || !p->rays_d || !p->z || !p->color || !p->uv || !p->cam_z) return mp_fail(SCG_E_NULL, "%s: an input tensor is NULL", who);
+        return g_err.fail(SCG_E_SCRATCH, "%s: workspace of %zu bytes < %zu", who, workspace_bytes, workspace_of(l));
+    if (reinterpret_cast<uintptr_t>(workspace) % 4) return g_err.fail(SCG_E_ALIGN, "%s: workspace not 4-byte aligned", who);
+    if (!p->rays_o || !p->rays_d || !p->z || !p->color || !p->uv || !p->cam_z) return g_err.fail(SCG_E_NULL, "%s: an input tensor is NULL", who);
     for (const float* t : {p->rays_o, p->rays_d, p->z, p->color, p->uv, p->cam_z})
-        if (reinterpret_cast<uintptr_t>(t) % 4) return mp_fail(SCG_E_ALIGN, "%s: an input tensor is not 4-byte aligned", who);
+        if (reinterpret_cast<uintptr_t>(t) % 4) return g_err.fail(SCG_E_ALIGN, "%s: an input tensor is not 4-byte aligned", who);
 
     MpArgs a;
     a.N = N; a.V = V; a.nseg = p->nseg;
@@ -412,13 +394,13 @@ int scg_mp_pack(const ScgMpPack* p, void* buffer, size_t buffer_bytes, void* wor
     int64_t clear = ((int64_t)l.pixels + 4 * kBlock - 1) / (4 * kBlock);
     clear = clear > kMaxClearGroups ? kMaxClearGroups : (clear < 1 ? 1 : clear);
     hipLaunchKernelGGL(mp_clear_kernel, dim3((unsigned)clear), dim3(kBlock), 0, st, a);
-    if (int rc = mp_check_hip(hipGetLastError(), "mp_clear")) return rc;
+    if (int rc = g_err.check_hip(hipGetLastError(), "mp_clear")) return rc;
     hipLaunchKernelGGL(mp_matches_kernel, dim3((unsigned)(((int64_t)N + kGroup - 1) / kGroup)), dim3(kBlock), 0, st, a);
-    if (int rc = mp_check_hip(hipGetLastError(), "mp_matches")) return rc;
+    if (int rc = g_err.check_hip(hipGetLastError(), "mp_matches")) return rc;
     hipLaunchKernelGGL(mp_resolve_kernel, dim3((unsigned)l.resolve_groups), dim3(kBlock), 0, st, a);
-    if (int rc = mp_check_hip(hipGetLastError(), "mp_resolve")) return rc;
+    if (int rc = g_err.check_hip(hipGetLastError(), "mp_resolve")) return rc;
     hipLaunchKernelGGL(mp_quantise_kernel, dim3((unsigned)l.quant_groups), dim3(kBlock), 0, st, a);
-    return mp_check_hip(hipGetLastError(), "mp_quantise");
+    return g_err.check_hip(hipGetLastError(), "mp_quantise");
 }
 
 }  // extern "C"

@@ -16,11 +16,11 @@
 // Compiled with -ffp-contract=off: x = rayo + rayd * zval is a product and a sum, each rounded, as torch and numpy round them; the
 // colour is the chain of single fp32 operations of include/io/scg_ply.h.  Everything else moves as uint32_t.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/io/scg_ply.h"
+#include "host_align.h"
+#include "host_error.h"
 #include "sh_eval.h"
 
 #pragma clang fp contract(off)
@@ -36,33 +36,17 @@ constexpr int kRest = 45;                              // floats of a features_r
 constexpr int kColDc = 6, kColRest = 9, kColOpacity = 54, kColScale = 55, kColRot = 58, kColZval = 62, kColRayo = 63, kColRayd = 66;
 static_assert(kRows % 4 == 0 && (kRows * kColor) % 4 == 0, "a tile of colour records is a whole number of dwords");
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int check_hip(hipError_t e, const char* what) {
-    if (e == hipSuccess) return 0;
-    snprintf(g_err, sizeof(g_err), "%s: %s (hipError %d)", what, hipGetErrorString(e), (int)e);
-    return (int)e;
-}
-
-uint64_t align256(uint64_t v) { return (v + 255u) & ~(uint64_t)255u; }
+thread_local ErrorText g_err = {};
 
 ScgPlyLayout layout_of(int32_t nr, int32_t nb) {
     ScgPlyLayout l;
     l.ray_offset = 0;
     l.ray_bytes = (uint64_t)nr * kRay * 4;
-    l.bg_offset = align256(l.ray_offset + l.ray_bytes);
+    l.bg_offset = align_to<256>(l.ray_offset + l.ray_bytes);
     l.bg_bytes = (uint64_t)nb * kBg * 4;
-    l.color_offset = align256(l.bg_offset + l.bg_bytes);
-    l.color_bytes = (((uint64_t)nr + (uint64_t)nb) * kColor + 3u) & ~(uint64_t)3u;
-    l.total = align256(l.color_offset + l.color_bytes);
+    l.color_offset = align_to<256>(l.bg_offset + l.bg_bytes);
+    l.color_bytes = align_to<4>(((uint64_t)nr + (uint64_t)nb) * kColor);
+    l.total = align_to<256>(l.color_offset + l.color_bytes);
     return l;
 }
 
@@ -287,24 +271,24 @@ __global__ void __launch_bounds__(kBlock) ply_unpack_kernel(const uint32_t* __re
 
 // ---- validation ----------------------------------------------------------------------------------------------------------------
 int check_set(const char* who, const ScgModelSet& s, bool ray) {
-    if (s.count < 0) return fail(SCG_E_RANGE, "%s: a set of %d Gaussians", who, s.count);
+    if (s.count < 0) return g_err.fail(SCG_E_RANGE, "%s: a set of %d Gaussians", who, s.count);
     if (s.count == 0) return 0;
     const bool have = s.features_dc && s.features_rest && s.opacity && s.scaling && s.rotation &&
                       (ray ? (s.zval && s.rayo && s.rayd) : s.xyz != nullptr);
-    if (!have) return fail(SCG_E_NULL, "%s: a tensor of the %s set is NULL", who, ray ? "ray-bound" : "background");
+    if (!have) return g_err.fail(SCG_E_NULL, "%s: a tensor of the %s set is NULL", who, ray ? "ray-bound" : "background");
     return 0;
 }
 
 int check_model(const char* who, const ScgModel* m) {
-    if (!m) return fail(SCG_E_NULL, "%s: model is NULL", who);
+    if (!m) return g_err.fail(SCG_E_NULL, "%s: model is NULL", who);
     if (int rc = check_set(who, m->ray, true)) return rc;
     return check_set(who, m->bg, false);
 }
 
 int check_buffer(const char* who, const void* buffer, size_t bytes, uint64_t need) {
-    if (!buffer) return fail(SCG_E_NULL, "%s: buffer is NULL", who);
-    if (bytes < need) return fail(SCG_E_SCRATCH, "%s: buffer of %zu bytes < %llu", who, bytes, (unsigned long long)need);
-    if (reinterpret_cast<uintptr_t>(buffer) % 16) return fail(SCG_E_ALIGN, "%s: buffer not 16-byte aligned", who);
+    if (!buffer) return g_err.fail(SCG_E_NULL, "%s: buffer is NULL", who);
+    if (bytes < need) return g_err.fail(SCG_E_SCRATCH, "%s: buffer of %zu bytes < %llu", who, bytes, (unsigned long long)need);
+    if (reinterpret_cast<uintptr_t>(buffer) % 16) return g_err.fail(SCG_E_ALIGN, "%s: buffer not 16-byte aligned", who);
     return 0;
 }
 
@@ -315,13 +299,13 @@ using namespace scg;
 
 extern "C" {
 
-const char* scg_io_last_error(void) { return g_err; }
+const char* scg_io_last_error(void) { return g_err.text; }
 int32_t scg_io_abi_version(void) { return SCG_IO_ABI_VERSION; }
 size_t scg_ply_layout_bytes(void) { return sizeof(ScgPlyLayout); }
 
 int scg_ply_layout(int32_t nr, int32_t nb, ScgPlyLayout* out) {
-    if (!out) return fail(SCG_E_NULL, "scg_ply_layout: out is NULL");
-    if (nr < 0 || nb < 0) return fail(SCG_E_RANGE, "scg_ply_layout: %d ray-bound and %d background Gaussians", nr, nb);
+    if (!out) return g_err.fail(SCG_E_NULL, "scg_ply_layout: out is NULL");
+    if (nr < 0 || nb < 0) return g_err.fail(SCG_E_RANGE, "scg_ply_layout: %d ray-bound and %d background Gaussians", nr, nb);
     *out = layout_of(nr, nb);
     return 0;
 }
@@ -346,16 +330,16 @@ int scg_ply_pack(const ScgModel* model, void* buffer, size_t buffer_bytes, void*
     a.color_pad = (int)((l.total - (l.color_offset + l.color_bytes)) / 4);
     a.campos = nullptr;
     const int64_t blocks = (int64_t)a.ray_tiles + a.bg_tiles + a.color_tiles;
-    if (blocks > 0x7fffffff) return fail(SCG_E_RANGE, "scg_ply_pack: %lld tiles are more than one launch takes", (long long)blocks);
+    if (blocks > 0x7fffffff) return g_err.fail(SCG_E_RANGE, "scg_ply_pack: %lld tiles are more than one launch takes", (long long)blocks);
     hipLaunchKernelGGL(ply_pack_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), a);
-    return check_hip(hipGetLastError(), "scg_ply_pack");
+    return g_err.check_hip(hipGetLastError(), "scg_ply_pack");
 }
 
 int scg_ply_pack_color_view(const ScgModel* model, int32_t sh_degree, const float* campos, void* buffer, size_t buffer_bytes,
                             void* stream) {
     if (int rc = check_model("scg_ply_pack_color_view", model)) return rc;
-    if (sh_degree < 0 || sh_degree > 3) return fail(SCG_E_RANGE, "scg_ply_pack_color_view: SH degree %d is not 0..3", sh_degree);
-    if (!campos) return fail(SCG_E_NULL, "scg_ply_pack_color_view: campos is NULL");
+    if (sh_degree < 0 || sh_degree > 3) return g_err.fail(SCG_E_RANGE, "scg_ply_pack_color_view: SH degree %d is not 0..3", sh_degree);
+    if (!campos) return g_err.fail(SCG_E_NULL, "scg_ply_pack_color_view: campos is NULL");
     const int64_t P = (int64_t)model->ray.count + model->bg.count;
     if (P == 0) return 0;
     const uint64_t bytes = ((uint64_t)P * kColor + 3u) & ~(uint64_t)3u;
@@ -376,26 +360,26 @@ int scg_ply_pack_color_view(const ScgModel* model, int32_t sh_degree, const floa
         case 2: hipLaunchKernelGGL(ply_color_view_kernel<2>, grid, block, 0, st, a); break;
         default: hipLaunchKernelGGL(ply_color_view_kernel<3>, grid, block, 0, st, a); break;
     }
-    return check_hip(hipGetLastError(), "scg_ply_pack_color_view");
+    return g_err.check_hip(hipGetLastError(), "scg_ply_pack_color_view");
 }
 
 int scg_ply_unpack(const void* upload, size_t body_bytes, const int32_t* table_host, int32_t rows, int32_t stride, int32_t bg,
                    const ScgModel* model, void* stream) {
     const char* who = "scg_ply_unpack";
-    if (!upload || !table_host) return fail(SCG_E_NULL, "%s: %s is NULL", who, upload ? "table_host" : "upload");
+    if (!upload || !table_host) return g_err.fail(SCG_E_NULL, "%s: %s is NULL", who, upload ? "table_host" : "upload");
     if (int rc = check_model(who, model)) return rc;
-    if (rows < 0) return fail(SCG_E_RANGE, "%s: %d rows", who, rows);
+    if (rows < 0) return g_err.fail(SCG_E_RANGE, "%s: %d rows", who, rows);
     if (stride < 1 || stride > SCG_PLY_MAX_STRIDE)
-        return fail(SCG_E_RANGE, "%s: a record of %d dwords is outside 1..%d", who, stride, SCG_PLY_MAX_STRIDE);
+        return g_err.fail(SCG_E_RANGE, "%s: a record of %d dwords is outside 1..%d", who, stride, SCG_PLY_MAX_STRIDE);
     if (body_bytes != (size_t)rows * (size_t)stride * 4)
-        return fail(SCG_E_SCRATCH, "%s: a body of %zu bytes is not %d rows of %d dwords", who, body_bytes, rows, stride);
+        return g_err.fail(SCG_E_SCRATCH, "%s: a body of %zu bytes is not %d rows of %d dwords", who, body_bytes, rows, stride);
     const int cols = bg ? kBg : kRay;
     for (int d = 0; d < cols; ++d)
         if (table_host[d] < 0 || table_host[d] >= stride)
-            return fail(SCG_E_RANGE, "%s: table[%d] = %d is outside the record of %d dwords", who, d, table_host[d], stride);
-    if (reinterpret_cast<uintptr_t>(upload) % 16) return fail(SCG_E_ALIGN, "%s: upload not 16-byte aligned", who);
+            return g_err.fail(SCG_E_RANGE, "%s: table[%d] = %d is outside the record of %d dwords", who, d, table_host[d], stride);
+    if (reinterpret_cast<uintptr_t>(upload) % 16) return g_err.fail(SCG_E_ALIGN, "%s: upload not 16-byte aligned", who);
     const ScgModelSet& s = bg ? model->bg : model->ray;
-    if (s.count != rows) return fail(SCG_E_RANGE, "%s: the model's set holds %d rows, the file %d", who, s.count, rows);
+    if (s.count != rows) return g_err.fail(SCG_E_RANGE, "%s: the model's set holds %d rows, the file %d", who, s.count, rows);
     if (rows == 0) return 0;
     const dim3 grid((unsigned)tiles_of(rows)), block(kBlock);
     const size_t lds = ((size_t)kRows * stride + cols) * 4;
@@ -403,7 +387,7 @@ int scg_ply_unpack(const void* upload, size_t body_bytes, const int32_t* table_h
     const uint32_t* up = static_cast<const uint32_t*>(upload);
     if (bg) hipLaunchKernelGGL(ply_unpack_kernel<true>, grid, block, lds, st, up, (size_t)rows, (int)stride, s);
     else hipLaunchKernelGGL(ply_unpack_kernel<false>, grid, block, lds, st, up, (size_t)rows, (int)stride, s);
-    return check_hip(hipGetLastError(), who);
+    return g_err.check_hip(hipGetLastError(), who);
 }
 
 }  // extern "C"

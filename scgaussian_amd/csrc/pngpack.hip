@@ -18,11 +18,10 @@
 //                      all four bytes are this block's, single bytes at the edges.
 //
 // No workgroup waits for another, nothing is allocated, nothing is read back; the same input gives the same bytes.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "../../include/png/scg_png.h"
 #include "compact.h"
+#include "host_align.h"
+#include "host_error.h"
 
 namespace scg {
 namespace {
@@ -42,23 +41,7 @@ constexpr uint32_t kMod = 65521u;
 constexpr int kWinWords = 4096;                    // the encode kernel's LDS window of the block: 16 KiB
 static_assert(kT == kBlock && kSeg == 128 && kKeys == 2 * kT && kKeys >= kSyms, "a 128-bit start mask per thread, a key pair per thread");
 
-thread_local char g_png_err[512] = "";
-
-int png_fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_png_err, sizeof(g_png_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int png_check_hip(hipError_t e, const char* what) {
-    if (e == hipSuccess) return 0;
-    snprintf(g_png_err, sizeof(g_png_err), "%s: %s (hipError %d)", what, hipGetErrorString(e), (int)e);
-    return (int)e;
-}
-
-uint64_t align16(uint64_t v) { return (v + 15u) & ~(uint64_t)15u; }
+thread_local ErrorText g_err = {};
 
 struct PngArgs {
     int images, chunks, filter, gray_as_rgb;
@@ -606,29 +589,29 @@ bool filter_ok(int f) { return f == SCG_PNG_FILTER_NONE || f == SCG_PNG_FILTER_S
 // The workspace's regions from images and chunks.
 void place(ScgPngLayout* l) {
     l->lengths_offset = 0u;
-    l->info_offset = align16(l->lengths_offset + l->chunks * kLens);
-    l->base_offset = align16(l->info_offset + l->chunks * sizeof(ScgPngChunkInfo));
-    l->scan_offset = align16(l->base_offset + 4u * (l->chunks + 1u));
-    l->table_offset = align16(l->scan_offset + 4u * l->images);
+    l->info_offset = align_to<16>(l->lengths_offset + l->chunks * kLens);
+    l->base_offset = align_to<16>(l->info_offset + l->chunks * sizeof(ScgPngChunkInfo));
+    l->scan_offset = align_to<16>(l->base_offset + 4u * (l->chunks + 1u));
+    l->table_offset = align_to<16>(l->scan_offset + 4u * l->images);
     l->table_bytes = 8u * (l->images + 1u);
-    l->workspace_bytes = align16(l->table_offset + l->table_bytes);
+    l->workspace_bytes = align_to<16>(l->table_offset + l->table_bytes);
 }
 
 // The layout and the two tables from the sizes; who == nullptr: no message.
 int layout_of(const char* who, int64_t n, const int32_t* hwc, int gray_as_rgb, ScgPngLayout* l, ScgPngImage* images, ScgPngChunk* chunks) {
-    if (n < 0 || n > SCG_PNG_MAX_IMAGES) return who ? png_fail(SCG_E_RANGE, "%s: %lld images (0..%d)", who, (long long)n, SCG_PNG_MAX_IMAGES) : SCG_E_RANGE;
-    if (n > 0 && !hwc) return who ? png_fail(SCG_E_NULL, "%s: hwc is NULL", who) : SCG_E_NULL;
-    if (gray_as_rgb != 0 && gray_as_rgb != 1) return who ? png_fail(SCG_E_RANGE, "%s: gray_as_rgb = %d (0 or 1)", who, gray_as_rgb) : SCG_E_RANGE;
+    if (n < 0 || n > SCG_PNG_MAX_IMAGES) return who ? g_err.fail(SCG_E_RANGE, "%s: %lld images (0..%d)", who, (long long)n, SCG_PNG_MAX_IMAGES) : SCG_E_RANGE;
+    if (n > 0 && !hwc) return who ? g_err.fail(SCG_E_NULL, "%s: hwc is NULL", who) : SCG_E_NULL;
+    if (gray_as_rgb != 0 && gray_as_rgb != 1) return who ? g_err.fail(SCG_E_RANGE, "%s: gray_as_rgb = %d (0 or 1)", who, gray_as_rgb) : SCG_E_RANGE;
     uint64_t nchunks = 0, capacity = 0;
     for (int64_t i = 0; i < n; ++i) {
         const int32_t H = hwc[3 * i], W = hwc[3 * i + 1], C = hwc[3 * i + 2];
         if (H < 1 || W < 1 || H > SCG_PNG_MAX_DIM || W > SCG_PNG_MAX_DIM)
-            return who ? png_fail(SCG_E_RANGE, "%s: image %lld of %d x %d pixels (H, W must be 1..%d)", who, (long long)i, W, H, SCG_PNG_MAX_DIM) : SCG_E_RANGE;
-        if (C != 1 && C != 3) return who ? png_fail(SCG_E_RANGE, "%s: image %lld has %d channels (1 or 3)", who, (long long)i, C) : SCG_E_RANGE;
+            return who ? g_err.fail(SCG_E_RANGE, "%s: image %lld of %d x %d pixels (H, W must be 1..%d)", who, (long long)i, W, H, SCG_PNG_MAX_DIM) : SCG_E_RANGE;
+        if (C != 1 && C != 3) return who ? g_err.fail(SCG_E_RANGE, "%s: image %lld has %d channels (1 or 3)", who, (long long)i, C) : SCG_E_RANGE;
         const uint64_t bpp = (C == 3 || gray_as_rgb) ? 3u : 1u;
         const uint64_t S = (uint64_t)H * (1u + (uint64_t)W * bpp);
         if (S > SCG_PNG_MAX_STREAM)
-            return who ? png_fail(SCG_E_RANGE, "%s: image %lld has a filtered stream of %llu bytes (< 2^31)", who, (long long)i, (unsigned long long)S) : SCG_E_RANGE;
+            return who ? g_err.fail(SCG_E_RANGE, "%s: image %lld has a filtered stream of %llu bytes (< 2^31)", who, (long long)i, (unsigned long long)S) : SCG_E_RANGE;
         const uint64_t k = (S + SCG_PNG_CHUNK - 1u) / SCG_PNG_CHUNK;
         if (images) {
             ScgPngImage& im = images[i];
@@ -644,7 +627,7 @@ int layout_of(const char* who, int64_t n, const int32_t* hwc, int gray_as_rgb, S
         nchunks += k;
         capacity += SCG_PNG_ALIGN + S + 5u * k + 6u;
         if (capacity > 0xFFFFFFFFull || nchunks > 0x7FFFFFFFull)
-            return who ? png_fail(SCG_E_RANGE, "%s: the batch needs more than 2^32 - 1 bytes of output", who) : SCG_E_RANGE;
+            return who ? g_err.fail(SCG_E_RANGE, "%s: the batch needs more than 2^32 - 1 bytes of output", who) : SCG_E_RANGE;
     }
     l->images = (uint64_t)n;
     l->chunks = nchunks;
@@ -660,7 +643,7 @@ using namespace scg;
 
 extern "C" {
 
-const char* scg_png_last_error(void) { return g_png_err; }
+const char* scg_png_last_error(void) { return g_err.text; }
 int32_t scg_png_abi_version(void) { return SCG_PNG_ABI_VERSION; }
 
 size_t scg_png_struct_bytes(int32_t which) {
@@ -675,7 +658,7 @@ size_t scg_png_struct_bytes(int32_t which) {
 }
 
 int scg_png_layout(int32_t n, const int32_t* hwc, int32_t gray_as_rgb, ScgPngLayout* out, ScgPngImage* images_out, ScgPngChunk* chunks_out) {
-    if (!out) return png_fail(SCG_E_NULL, "scg_png_layout: out is NULL");
+    if (!out) return g_err.fail(SCG_E_NULL, "scg_png_layout: out is NULL");
     ScgPngLayout l;
     if (int rc = layout_of("scg_png_layout", n, hwc, gray_as_rgb, &l, images_out, chunks_out)) return rc;
     *out = l;
@@ -684,14 +667,14 @@ int scg_png_layout(int32_t n, const int32_t* hwc, int32_t gray_as_rgb, ScgPngLay
 
 int scg_png_encode(const ScgPngEncode* p, void* out, size_t out_bytes, void* workspace, size_t workspace_bytes, void* stream) {
     const char* who = "scg_png_encode";
-    if (!p) return png_fail(SCG_E_NULL, "%s: args is NULL", who);
+    if (!p) return g_err.fail(SCG_E_NULL, "%s: args is NULL", who);
     if (p->struct_bytes != (int32_t)sizeof(ScgPngEncode))
-        return png_fail(SCG_E_RANGE, "%s: struct_bytes = %d, the library's ScgPngEncode has %zu", who, p->struct_bytes, sizeof(ScgPngEncode));
-    if (p->images < 1 || p->images > SCG_PNG_MAX_IMAGES) return png_fail(SCG_E_RANGE, "%s: images = %d is outside 1..%d", who, p->images, SCG_PNG_MAX_IMAGES);
-    if (!filter_ok(p->filter)) return png_fail(SCG_E_RANGE, "%s: filter = %d (0 None, 1 Sub, 2 Up, 4 Paeth)", who, p->filter);
-    if (p->gray_as_rgb != 0 && p->gray_as_rgb != 1) return png_fail(SCG_E_RANGE, "%s: gray_as_rgb = %d (0 or 1)", who, p->gray_as_rgb);
-    if (!p->images_host || !p->images_dev) return png_fail(SCG_E_NULL, "%s: an image table is NULL", who);
-    if (!p->chunks_dev) return png_fail(SCG_E_NULL, "%s: the chunk table is NULL", who);
+        return g_err.fail(SCG_E_RANGE, "%s: struct_bytes = %d, the library's ScgPngEncode has %zu", who, p->struct_bytes, sizeof(ScgPngEncode));
+    if (p->images < 1 || p->images > SCG_PNG_MAX_IMAGES) return g_err.fail(SCG_E_RANGE, "%s: images = %d is outside 1..%d", who, p->images, SCG_PNG_MAX_IMAGES);
+    if (!filter_ok(p->filter)) return g_err.fail(SCG_E_RANGE, "%s: filter = %d (0 None, 1 Sub, 2 Up, 4 Paeth)", who, p->filter);
+    if (p->gray_as_rgb != 0 && p->gray_as_rgb != 1) return g_err.fail(SCG_E_RANGE, "%s: gray_as_rgb = %d (0 or 1)", who, p->gray_as_rgb);
+    if (!p->images_host || !p->images_dev) return g_err.fail(SCG_E_NULL, "%s: an image table is NULL", who);
+    if (!p->chunks_dev) return g_err.fail(SCG_E_NULL, "%s: the chunk table is NULL", who);
     // the image table: the one the layout gives for its own sizes, record by record
     ScgPngLayout l;
     {
@@ -703,11 +686,11 @@ int scg_png_encode(const ScgPngEncode* p, void* out, size_t out_bytes, void* wor
             const ScgPngImage& x = p->images_host[i];
             hwc[0] = x.H; hwc[1] = x.W; hwc[2] = x.channels;
             if (layout_of(nullptr, 1, hwc, p->gray_as_rgb, &one, &want, nullptr))
-                return png_fail(SCG_E_RANGE, "%s: image %d of %d x %d pixels and %d channels is outside the limits", who, i, x.W, x.H, x.channels);
+                return g_err.fail(SCG_E_RANGE, "%s: image %d of %d x %d pixels and %d channels is outside the limits", who, i, x.W, x.H, x.channels);
             if ((uint64_t)x.first_chunk != first || x.chunks != want.chunks || x.stream_bytes != want.stream_bytes)
-                return png_fail(SCG_E_RANGE, "%s: image %d is (first chunk %d, chunks %d, stream %d), the layout gives (%llu, %d, %d)", who, i,
+                return g_err.fail(SCG_E_RANGE, "%s: image %d is (first chunk %d, chunks %d, stream %d), the layout gives (%llu, %d, %d)", who, i,
                                 x.first_chunk, x.chunks, x.stream_bytes, (unsigned long long)first, want.chunks, want.stream_bytes);
-            if (!x.src) return png_fail(SCG_E_NULL, "%s: image %d has no pixels (src is 0)", who, i);
+            if (!x.src) return g_err.fail(SCG_E_NULL, "%s: image %d has no pixels (src is 0)", who, i);
             first += (uint64_t)want.chunks;
         }
         // the sums: the same arithmetic over all images
@@ -715,21 +698,21 @@ int scg_png_encode(const ScgPngEncode* p, void* out, size_t out_bytes, void* wor
         for (int i = 0; i < p->images; ++i)
             capacity += SCG_PNG_ALIGN + (uint64_t)p->images_host[i].stream_bytes + 5u * (uint64_t)p->images_host[i].chunks + 6u;
         if (capacity > 0xFFFFFFFFull || first > 0x7FFFFFFFull)
-            return png_fail(SCG_E_RANGE, "%s: the batch needs more than 2^32 - 1 bytes of output", who);
+            return g_err.fail(SCG_E_RANGE, "%s: the batch needs more than 2^32 - 1 bytes of output", who);
         l.images = (uint64_t)p->images;
         l.chunks = first;
         l.capacity = capacity;
         place(&l);
     }
-    if (!out) return png_fail(SCG_E_NULL, "%s: out is NULL", who);
-    if (out_bytes < l.capacity) return png_fail(SCG_E_SCRATCH, "%s: out of %zu bytes < %llu", who, out_bytes, (unsigned long long)l.capacity);
-    if (reinterpret_cast<uintptr_t>(out) % 16) return png_fail(SCG_E_ALIGN, "%s: out not 16-byte aligned", who);
-    if (!workspace) return png_fail(SCG_E_NULL, "%s: workspace is NULL", who);
+    if (!out) return g_err.fail(SCG_E_NULL, "%s: out is NULL", who);
+    if (out_bytes < l.capacity) return g_err.fail(SCG_E_SCRATCH, "%s: out of %zu bytes < %llu", who, out_bytes, (unsigned long long)l.capacity);
+    if (reinterpret_cast<uintptr_t>(out) % 16) return g_err.fail(SCG_E_ALIGN, "%s: out not 16-byte aligned", who);
+    if (!workspace) return g_err.fail(SCG_E_NULL, "%s: workspace is NULL", who);
     if (workspace_bytes < l.workspace_bytes)
-        return png_fail(SCG_E_SCRATCH, "%s: workspace of %zu bytes < %llu", who, workspace_bytes, (unsigned long long)l.workspace_bytes);
-    if (reinterpret_cast<uintptr_t>(workspace) % 16) return png_fail(SCG_E_ALIGN, "%s: workspace not 16-byte aligned", who);
+        return g_err.fail(SCG_E_SCRATCH, "%s: workspace of %zu bytes < %llu", who, workspace_bytes, (unsigned long long)l.workspace_bytes);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16) return g_err.fail(SCG_E_ALIGN, "%s: workspace not 16-byte aligned", who);
     if (reinterpret_cast<uintptr_t>(p->images_dev) % 8 || reinterpret_cast<uintptr_t>(p->chunks_dev) % 4)
-        return png_fail(SCG_E_ALIGN, "%s: a device table is not aligned to its records", who);
+        return g_err.fail(SCG_E_ALIGN, "%s: a device table is not aligned to its records", who);
 
     PngArgs a;
     a.images = p->images;
@@ -748,11 +731,11 @@ int scg_png_encode(const ScgPngEncode* p, void* out, size_t out_bytes, void* wor
     a.capacity = l.capacity;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(png_count_kernel, dim3((unsigned)l.chunks), dim3(kT), 0, st, a);
-    if (int rc = png_check_hip(hipGetLastError(), "png_count")) return rc;
+    if (int rc = g_err.check_hip(hipGetLastError(), "png_count")) return rc;
     hipLaunchKernelGGL(png_scan_kernel, dim3(1), dim3(kT), 0, st, a);
-    if (int rc = png_check_hip(hipGetLastError(), "png_scan")) return rc;
+    if (int rc = g_err.check_hip(hipGetLastError(), "png_scan")) return rc;
     hipLaunchKernelGGL(png_encode_kernel, dim3((unsigned)l.chunks), dim3(kT), 0, st, a);
-    return png_check_hip(hipGetLastError(), "png_encode");
+    return g_err.check_hip(hipGetLastError(), "png_encode");
 }
 
 }  // extern "C"

@@ -22,11 +22,11 @@
 //
 // Offsets are 64-bit (twenty 36 MB images exceed 2^31 bytes).  No atomics, no host read, no workgroup waits on another.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/img/scg_resample.h"
+#include "host_align.h"
+#include "host_error.h"
 
 namespace scg {
 namespace {
@@ -44,25 +44,9 @@ constexpr size_t kLdsBudget = 40 * 1024;               // per workgroup, so that
 static_assert(kBlock % kStrip == 0 && kStrip <= kWave && (kStrip * 3) % 4 == 0, "a strip of either pixel size is whole dwords");
 static_assert(kVTile == 4 * kBlock, "4 bytes per lane");
 
-thread_local char g_err[512] = "";
+thread_local ErrorText g_err = {};
 
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int check_hip(hipError_t e, const char* what) {
-    if (e == hipSuccess) return 0;
-    snprintf(g_err, sizeof(g_err), "%s: %s (hipError %d)", what, hipGetErrorString(e), (int)e);
-    return (int)e;
-}
-
-size_t pitch_of(int32_t wout, int32_t channels) {
-    return ((size_t)wout * channels + kPitchAlign - 1) / kPitchAlign * kPitchAlign;
-}
+size_t pitch_of(int32_t wout, int32_t channels) { return align_up((size_t)wout * channels, kPitchAlign); }
 
 // ---- device side ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t to_byte(int acc) {
@@ -253,7 +237,7 @@ using namespace scg;
 
 extern "C" {
 
-const char* scg_img_last_error(void) { return g_err; }
+const char* scg_img_last_error(void) { return g_err.text; }
 int32_t scg_img_abi_version(void) { return SCG_IMG_ABI_VERSION; }
 
 size_t scg_resample_pitch(int32_t wout, int32_t channels) {
@@ -272,35 +256,35 @@ int scg_resample_u8(const uint8_t* src, int32_t n, int32_t hin, int32_t win, int
                     void* mid, size_t mid_bytes, uint8_t* out, size_t out_bytes, float* out_float, size_t out_float_bytes,
                     void* stream) {
     const char* who = "scg_resample_u8";
-    if (!src || !out) return fail(SCG_E_NULL, "%s: %s is NULL", who, src ? "out" : "src");
+    if (!src || !out) return g_err.fail(SCG_E_NULL, "%s: %s is NULL", who, src ? "out" : "src");
     if (!size_ok(n) || !size_ok(hin) || !size_ok(win) || !size_ok(hout) || !size_ok(wout))
-        return fail(SCG_E_RANGE, "%s: %d images of %d x %d to %d x %d: every size must be 1..%d", who, n, win, hin, wout, hout,
+        return g_err.fail(SCG_E_RANGE, "%s: %d images of %d x %d to %d x %d: every size must be 1..%d", who, n, win, hin, wout, hout,
                     SCG_RESAMPLE_MAX_SIZE);
-    if (channels != 1 && channels != 3) return fail(SCG_E_RANGE, "%s: %d channels, not 1 or 3", who, channels);
+    if (channels != 1 && channels != 3) return g_err.fail(SCG_E_RANGE, "%s: %d channels, not 1 or 3", who, channels);
     const bool horizontal = wout != win, vertical = hout != hin;
     if (horizontal) {
-        if (!hbounds || !hcoeffs) return fail(SCG_E_NULL, "%s: the width changes and its tables are NULL", who);
+        if (!hbounds || !hcoeffs) return g_err.fail(SCG_E_NULL, "%s: the width changes and its tables are NULL", who);
         if (hksize < 1 || hksize > SCG_RESAMPLE_MAX_KSIZE)
-            return fail(SCG_E_RANGE, "%s: hksize %d is outside 1..%d", who, hksize, SCG_RESAMPLE_MAX_KSIZE);
+            return g_err.fail(SCG_E_RANGE, "%s: hksize %d is outside 1..%d", who, hksize, SCG_RESAMPLE_MAX_KSIZE);
     }
     if (vertical) {
-        if (!vbounds || !vcoeffs) return fail(SCG_E_NULL, "%s: the height changes and its tables are NULL", who);
+        if (!vbounds || !vcoeffs) return g_err.fail(SCG_E_NULL, "%s: the height changes and its tables are NULL", who);
         if (vksize < 1 || vksize > SCG_RESAMPLE_MAX_KSIZE)
-            return fail(SCG_E_RANGE, "%s: vksize %d is outside 1..%d", who, vksize, SCG_RESAMPLE_MAX_KSIZE);
+            return g_err.fail(SCG_E_RANGE, "%s: vksize %d is outside 1..%d", who, vksize, SCG_RESAMPLE_MAX_KSIZE);
     }
     const size_t pitch = pitch_of(wout, channels);
     if (horizontal) {
         const size_t need = (size_t)n * hin * pitch;
-        if (!mid) return fail(SCG_E_NULL, "%s: the width changes and mid is NULL", who);
-        if (mid_bytes < need) return fail(SCG_E_SCRATCH, "%s: mid of %zu bytes < %zu", who, mid_bytes, need);
-        if (reinterpret_cast<uintptr_t>(mid) % kPitchAlign) return fail(SCG_E_ALIGN, "%s: mid not %d-byte aligned", who, kPitchAlign);
+        if (!mid) return g_err.fail(SCG_E_NULL, "%s: the width changes and mid is NULL", who);
+        if (mid_bytes < need) return g_err.fail(SCG_E_SCRATCH, "%s: mid of %zu bytes < %zu", who, mid_bytes, need);
+        if (reinterpret_cast<uintptr_t>(mid) % kPitchAlign) return g_err.fail(SCG_E_ALIGN, "%s: mid not %d-byte aligned", who, kPitchAlign);
     }
     const size_t out_need = (size_t)n * hout * wout * channels;
-    if (out_bytes < out_need) return fail(SCG_E_SCRATCH, "%s: out of %zu bytes < %zu", who, out_bytes, out_need);
+    if (out_bytes < out_need) return g_err.fail(SCG_E_SCRATCH, "%s: out of %zu bytes < %zu", who, out_bytes, out_need);
     if (out_float) {
         if (out_float_bytes < out_need * 4)
-            return fail(SCG_E_SCRATCH, "%s: out_float of %zu bytes < %zu", who, out_float_bytes, out_need * 4);
-        if (reinterpret_cast<uintptr_t>(out_float) % 4) return fail(SCG_E_ALIGN, "%s: out_float not 4-byte aligned", who);
+            return g_err.fail(SCG_E_SCRATCH, "%s: out_float of %zu bytes < %zu", who, out_float_bytes, out_need * 4);
+        if (reinterpret_cast<uintptr_t>(out_float) % 4) return g_err.fail(SCG_E_ALIGN, "%s: out_float not 4-byte aligned", who);
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
 
@@ -329,11 +313,11 @@ int scg_resample_u8(const uint8_t* src, int32_t n, int32_t hin, int32_t win, int
         if (rt > (size_t)kStripRows) rt = kStripRows;
         h.rt = (int)rt;
         const size_t lds = fixed + rt * per_row;
-        if (lds > 64 * 1024) return fail(SCG_E_RANGE, "%s: a strip of %d -> %d needs %zu bytes of LDS", who, win, wout, lds);
+        if (lds > 64 * 1024) return g_err.fail(SCG_E_RANGE, "%s: a strip of %d -> %d needs %zu bytes of LDS", who, win, wout, lds);
         const dim3 grid((unsigned)((wout + kStrip - 1) / kStrip), (unsigned)((hin + kStripRows - 1) / kStripRows), (unsigned)n);
         if (channels == 3) hipLaunchKernelGGL(resample_h_kernel<3>, grid, dim3(kBlock), lds, st, h);
         else hipLaunchKernelGGL(resample_h_kernel<1>, grid, dim3(kBlock), lds, st, h);
-        if (int rc = check_hip(hipGetLastError(), who)) return rc;
+        if (int rc = g_err.check_hip(hipGetLastError(), who)) return rc;
     }
 
     VArgs v;
@@ -357,7 +341,7 @@ int scg_resample_u8(const uint8_t* src, int32_t n, int32_t hin, int32_t win, int
         if (dword_in) hipLaunchKernelGGL((resample_v_kernel<1, true>), grid, dim3(kBlock), 0, st, v);
         else hipLaunchKernelGGL((resample_v_kernel<1, false>), grid, dim3(kBlock), 0, st, v);
     }
-    return check_hip(hipGetLastError(), who);
+    return g_err.check_hip(hipGetLastError(), who);
 }
 
 }  // extern "C"

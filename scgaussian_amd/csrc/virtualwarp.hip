@@ -16,10 +16,8 @@
 //
 // No scatter, no atomics, no allocation, no host read.  Compiled with -ffp-contract=off.  fp32 in, fp32 out, fp64 in between (the
 // header says why): the kernels are bound by their gathers, not by the fp64 rate.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "../../include/vw/scg_virtualwarp.h"
+#include "host_error.h"
 #include "reduce.h"
 
 #pragma clang fp contract(off)
@@ -31,21 +29,7 @@ constexpr int kSide = SCG_VW_TILE;
 constexpr int kNW = kBlock / kWave;
 static_assert(kSide * kSide == kBlock && SCG_VW_SMOOTH_PIXELS == kBlock, "one pixel per thread");
 
-thread_local char g_vw_err[512] = "";
-
-int vw_fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_vw_err, sizeof(g_vw_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int vw_check_hip(hipError_t e, const char* what) {
-    if (e == hipSuccess) return 0;
-    snprintf(g_vw_err, sizeof(g_vw_err), "%s: %s (hipError %d)", what, hipGetErrorString(e), (int)e);
-    return (int)e;
-}
+thread_local ErrorText g_err = {};
 
 struct WarpLayout {
     size_t hw, y, dyd, partial, coef, total;      // offsets and total in BYTES: the fp64 regions first
@@ -353,16 +337,10 @@ __global__ __launch_bounds__(kBlock) void vw_smooth_backward_kernel(SmoothArgs a
     a.d_depth[e] = g;
 }
 
-int check_ptr(const char* who, const void* p, const char* name, size_t align) {
-    if (!p) return vw_fail(SCG_E_NULL, "%s: %s is NULL", who, name);
-    if (reinterpret_cast<uintptr_t>(p) % align) return vw_fail(SCG_E_ALIGN, "%s: %s is not %zu-byte aligned", who, name, align);
-    return 0;
-}
-
 int check_warp_sizes(const char* who, int32_t nv, int32_t H, int32_t W, WarpLayout* l) {
-    if (nv < 1 || nv > SCG_VW_MAX_VIEWS) return vw_fail(SCG_E_RANGE, "%s: nv = %d is outside 1..%d", who, nv, SCG_VW_MAX_VIEWS);
+    if (nv < 1 || nv > SCG_VW_MAX_VIEWS) return g_err.fail(SCG_E_RANGE, "%s: nv = %d is outside 1..%d", who, nv, SCG_VW_MAX_VIEWS);
     if (H < SCG_VW_MIN_DIM || W < SCG_VW_MIN_DIM || H > SCG_VW_MAX_DIM || W > SCG_VW_MAX_DIM)
-        return vw_fail(SCG_E_RANGE, "%s: %d x %d pixels (H, W must be %d..%d: the 5x5 window reflects by 2)", who, W, H, SCG_VW_MIN_DIM,
+        return g_err.fail(SCG_E_RANGE, "%s: %d x %d pixels (H, W must be %d..%d: the 5x5 window reflects by 2)", who, W, H, SCG_VW_MIN_DIM,
                        SCG_VW_MAX_DIM);
     warp_layout(nv, H, W, l);
     return 0;
@@ -370,8 +348,8 @@ int check_warp_sizes(const char* who, int32_t nv, int32_t H, int32_t W, WarpLayo
 
 int check_smooth_sizes(const char* who, int32_t H, int32_t W, int32_t C) {
     if (H < 1 || W < 1 || H > SCG_VW_MAX_DIM || W > SCG_VW_MAX_DIM)
-        return vw_fail(SCG_E_RANGE, "%s: %d x %d pixels (H, W must be 1..%d)", who, W, H, SCG_VW_MAX_DIM);
-    if (C < 0 || C > SCG_VW_MAX_GUIDE_CHANNELS) return vw_fail(SCG_E_RANGE, "%s: C = %d is outside 0..%d", who, C, SCG_VW_MAX_GUIDE_CHANNELS);
+        return g_err.fail(SCG_E_RANGE, "%s: %d x %d pixels (H, W must be 1..%d)", who, W, H, SCG_VW_MAX_DIM);
+    if (C < 0 || C > SCG_VW_MAX_GUIDE_CHANNELS) return g_err.fail(SCG_E_RANGE, "%s: C = %d is outside 0..%d", who, C, SCG_VW_MAX_GUIDE_CHANNELS);
     return 0;
 }
 
@@ -384,7 +362,7 @@ using namespace scg;
 
 extern "C" {
 
-const char* scg_vw_last_error(void) { return g_vw_err; }
+const char* scg_vw_last_error(void) { return g_err.text; }
 int32_t scg_vw_abi_version(void) { return SCG_VW_ABI_VERSION; }
 
 size_t scg_vw_warp_scratch_bytes(int32_t nv, int32_t H, int32_t W) {
@@ -398,18 +376,18 @@ int scg_vw_warp_forward(int32_t nv, int32_t H, int32_t W, const float* virtual_i
     const char* who = "scg_vw_warp_forward";
     WarpLayout l;
     if (int rc = check_warp_sizes(who, nv, H, W, &l)) return rc;
-    if (int rc = check_ptr(who, virtual_img, "virtual_img", 4)) return rc;
-    if (int rc = check_ptr(who, virtual_depth, "virtual_depth", 4)) return rc;
-    if (int rc = check_ptr(who, vir_mask, "vir_mask", 1)) return rc;
-    if (int rc = check_ptr(who, img_colors, "img_colors", 4)) return rc;
-    if (int rc = check_ptr(who, records, "records", 4)) return rc;
-    if (int rc = check_ptr(who, loss, "loss", 4)) return rc;
-    if (int rc = check_ptr(who, loss_map, "loss_map", 4)) return rc;
-    if (int rc = check_ptr(who, winner, "winner", 1)) return rc;
-    if (int rc = check_ptr(who, in_bounds, "in_bounds", 1)) return rc;
-    if (!scratch) return vw_fail(SCG_E_NULL, "%s: scratch is NULL", who);
-    if (scratch_bytes < l.total) return vw_fail(SCG_E_SCRATCH, "%s: scratch of %zu bytes < %zu", who, scratch_bytes, l.total);
-    if (reinterpret_cast<uintptr_t>(scratch) % 16) return vw_fail(SCG_E_ALIGN, "%s: scratch is not 16-byte aligned", who);
+    if (int rc = g_err.check_ptr(who, virtual_img, "virtual_img", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, virtual_depth, "virtual_depth", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, vir_mask, "vir_mask", 1)) return rc;
+    if (int rc = g_err.check_ptr(who, img_colors, "img_colors", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, records, "records", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, loss, "loss", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, loss_map, "loss_map", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, winner, "winner", 1)) return rc;
+    if (int rc = g_err.check_ptr(who, in_bounds, "in_bounds", 1)) return rc;
+    if (!scratch) return g_err.fail(SCG_E_NULL, "%s: scratch is NULL", who);
+    if (scratch_bytes < l.total) return g_err.fail(SCG_E_SCRATCH, "%s: scratch of %zu bytes < %zu", who, scratch_bytes, l.total);
+    if (reinterpret_cast<uintptr_t>(scratch) % 16) return g_err.fail(SCG_E_ALIGN, "%s: scratch is not 16-byte aligned", who);
 
     WarpArgs a = {};
     a.nv = nv; a.H = H; a.W = W; a.tiles_x = l.tiles_x; a.tiles = l.tiles_x * l.tiles_y;
@@ -420,11 +398,11 @@ int scg_vw_warp_forward(int32_t nv, int32_t H, int32_t W, const float* virtual_i
     a.partial = reinterpret_cast<double*>(s + l.partial); a.coef = reinterpret_cast<float*>(s + l.coef);
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(vw_warp_kernel, dim3((unsigned)a.tiles, (unsigned)nv), dim3(kBlock), 0, st, a);
-    if (int rc = vw_check_hip(hipGetLastError(), "vw_warp")) return rc;
+    if (int rc = g_err.check_hip(hipGetLastError(), "vw_warp")) return rc;
     hipLaunchKernelGGL(vw_ssim_kernel, dim3((unsigned)a.tiles), dim3(kBlock), 0, st, a);
-    if (int rc = vw_check_hip(hipGetLastError(), "vw_ssim")) return rc;
+    if (int rc = g_err.check_hip(hipGetLastError(), "vw_ssim")) return rc;
     hipLaunchKernelGGL(vw_fold_kernel, dim3(1), dim3(kBlock), 0, st, (const double*)a.partial, a.tiles, (double)l.hw, loss);
-    return vw_check_hip(hipGetLastError(), "vw_fold");
+    return g_err.check_hip(hipGetLastError(), "vw_fold");
 }
 
 int scg_vw_warp_backward(int32_t nv, int32_t H, int32_t W, const float* virtual_img, const float* upstream, const int8_t* winner,
@@ -432,14 +410,14 @@ int scg_vw_warp_backward(int32_t nv, int32_t H, int32_t W, const float* virtual_
     const char* who = "scg_vw_warp_backward";
     WarpLayout l;
     if (int rc = check_warp_sizes(who, nv, H, W, &l)) return rc;
-    if (int rc = check_ptr(who, virtual_img, "virtual_img", 4)) return rc;
-    if (int rc = check_ptr(who, upstream, "upstream", 4)) return rc;
-    if (int rc = check_ptr(who, winner, "winner", 1)) return rc;
-    if (int rc = check_ptr(who, d_img, "d_img", 4)) return rc;
-    if (int rc = check_ptr(who, d_depth, "d_depth", 4)) return rc;
-    if (!scratch) return vw_fail(SCG_E_NULL, "%s: scratch is NULL", who);
-    if (scratch_bytes < l.total) return vw_fail(SCG_E_SCRATCH, "%s: scratch of %zu bytes < %zu", who, scratch_bytes, l.total);
-    if (reinterpret_cast<uintptr_t>(scratch) % 16) return vw_fail(SCG_E_ALIGN, "%s: scratch is not 16-byte aligned", who);
+    if (int rc = g_err.check_ptr(who, virtual_img, "virtual_img", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, upstream, "upstream", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, winner, "winner", 1)) return rc;
+    if (int rc = g_err.check_ptr(who, d_img, "d_img", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, d_depth, "d_depth", 4)) return rc;
+    if (!scratch) return g_err.fail(SCG_E_NULL, "%s: scratch is NULL", who);
+    if (scratch_bytes < l.total) return g_err.fail(SCG_E_SCRATCH, "%s: scratch of %zu bytes < %zu", who, scratch_bytes, l.total);
+    if (reinterpret_cast<uintptr_t>(scratch) % 16) return g_err.fail(SCG_E_ALIGN, "%s: scratch is not 16-byte aligned", who);
 
     WarpArgs a = {};
     a.nv = nv; a.H = H; a.W = W; a.tiles_x = l.tiles_x; a.tiles = l.tiles_x * l.tiles_y;
@@ -449,7 +427,7 @@ int scg_vw_warp_backward(int32_t nv, int32_t H, int32_t W, const float* virtual_
     a.partial = reinterpret_cast<double*>(s + l.partial); a.coef = reinterpret_cast<float*>(s + l.coef);
     a.d_img = d_img; a.d_depth = d_depth;
     hipLaunchKernelGGL(vw_backward_kernel, dim3((unsigned)a.tiles), dim3(kBlock), 0, static_cast<hipStream_t>(stream), a);
-    return vw_check_hip(hipGetLastError(), "vw_backward");
+    return g_err.check_hip(hipGetLastError(), "vw_backward");
 }
 
 size_t scg_vw_smooth_scratch_bytes(int32_t H, int32_t W) {
@@ -461,37 +439,37 @@ int scg_vw_smooth_forward(int32_t H, int32_t W, int32_t C, const float* depth, c
                           size_t scratch_bytes, void* stream) {
     const char* who = "scg_vw_smooth_forward";
     if (int rc = check_smooth_sizes(who, H, W, C)) return rc;
-    if (int rc = check_ptr(who, depth, "depth", 4)) return rc;
-    if (C == 0 && guide) return vw_fail(SCG_E_EXCLUSIVE, "%s: a guide with C = 0", who);
-    if (C > 0) if (int rc = check_ptr(who, guide, "guide", 4)) return rc;
-    if (int rc = check_ptr(who, loss, "loss", 4)) return rc;
-    if (int rc = check_ptr(who, scratch, "scratch", 8)) return rc;
+    if (int rc = g_err.check_ptr(who, depth, "depth", 4)) return rc;
+    if (C == 0 && guide) return g_err.fail(SCG_E_EXCLUSIVE, "%s: a guide with C = 0", who);
+    if (C > 0) if (int rc = g_err.check_ptr(who, guide, "guide", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, loss, "loss", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, scratch, "scratch", 8)) return rc;
     const size_t need = scg_vw_smooth_scratch_bytes(H, W);
-    if (scratch_bytes < need) return vw_fail(SCG_E_SCRATCH, "%s: scratch of %zu bytes < %zu", who, scratch_bytes, need);
+    if (scratch_bytes < need) return g_err.fail(SCG_E_SCRATCH, "%s: scratch of %zu bytes < %zu", who, scratch_bytes, need);
     SmoothArgs a = {};
     a.H = H; a.W = W; a.C = C; a.groups = smooth_groups(H, W);
     a.depth = depth; a.guide = guide; a.partial = static_cast<double*>(scratch); a.loss = loss;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(vw_smooth_kernel, dim3((unsigned)a.groups), dim3(kBlock), 0, st, a);
-    if (int rc = vw_check_hip(hipGetLastError(), "vw_smooth")) return rc;
+    if (int rc = g_err.check_hip(hipGetLastError(), "vw_smooth")) return rc;
     hipLaunchKernelGGL(vw_smooth_fold_kernel, dim3(1), dim3(kBlock), 0, st, a);
-    return vw_check_hip(hipGetLastError(), "vw_smooth_fold");
+    return g_err.check_hip(hipGetLastError(), "vw_smooth_fold");
 }
 
 int scg_vw_smooth_backward(int32_t H, int32_t W, int32_t C, const float* depth, const float* guide, const float* upstream,
                            float* d_depth, void* stream) {
     const char* who = "scg_vw_smooth_backward";
     if (int rc = check_smooth_sizes(who, H, W, C)) return rc;
-    if (int rc = check_ptr(who, depth, "depth", 4)) return rc;
-    if (C == 0 && guide) return vw_fail(SCG_E_EXCLUSIVE, "%s: a guide with C = 0", who);
-    if (C > 0) if (int rc = check_ptr(who, guide, "guide", 4)) return rc;
-    if (int rc = check_ptr(who, upstream, "upstream", 4)) return rc;
-    if (int rc = check_ptr(who, d_depth, "d_depth", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, depth, "depth", 4)) return rc;
+    if (C == 0 && guide) return g_err.fail(SCG_E_EXCLUSIVE, "%s: a guide with C = 0", who);
+    if (C > 0) if (int rc = g_err.check_ptr(who, guide, "guide", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, upstream, "upstream", 4)) return rc;
+    if (int rc = g_err.check_ptr(who, d_depth, "d_depth", 4)) return rc;
     SmoothArgs a = {};
     a.H = H; a.W = W; a.C = C; a.groups = smooth_groups(H, W);
     a.depth = depth; a.guide = guide; a.upstream = upstream; a.d_depth = d_depth;
     hipLaunchKernelGGL(vw_smooth_backward_kernel, dim3((unsigned)a.groups), dim3(kBlock), 0, static_cast<hipStream_t>(stream), a);
-    return vw_check_hip(hipGetLastError(), "vw_smooth_backward");
+    return g_err.check_hip(hipGetLastError(), "vw_smooth_backward");
 }
 
 }  // extern "C"

@@ -4,63 +4,18 @@ touching a GPU, and the Python operator mirrors the reference's error behaviour.
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 import torch
 
 import abi_text
+from abi_compare import ANY, TYPED, VOID, bound_structs, exported_names, prototype_differences, struct_differences
 from scgaussian_amd import _lib
 from scgaussian_amd._lib import ScgFrame
 from scgaussian_amd import rasterizer as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ABI = abi_text.read()
-
-# The C scalar types of the headers and their ctypes types.  (On the LP64 targets of this library ctypes has one class for int and
-# int32_t, and one for size_t and uint64_t; int32_t against int64_t, float against double and every count or order are told apart.)
-_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "size_t": C.c_size_t, "float": C.c_float,
-            "double": C.c_double, "uint8_t": C.c_uint8, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "char": C.c_char}
-
-
-def _matches(decl, ctype, structs, returned=False):
-    """Does the ctypes type stand for the C declaration?  structs: {name: ctypes class} for the struct types a header may name."""
-    if decl.array:
-        return (issubclass(ctype, C.Array) and ctype._length_ == decl.array
-                and _matches(decl._replace(array=0), ctype._type_, structs))
-    if decl.pointer == 0:
-        return ctype is (structs[decl.base] if decl.base in structs else _SCALARS.get(decl.base, False))
-    if returned and decl.base == "char":
-        return decl.pointer == 1 and ctype is C.c_char_p
-    if ctype is C.c_void_p:                                          # any pointer
-        return True
-    if decl.pointer == 2:
-        return decl.base == "void" and ctype is C.POINTER(C.c_void_p)
-    target = structs.get(decl.base, _SCALARS.get(decl.base))
-    return target is not None and ctype is C.POINTER(target)
-
-
-def _prototype_differences(fn, restype, argtypes, structs):
-    diffs = []
-    if not _matches(fn.ret, restype, structs, returned=True):
-        diffs.append(f"{fn.name} ({fn.header}): returns {fn.ret.base}{'*' * fn.ret.pointer}, bound as {restype}")
-    if len(fn.params) != len(argtypes):
-        diffs.append(f"{fn.name} ({fn.header}): {len(fn.params)} parameters, bound with {len(argtypes)}")
-    for i, (decl, ctype) in enumerate(zip(fn.params, argtypes)):
-        if not _matches(decl, ctype, structs):
-            diffs.append(f"{fn.name} ({fn.header}): parameter {i} is {decl}, bound as {ctype}")
-    return diffs
-
-
-def _struct_differences(name, fields, cls, structs):
-    bound = list(cls._fields_)
-    if [f.name for f in fields] != [n for n, _ in bound]:
-        return [f"{name}: members {[f.name for f in fields]}, bound as {[n for n, _ in bound]}"]
-    return [f"{name}.{f.name} is {f}, bound as {t}" for f, (_, t) in zip(fields, bound) if not _matches(f, t, structs)]
-
-
-def _bound_structs(module):
-    return {k: v for k, v in vars(module).items() if isinstance(v, type) and issubclass(v, C.Structure) and v is not C.Structure}
 
 
 def test_library_exports_every_declared_symbol():
@@ -69,8 +24,7 @@ def test_library_exports_every_declared_symbol():
     scg:: function, kernel handle or __hip_cuid_* symbol leaks, and a definition that does not see its declaration is missed here."""
     where = abi_text.declared_in(ABI)                                # raises, naming both headers, when a name is declared twice
     assert len(where) == 73 and len(set(where.values())) == 8
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
+    exported = exported_names(_lib.LIB_PATH)
     assert exported == sorted(where), {n: where.get(n, "not declared") for n in set(exported) ^ set(where)}
     lib = _lib.load()
     for name, header in where.items():
@@ -86,15 +40,15 @@ def test_library_exports_every_declared_symbol():
 def test_every_prototype_is_bound_as_declared():
     where = abi_text.declared_in(ABI)
     assert sorted(_lib.SYMBOLS) == sorted(where), {n: where.get(n, "not declared") for n in set(_lib.SYMBOLS) ^ set(where)}
-    structs = _bound_structs(_lib)
-    diffs = [d for fn in ABI.functions for d in _prototype_differences(fn, *_lib.SYMBOLS[fn.name], structs)]
+    structs = bound_structs(_lib)
+    diffs = [d for fn in ABI.functions for d in prototype_differences(fn, *_lib.SYMBOLS[fn.name], structs)]
     assert not diffs, "\n".join(diffs)
 
 
 def test_every_struct_is_bound_field_by_field():
-    structs = _bound_structs(_lib)
+    structs = bound_structs(_lib)
     assert sorted(structs) == sorted(ABI.structs) and len(structs) == 17
-    diffs = [d for name, fields in ABI.structs.items() for d in _struct_differences(name, fields, structs[name], structs)]
+    diffs = [d for name, fields in ABI.structs.items() for d in struct_differences(name, fields, structs[name], structs)]
     assert not diffs, "\n".join(diffs)
 
 
@@ -163,8 +117,8 @@ def _toy_differences(text):
     abi = abi_text.parse(text, "toy.h")
     structs = {"ScgToy": ScgToy}
     assert sorted(abi_text.declared_in(abi)) == sorted(_TOY_SYMBOLS) and list(abi.structs) == ["ScgToy"]
-    return ([d for fn in abi.functions for d in _prototype_differences(fn, *_TOY_SYMBOLS[fn.name], structs)]
-            + _struct_differences("ScgToy", abi.structs["ScgToy"], ScgToy, structs))
+    return ([d for fn in abi.functions for d in prototype_differences(fn, *_TOY_SYMBOLS[fn.name], structs)]
+            + struct_differences("ScgToy", abi.structs["ScgToy"], ScgToy, structs))
 
 
 def test_the_toy_header_as_bound_shows_no_difference():
@@ -173,6 +127,15 @@ def test_the_toy_header_as_bound_shows_no_difference():
     assert abi.defines == {"SCG_TOY_MAX": 7} and [f.header for f in abi.functions] == ["toy.h", "toy.h"]
     assert abi.structs["ScgToy"] == [abi_text.Decl("rows", "int32_t", 0, 0), abi_text.Decl("cols", "int32_t", 0, 0),
                                      abi_text.Decl("data", "float", 1, 0), abi_text.Decl("m", "double", 0, 9)]
+
+
+def test_the_pointer_rules_tell_the_toy_bindings_pointers_apart():
+    """scg_toy_run is bound with POINTER(ScgToy) for `const ScgToy*` and c_void_p for `float*` and `void*`: the rule of the main
+    library takes all three, the typed rule refuses the float*, the void-only rule the struct pointer."""
+    run = abi_text.parse(_TOY, "toy.h").functions[0]
+    per_rule = {rule: prototype_differences(run, *_TOY_SYMBOLS["scg_toy_run"], {"ScgToy": ScgToy}, rule) for rule in (ANY, TYPED, VOID)}
+    assert per_rule[ANY] == [] and len(per_rule[TYPED]) == len(per_rule[VOID]) == 1
+    assert "parameter 2" in per_rule[TYPED][0] and "parameter 0" in per_rule[VOID][0]
 
 
 @pytest.mark.parametrize("what, old, new", [

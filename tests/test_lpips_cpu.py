@@ -3,21 +3,14 @@ tests compare against (tests/lpips_refs.py) is held to a literal module list of 
 (tests/golden/ref_lpips.npz); the sixth library and its binding to the header's text; the library's validation to its codes; the
 scratch size to its stated arithmetic; the key mapping; the plain-torch twin (the path CPU tensors take) to the fp64 restatement
 under the GPU tests' bar."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
-import abi_text
 import lpips_refs as LR
-from scgaussian_amd import _lib, _lib_img, _lib_io, _lib_lp, _lib_mp, _lib_vw, build, lpips
+from abi_compare import VOID, check_side_library
+from scgaussian_amd import _lib_lp, lpips
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "lp", "scg_lpips.h")
-_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "size_t": C.c_size_t}
 FX = np.load(LR.GOLDEN)
 WEIGHTS = LR.make_weights()
 
@@ -85,52 +78,14 @@ def test_fixture_against_the_restatement(scene):
 
 
 # ---- the sixth library against its header ---------------------------------------------------------------------------------------
-def _matches(decl, ctype, returned=False):
-    if decl.pointer == 0:
-        return ctype is _SCALARS.get(decl.base, False)
-    if returned and decl.base == "char":
-        return decl.pointer == 1 and ctype is C.c_char_p
-    return decl.pointer == 1 and ctype is C.c_void_p
-
-
 def test_sixth_library_exports_and_binds_exactly_its_header():
-    abi = abi_text.read([HEADER])
-    where = abi_text.declared_in(abi)
-    assert len(where) == 7 and set(where.values()) == {"scg_lpips.h"} and all(n.startswith("scg_lp_") for n in where)
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib_lp.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
-    assert exported == sorted(where) == sorted(_lib_lp.SYMBOLS)
-    main = abi_text.declared_in(abi_text.read())
-    sides = abi_text.declared_in(abi_text.read([os.path.join(ROOT, "include", "io", "scg_ply.h"),
-                                                os.path.join(ROOT, "include", "img", "scg_resample.h"),
-                                                os.path.join(ROOT, "include", "mp", "scg_matchpoint.h"),
-                                                os.path.join(ROOT, "include", "vw", "scg_virtualwarp.h")]))
-    assert not set(where) & (set(main) | set(sides)) and "scg_lpips.h" not in set(main.values())
-    for other in (_lib, _lib_io, _lib_img, _lib_mp, _lib_vw):
-        assert not set(_lib_lp.SYMBOLS) & set(other.SYMBOLS)
-    diffs = []
-    for fn in abi.functions:
-        res, args = _lib_lp.SYMBOLS[fn.name]
-        if not _matches(fn.ret, res, returned=True) or len(fn.params) != len(args):
-            diffs.append(f"{fn.name}: return type or parameter count")
-        diffs += [f"{fn.name}: parameter {i} is {d}, bound as {t}" for i, (d, t) in enumerate(zip(fn.params, args)) if not _matches(d, t)]
-    assert not diffs, "\n".join(diffs)
-    assert not abi.structs
-    assert {n[4:]: v for n, v in abi.defines.items()} == {n: getattr(_lib_lp, n) for n in (
+    abi = check_side_library(_lib_lp, "lp", "scg_lpips.h", VOID)
+    assert len(abi.functions) == 7 and not abi.structs
+    assert {d.base for fn in abi.functions for d in fn.params if not d.pointer} <= {"int", "int32_t", "size_t"}
+    assert sorted(abi.defines) == sorted("SCG_" + n for n in (
         "LP_ABI_VERSION", "LP_LAYERS", "LP_TAPS", "LP_TILE_M", "LP_HEAD_PIXELS", "LP_SMALL_GRID", "LP_MIN_DIM", "LP_MAX_DIM", "LP_MAX_PIXELS",
-        "LP_MAX_BATCH", "LP_PARAM_FLOATS", "LP_RELU", "LP_POOL", "LP_ZSCORE")}
-    lib = _lib_lp.load()
-    assert lib.scg_lp_abi_version() == _lib_lp.ABI_VERSION == abi.defines["SCG_LP_ABI_VERSION"]
+        "LP_MAX_BATCH", "LP_PARAM_FLOATS", "LP_RELU", "LP_POOL", "LP_ZSCORE"))
     assert _lib_lp.LP_PARAM_FLOATS == sum(9 * a * b + b for a, b in lpips.CHANNELS) + sum(lpips.TAP_CHANNELS)
-
-
-def test_build_tables():
-    assert build.LP_SOURCES == {"lpips.hip": []}
-    others = set(build.SOURCES) | set(build.IO_SOURCES) | set(build.IMG_SOURCES) | set(build.MP_SOURCES) | set(build.VW_SOURCES)
-    assert not set(build.LP_SOURCES) & others
-    assert build.LP_LIB_PATH == _lib_lp.LIB_PATH and os.path.exists(os.path.join(build.CSRC, "lpips.hip"))
-    assert HEADER in build.HEADERS and callable(build.build_lp)
-    assert len({build.LIB_PATH, build.IO_LIB_PATH, build.IMG_LIB_PATH, build.MP_LIB_PATH, build.VW_LIB_PATH, build.LP_LIB_PATH}) == 6
 
 
 # ---- scratch sizes and validation, without a GPU ----------------------------------------------------------------------------------

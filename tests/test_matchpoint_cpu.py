@@ -5,21 +5,15 @@ operation on both sides, so there is no tolerance — and its file to ply_io.wri
 to the header's text; the library's validation to its codes; the layout to its arithmetic."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-import abi_text
 import matchpoint_refs as MR
 import ply_refs as P
-from scgaussian_amd import _lib, _lib_img, _lib_io, _lib_mp, build, matchpoint, ply_io
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "mp", "scg_matchpoint.h")
-_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "size_t": C.c_size_t, "float": C.c_float,
-            "double": C.c_double, "uint8_t": C.c_uint8, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "char": C.c_char}
+from abi_compare import ANY, check_side_library
+from scgaussian_amd import _lib, _lib_mp, matchpoint, ply_io
 FX = np.load(MR.GOLDEN)
 SEED_FX = np.load(MR.SEED_GOLDEN)
 
@@ -94,65 +88,17 @@ def test_restatement_rules_on_a_hand_made_scene():
 
 
 # ---- the fourth library against its header --------------------------------------------------------------------------------------
-def _matches(decl, ctype, structs, returned=False):
-    """tests/test_abi_cpu.py's comparison, restated: does the ctypes type stand for the C declaration?"""
-    if decl.pointer == 0:
-        return ctype is (structs[decl.base] if decl.base in structs else _SCALARS.get(decl.base, False))
-    if returned and decl.base == "char":
-        return decl.pointer == 1 and ctype is C.c_char_p
-    if ctype is C.c_void_p:
-        return True
-    target = structs.get(decl.base, _SCALARS.get(decl.base))
-    return decl.pointer == 1 and target is not None and ctype is C.POINTER(target)
-
-
 def test_fourth_library_exports_and_binds_exactly_its_header():
-    abi = abi_text.read([HEADER])
-    where = abi_text.declared_in(abi)
-    assert len(where) == 6 and set(where.values()) == {"scg_matchpoint.h"} and all(n.startswith("scg_mp_") for n in where)
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib_mp.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
-    assert exported == sorted(where) == sorted(_lib_mp.SYMBOLS)
-    # no name is shared with the other three libraries' headers or bindings, and the glob of the main headers does not see this one
-    main = abi_text.declared_in(abi_text.read())
-    sides = abi_text.declared_in(abi_text.read([os.path.join(ROOT, "include", "io", "scg_ply.h"),
-                                                os.path.join(ROOT, "include", "img", "scg_resample.h")]))
-    assert not set(where) & (set(main) | set(sides)) and "scg_matchpoint.h" not in set(main.values())
-    for other in (_lib, _lib_io, _lib_img):
-        assert not set(_lib_mp.SYMBOLS) & set(other.SYMBOLS)
-    structs = {"ScgMpLayout": _lib_mp.ScgMpLayout, "ScgMpView": _lib_mp.ScgMpView, "ScgMpPack": _lib_mp.ScgMpPack,
-               "ScgSeedSegment": _lib.ScgSeedSegment}
-    diffs = []
-    for fn in abi.functions:
-        res, args = _lib_mp.SYMBOLS[fn.name]
-        if not _matches(fn.ret, res, structs, returned=True) or len(fn.params) != len(args):
-            diffs.append(f"{fn.name}: return type or parameter count")
-        diffs += [f"{fn.name}: parameter {i} is {d}, bound as {t}" for i, (d, t) in enumerate(zip(fn.params, args))
-                  if not _matches(d, t, structs)]
-    assert not diffs, "\n".join(diffs)
-    assert list(abi.structs) == ["ScgMpLayout", "ScgMpView", "ScgMpPack"] == [s.__name__ for s in _lib_mp.STRUCTS]
-    for name, fields in abi.structs.items():
-        bound = structs[name]._fields_
-        assert [f.name for f in fields] == [n for n, _ in bound], name
-        for f, (_n, t) in zip(fields, bound):
-            assert not f.array and (t is C.c_void_p if f.pointer else t is _SCALARS[f.base]), (name, f)
-    assert {n[4:]: v for n, v in abi.defines.items()} == {n: getattr(_lib_mp, n) for n in (
+    abi = check_side_library(_lib_mp, "mp", "scg_matchpoint.h", ANY)
+    assert len(abi.functions) == 6 and list(abi.structs) == ["ScgMpLayout", "ScgMpView", "ScgMpPack"]
+    assert not any(f.array for fields in abi.structs.values() for f in fields)
+    assert sorted(abi.defines) == sorted("SCG_" + n for n in (
         "MP_ABI_VERSION", "MP_RECORD_BYTES", "MP_TILE_RECORDS", "MP_MATCH_GROUP", "MP_RESOLVE_PIXELS", "MP_QUANT_PIXELS",
-        "MP_MAX_SEGMENTS", "MP_MAX_VIEWS", "MP_MAX_DIM", "MP_MAX_MATCHES", "MP_MAX_PIXELS")}
-    lib = _lib_mp.load()
-    assert lib.scg_mp_abi_version() == _lib_mp.ABI_VERSION == abi.defines["SCG_MP_ABI_VERSION"]
-    assert [lib.scg_mp_struct_bytes(k) for k in range(-1, 4)] == [0, 96, 24, 96, 0]
+        "MP_MAX_SEGMENTS", "MP_MAX_VIEWS", "MP_MAX_DIM", "MP_MAX_MATCHES", "MP_MAX_PIXELS"))
+    assert [_lib_mp.load().scg_mp_struct_bytes(k) for k in range(-1, 4)] == [0, 96, 24, 96, 0]
     assert [C.sizeof(s) for s in _lib_mp.STRUCTS] == [96, 24, 96]
     assert _lib_mp.MP_MATCH_GROUP % _lib_mp.MP_TILE_RECORDS == 0 and (_lib_mp.MP_TILE_RECORDS * _lib_mp.MP_RECORD_BYTES) % 4 == 0
     assert _lib_mp.MP_MAX_SEGMENTS == _lib.SEED_MAX_SEGMENTS
-
-
-def test_build_tables():
-    assert build.MP_SOURCES == {"matchpoint.hip": ["-ffp-contract=off"]}
-    assert not set(build.MP_SOURCES) & (set(build.SOURCES) | set(build.IO_SOURCES) | set(build.IMG_SOURCES))
-    assert build.MP_LIB_PATH == _lib_mp.LIB_PATH and os.path.exists(os.path.join(build.CSRC, "matchpoint.hip"))
-    assert HEADER in build.HEADERS and callable(build.build_mp)
-    assert len({build.LIB_PATH, build.IO_LIB_PATH, build.IMG_LIB_PATH, build.MP_LIB_PATH}) == 4
 
 
 # ---- the layout -----------------------------------------------------------------------------------------------------------------

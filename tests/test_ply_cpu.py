@@ -2,21 +2,14 @@
 GPU tests compare against (tests/ply_refs.py) is held to the files ply_io.save_ply writes, the byte rule to numpy's cast where
 numpy's cast is defined, the second library and its binding to the header's text, and the library's validation to its codes."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-import abi_text
 import ply_refs as R
-from scgaussian_amd import _lib, _lib_io, build, ply, ply_io
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "io", "scg_ply.h")
-_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "size_t": C.c_size_t, "float": C.c_float,
-            "double": C.c_double, "uint8_t": C.c_uint8, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "char": C.c_char}
+from abi_compare import ANY, check_side_library
+from scgaussian_amd import _lib, _lib_io, ply, ply_io
 
 
 def _ray_bound(m):
@@ -106,54 +99,14 @@ def test_column_table_reordered_extra_and_suffix_sort():
 
 
 # ---- the second library against its header -------------------------------------------------------------------------------------
-def _matches(decl, ctype, structs, returned=False):
-    """tests/test_abi_cpu.py's comparison, restated: does the ctypes type stand for the C declaration?"""
-    if decl.pointer == 0:
-        return ctype is (structs[decl.base] if decl.base in structs else _SCALARS.get(decl.base, False))
-    if returned and decl.base == "char":
-        return decl.pointer == 1 and ctype is C.c_char_p
-    if ctype is C.c_void_p:
-        return True
-    target = structs.get(decl.base, _SCALARS.get(decl.base))
-    return decl.pointer == 1 and target is not None and ctype is C.POINTER(target)
-
-
 def test_second_library_exports_and_binds_exactly_its_header():
-    abi = abi_text.read([HEADER])
-    where = abi_text.declared_in(abi)
-    assert len(where) == 7 and set(where.values()) == {"scg_ply.h"}
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib_io.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
-    assert exported == sorted(where) == sorted(_lib_io.SYMBOLS)
-    # no name is shared with the main library's headers, and the glob of those does not see this one
-    main = abi_text.declared_in(abi_text.read())
-    assert not set(where) & set(main) and "scg_ply.h" not in set(main.values())
-    assert not set(_lib_io.SYMBOLS) & set(_lib.SYMBOLS)
-    structs = {"ScgPlyLayout": _lib_io.ScgPlyLayout, "ScgModel": _lib.ScgModel}
-    diffs = []
-    for fn in abi.functions:
-        res, args = _lib_io.SYMBOLS[fn.name]
-        if not _matches(fn.ret, res, structs, returned=True) or len(fn.params) != len(args):
-            diffs.append(f"{fn.name}: return type or parameter count")
-        diffs += [f"{fn.name}: parameter {i} is {d}, bound as {t}" for i, (d, t) in enumerate(zip(fn.params, args))
-                  if not _matches(d, t, structs)]
-    assert not diffs, "\n".join(diffs)
-    assert list(abi.structs) == ["ScgPlyLayout"]
-    assert [f.name for f in abi.structs["ScgPlyLayout"]] == [n for n, _ in _lib_io.ScgPlyLayout._fields_]
-    assert all(f.base == "uint64_t" and not f.pointer and t is C.c_uint64
-               for f, (_, t) in zip(abi.structs["ScgPlyLayout"], _lib_io.ScgPlyLayout._fields_))
-    assert {n[4:]: v for n, v in abi.defines.items()} == {n: getattr(_lib_io, n) for n in (
-        "IO_ABI_VERSION", "PLY_TILE_ROWS", "PLY_RAY_FLOATS", "PLY_BG_FLOATS", "PLY_COLOR_BYTES", "PLY_MAX_STRIDE")}
-    lib = _lib_io.load()
-    assert lib.scg_io_abi_version() == _lib_io.ABI_VERSION == abi.defines["SCG_IO_ABI_VERSION"]
-    assert lib.scg_ply_layout_bytes() == C.sizeof(_lib_io.ScgPlyLayout) == 56
+    abi = check_side_library(_lib_io, "io", "scg_ply.h", ANY, prefixes=("scg_io_", "scg_ply_"))
+    assert len(abi.functions) == 7 and list(abi.structs) == ["ScgPlyLayout"]
+    assert all(f.base == "uint64_t" and not f.pointer for f in abi.structs["ScgPlyLayout"])
+    assert sorted(abi.defines) == sorted("SCG_" + n for n in (
+        "IO_ABI_VERSION", "PLY_TILE_ROWS", "PLY_RAY_FLOATS", "PLY_BG_FLOATS", "PLY_COLOR_BYTES", "PLY_MAX_STRIDE"))
+    assert _lib_io.load().scg_ply_layout_bytes() == C.sizeof(_lib_io.ScgPlyLayout) == 56
     assert ply.TILE_ROWS == abi.defines["SCG_PLY_TILE_ROWS"] and ply.TILE_ROWS % 4 == 0
-
-
-def test_build_tables():
-    assert build.IO_SOURCES["plypack.hip"] == ["-ffp-contract=off"]
-    assert "plypack.hip" not in build.SOURCES and build.IO_LIB_PATH == _lib_io.LIB_PATH
-    assert os.path.exists(os.path.join(build.CSRC, "plypack.hip"))
 
 
 def test_layout():

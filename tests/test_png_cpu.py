@@ -3,22 +3,17 @@ lengths to the Kraft sum and to a heapq Huffman tree, the planted histograms, th
 text against its exports and its binding, every argument code, and the layout's arithmetic.  Nothing here launches a kernel."""
 import ctypes as C
 import heapq
-import os
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
-import abi_text
 import png_refs as R
-from scgaussian_amd import _lib, _lib_img, _lib_io, _lib_lp, _lib_mp, _lib_png, _lib_vw, build
+from abi_compare import TYPED, check_side_library
+from scgaussian_amd import _lib, _lib_png
 
-ROOT = abi_text.ROOT
-HEADER = os.path.join(ROOT, "include", "png", "scg_png.h")
 CH = R.CHUNK
 u8 = np.uint8
-_SCALARS = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "size_t": C.c_size_t, "int": C.c_int}
 
 
 def _images():
@@ -131,60 +126,14 @@ def test_tokens_of_planted_runs():
 
 
 # ---- the header's text, the library, the binding -----------------------------------------------------------------------------------
-def _matches(decl, ctype, structs, returned=False):
-    if decl.base == "char" and decl.pointer == 1:
-        return ctype is C.c_char_p
-    if decl.base == "void" and decl.pointer == 1:
-        return ctype is C.c_void_p
-    if decl.pointer == 0:
-        return ctype is _SCALARS.get(decl.base)
-    target = structs.get(decl.base, _SCALARS.get(decl.base))
-    return decl.pointer == 1 and target is not None and ctype is C.POINTER(target)
-
-
 def test_seventh_library_exports_and_binds_exactly_its_header():
-    abi = abi_text.read([HEADER])
-    where = abi_text.declared_in(abi)
-    assert len(where) == 5 and set(where.values()) == {"scg_png.h"} and all(n.startswith("scg_png_") for n in where)
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib_png.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
-    assert exported == sorted(where) == sorted(_lib_png.SYMBOLS)
-    main = abi_text.declared_in(abi_text.read())
-    assert not set(where) & set(main) and "scg_png.h" not in set(main.values())
-    for other in (_lib, _lib_io, _lib_img, _lib_mp, _lib_vw, _lib_lp):
-        assert not set(_lib_png.SYMBOLS) & set(other.SYMBOLS)
-    structs = {s.__name__: s for s in _lib_png.STRUCTS}
-    diffs = []
-    for fn in abi.functions:
-        res, args = _lib_png.SYMBOLS[fn.name]
-        if not _matches(fn.ret, res, structs, returned=True) or len(fn.params) != len(args):
-            diffs.append(f"{fn.name}: return type or parameter count")
-        diffs += [f"{fn.name}: parameter {i} is {d}, bound as {t}" for i, (d, t) in enumerate(zip(fn.params, args))
-                  if not _matches(d, t, structs)]
-    assert not diffs, "\n".join(diffs)
-    assert list(abi.structs) == [s.__name__ for s in _lib_png.STRUCTS]
-    for name, fields in abi.structs.items():
-        bound = structs[name]._fields_
-        assert [f.name for f in fields] == [n for n, _ in bound], name
-        for f, (_n, t) in zip(fields, bound):
-            assert not f.array and (t is C.c_void_p if f.pointer else t is _SCALARS[f.base]), (name, f)
-    assert {n[4:]: v for n, v in abi.defines.items()} == {n: getattr(_lib_png, n) for n in dir(_lib_png) if n.startswith("PNG_")}
-    lib = _lib_png.load()
-    assert lib.scg_png_abi_version() == _lib_png.ABI_VERSION == abi.defines["SCG_PNG_ABI_VERSION"]
-    assert [lib.scg_png_struct_bytes(k) for k in range(-1, 6)] == [0, 80, 32, 8, 16, 40, 0]
+    abi = check_side_library(_lib_png, "png", "scg_png.h", TYPED)
+    assert len(abi.functions) == 5 and len(abi.structs) == 5 and len(abi.defines) == 17
+    assert not any(f.array for fields in abi.structs.values() for f in fields)
+    assert [_lib_png.load().scg_png_struct_bytes(k) for k in range(-1, 6)] == [0, 80, 32, 8, 16, 40, 0]
     assert [C.sizeof(s) for s in _lib_png.STRUCTS] == [80, 32, 8, 16, 40]
     assert _lib_png.PNG_CHUNK == CH and _lib_png.PNG_HEADER_BITS == R.HEADER_BITS == 17 + 19 * 3 + 288 * 4
     assert (_lib_png.PNG_FILTER_NONE, _lib_png.PNG_FILTER_SUB, _lib_png.PNG_FILTER_UP, _lib_png.PNG_FILTER_PAETH) == R.FILTERS
-
-
-def test_build_tables():
-    assert build.PNG_SOURCES == {"pngpack.hip": []}
-    others = (build.SOURCES, build.IO_SOURCES, build.IMG_SOURCES, build.MP_SOURCES, build.VW_SOURCES, build.LP_SOURCES)
-    assert not any(set(build.PNG_SOURCES) & set(o) for o in others)
-    assert build.PNG_LIB_PATH == _lib_png.LIB_PATH and os.path.exists(os.path.join(build.CSRC, "pngpack.hip"))
-    assert HEADER in build.HEADERS and callable(build.build_png)
-    assert len({build.LIB_PATH, build.IO_LIB_PATH, build.IMG_LIB_PATH, build.MP_LIB_PATH, build.VW_LIB_PATH, build.LP_LIB_PATH,
-                build.PNG_LIB_PATH}) == 7
 
 
 # ---- the layout ---------------------------------------------------------------------------------------------------------------------

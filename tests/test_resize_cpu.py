@@ -2,23 +2,18 @@
 the GPU tests compare against (tests/resize_refs.py) is held to Pillow itself, byte for byte, and to the fixture recorded from the
 reference's PILtoTorch; the package's vectorised tables to the restatement's; loadCam's size arithmetic to its literal text; the
 third library and its binding to the header's text, and the library's validation to its codes."""
-import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-import abi_text
 import resize_refs as R
-from scgaussian_amd import _lib, _lib_img, _lib_io, build, images
+from abi_compare import VOID, check_side_library
+from scgaussian_amd import _lib, _lib_img, images
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "img", "scg_resample.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "ref_resize.npz")
-_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "size_t": C.c_size_t, "float": C.c_float,
-            "double": C.c_double, "uint8_t": C.c_uint8, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "char": C.c_char}
 LIMIT = images.MAX_KSIZE
 
 # ((win, hin), (wout, hout)): 8x, 4x and non-integer reductions, upscales, one axis unchanged, both unchanged, the smallest
@@ -160,46 +155,12 @@ def test_fixture_equals_the_restatement():
 
 
 # ---- the third library against its header --------------------------------------------------------------------------------------
-def _matches(decl, ctype, returned=False):
-    if decl.pointer == 0:
-        return ctype is _SCALARS.get(decl.base, False)
-    if returned and decl.base == "char":
-        return decl.pointer == 1 and ctype is C.c_char_p
-    return ctype is C.c_void_p or (decl.pointer == 1 and decl.base in _SCALARS and ctype is C.POINTER(_SCALARS[decl.base]))
-
-
 def test_third_library_exports_and_binds_exactly_its_header():
-    abi = abi_text.read([HEADER])
-    where = abi_text.declared_in(abi)
-    assert len(where) == 5 and set(where.values()) == {"scg_resample.h"}
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib_img.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
-    assert exported == sorted(where) == sorted(_lib_img.SYMBOLS)
-    # no name is shared with the other two libraries' headers or bindings
-    main = abi_text.declared_in(abi_text.read())
-    io = abi_text.declared_in(abi_text.read([os.path.join(ROOT, "include", "io", "scg_ply.h")]))
-    assert not set(where) & set(main) and not set(where) & set(io) and "scg_resample.h" not in set(main.values())
-    assert not set(_lib_img.SYMBOLS) & set(_lib.SYMBOLS) and not set(_lib_img.SYMBOLS) & set(_lib_io.SYMBOLS)
-    diffs = []
-    for fn in abi.functions:
-        res, args = _lib_img.SYMBOLS[fn.name]
-        if not _matches(fn.ret, res, returned=True) or len(fn.params) != len(args):
-            diffs.append(f"{fn.name}: return type or parameter count")
-        diffs += [f"{fn.name}: parameter {i} is {d}, bound as {t}" for i, (d, t) in enumerate(zip(fn.params, args))
-                  if not _matches(d, t)]
-    assert not diffs, "\n".join(diffs)
-    assert not abi.structs and not abi.enums
-    assert {n[4:]: v for n, v in abi.defines.items()} == {n: getattr(_lib_img, n) for n in (
+    abi = check_side_library(_lib_img, "img", "scg_resample.h", VOID, prefixes=("scg_img_", "scg_resample_"))
+    assert len(abi.functions) == 5 and not abi.structs and not abi.enums
+    assert sorted(abi.defines) == sorted("SCG_" + n for n in (
         "IMG_ABI_VERSION", "RESAMPLE_MAX_KSIZE", "RESAMPLE_MAX_SIZE", "RESAMPLE_STRIP", "RESAMPLE_STRIP_ROWS", "RESAMPLE_VTILE",
-        "RESAMPLE_PITCH_ALIGN")}
-    lib = _lib_img.load()
-    assert lib.scg_img_abi_version() == _lib_img.ABI_VERSION == abi.defines["SCG_IMG_ABI_VERSION"]
-
-
-def test_build_tables():
-    assert build.IMG_SOURCES == {"resample.hip": []} and build.IMG_LIB_PATH == _lib_img.LIB_PATH
-    assert "resample.hip" not in build.SOURCES and "resample.hip" not in build.IO_SOURCES
-    assert os.path.exists(os.path.join(build.CSRC, "resample.hip")) and HEADER in build.HEADERS
+        "RESAMPLE_PITCH_ALIGN"))
 
 
 def test_validation_returns_codes_without_a_gpu():

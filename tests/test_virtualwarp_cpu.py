@@ -3,22 +3,16 @@ include/vw/scg_virtualwarp.h): the restatements the GPU tests compare against (t
 reference's own functions gave (tests/golden/ref_virtualwarp.npz); the reflection fold to autograd; the fifth library and its
 binding to the header's text; the library's validation to its codes; the host arithmetic to the fixture; the plain-torch twin
 (the path CPU tensors take) to the fp64 restatement under the GPU tests' bar."""
-import ctypes as C
-import os
-import subprocess
 import types
 
 import numpy as np
 import pytest
 import torch
 
-import abi_text
 import virtualwarp_refs as VR
-from scgaussian_amd import _lib, _lib_img, _lib_io, _lib_mp, _lib_vw, build, synthetic, virtual
+from abi_compare import VOID, check_side_library
+from scgaussian_amd import _lib, _lib_vw, synthetic, virtual
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "vw", "scg_virtualwarp.h")
-_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "size_t": C.c_size_t}
 FX = np.load(VR.GOLDEN)
 TAGS = [str(t) for t in FX["scenes"]]
 
@@ -105,50 +99,14 @@ def test_fold_counts_are_the_reflections_of_the_padded_window():
 
 
 # ---- the fifth library against its header ---------------------------------------------------------------------------------------
-def _matches(decl, ctype, returned=False):
-    if decl.pointer == 0:
-        return ctype is _SCALARS.get(decl.base, False)
-    if returned and decl.base == "char":
-        return decl.pointer == 1 and ctype is C.c_char_p
-    return decl.pointer == 1 and ctype is C.c_void_p
-
-
 def test_fifth_library_exports_and_binds_exactly_its_header():
-    abi = abi_text.read([HEADER])
-    where = abi_text.declared_in(abi)
-    assert len(where) == 8 and set(where.values()) == {"scg_virtualwarp.h"} and all(n.startswith("scg_vw_") for n in where)
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib_vw.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
-    assert exported == sorted(where) == sorted(_lib_vw.SYMBOLS)
-    main = abi_text.declared_in(abi_text.read())
-    sides = abi_text.declared_in(abi_text.read([os.path.join(ROOT, "include", "io", "scg_ply.h"),
-                                                os.path.join(ROOT, "include", "img", "scg_resample.h"),
-                                                os.path.join(ROOT, "include", "mp", "scg_matchpoint.h")]))
-    assert not set(where) & (set(main) | set(sides)) and "scg_virtualwarp.h" not in set(main.values())
-    for other in (_lib, _lib_io, _lib_img, _lib_mp):
-        assert not set(_lib_vw.SYMBOLS) & set(other.SYMBOLS)
-    diffs = []
-    for fn in abi.functions:
-        res, args = _lib_vw.SYMBOLS[fn.name]
-        if not _matches(fn.ret, res, returned=True) or len(fn.params) != len(args):
-            diffs.append(f"{fn.name}: return type or parameter count")
-        diffs += [f"{fn.name}: parameter {i} is {d}, bound as {t}" for i, (d, t) in enumerate(zip(fn.params, args)) if not _matches(d, t)]
-    assert not diffs, "\n".join(diffs)
-    assert not abi.structs
-    assert {n[4:]: v for n, v in abi.defines.items()} == {n: getattr(_lib_vw, n) for n in (
+    abi = check_side_library(_lib_vw, "vw", "scg_virtualwarp.h", VOID)
+    assert len(abi.functions) == 8 and not abi.structs
+    assert {d.base for fn in abi.functions for d in fn.params if not d.pointer} <= {"int", "int32_t", "size_t"}
+    assert sorted(abi.defines) == sorted("SCG_" + n for n in (
         "VW_ABI_VERSION", "VW_MAX_VIEWS", "VW_TILE", "VW_SMOOTH_PIXELS", "VW_RECORD_FLOATS", "VW_MIN_DIM", "VW_MAX_DIM",
-        "VW_MAX_GUIDE_CHANNELS")}
-    lib = _lib_vw.load()
-    assert lib.scg_vw_abi_version() == _lib_vw.ABI_VERSION == abi.defines["SCG_VW_ABI_VERSION"]
+        "VW_MAX_GUIDE_CHANNELS"))
     assert _lib_vw.VW_MAX_VIEWS >= 8 and _lib_vw.VW_TILE ** 2 == 256
-
-
-def test_build_tables():
-    assert build.VW_SOURCES == {"virtualwarp.hip": ["-ffp-contract=off"]}
-    assert not set(build.VW_SOURCES) & (set(build.SOURCES) | set(build.IO_SOURCES) | set(build.IMG_SOURCES) | set(build.MP_SOURCES))
-    assert build.VW_LIB_PATH == _lib_vw.LIB_PATH and os.path.exists(os.path.join(build.CSRC, "virtualwarp.hip"))
-    assert HEADER in build.HEADERS and callable(build.build_vw)
-    assert len({build.LIB_PATH, build.IO_LIB_PATH, build.IMG_LIB_PATH, build.MP_LIB_PATH, build.VW_LIB_PATH}) == 5
 
 
 # ---- scratch sizes and validation, without a GPU ----------------------------------------------------------------------------------
