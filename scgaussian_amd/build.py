@@ -119,6 +119,18 @@ def build_cxx_trip_variant(verbose: bool = False) -> str:
     return build(verbose=verbose, tag=CXX_TRIP_TAG, defines=("SCG_FWD_TRIP_CXX",), only=("blend.hip",))
 
 
+# The probe build: every wave of the geometry, scatter, forward-blend and blend-backward kernels logs the wall clock at the
+# boundaries of its phases (csrc/probe_timeline.h; tools/probes/*_timeline.py read the log).  Not part of the default build;
+# tests/test_probe_timeline_cpu.py compiles it, so that a kernel change that breaks it is noticed.
+PROBE_TIMELINE_TAG = "tl"
+PROBE_TIMELINE_SOURCES = ("geometry.hip", "binning_tiles.hip", "blend.hip")       # the sources that include the header
+
+
+def build_probe_timeline_variant(verbose: bool = False) -> str:
+    build(verbose=verbose)
+    return build(verbose=verbose, tag=PROBE_TIMELINE_TAG, defines=("SCG_PROBE_TIMELINE",), only=PROBE_TIMELINE_SOURCES)
+
+
 def _compile(hipcc: str, src: str, extra, obj: str, force: bool, verbose: bool) -> bool:
     """Compile csrc/<src> to `obj` unless its stamp says that source, headers and flags are the ones it was built from."""
     src_path = os.path.join(CSRC, src)

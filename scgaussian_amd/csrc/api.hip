@@ -50,21 +50,20 @@ int validate_frame(const ScgFrame* f, bool need_bg) {
 
 int validate_model(const ScgFrame* f, const ScgModel* m);
 
-static int validate_inputs(const ScgFrame* f, const float* means3D, const float* opacities, const float* shs,
-                           const float* colors_precomp, const float* scales, const float* rotations,
-                           const float* cov3D_precomp) {
+static int validate_inputs(const ScgFrame* f, const GeoInputs& in) {
+    if (in.model) return validate_model(f, in.model);
     if (f->P == 0) return 0;
-    if (!means3D || !opacities) return fail(SCG_E_NULL, "means3D/opacities is NULL");
-    if ((shs == nullptr) == (colors_precomp == nullptr))
+    if (!in.means3D || !in.opacities) return fail(SCG_E_NULL, "means3D/opacities is NULL");
+    if ((in.shs == nullptr) == (in.colors_precomp == nullptr))
         return fail(SCG_E_EXCLUSIVE, "Please provide exactly one of either SHs or precomputed colors!");
-    const bool has_sr = scales != nullptr && rotations != nullptr;
-    if ((scales != nullptr) != (rotations != nullptr) || has_sr == (cov3D_precomp != nullptr))
+    const bool has_sr = in.scales != nullptr && in.rotations != nullptr;
+    if ((in.scales != nullptr) != (in.rotations != nullptr) || has_sr == (in.cov3D_precomp != nullptr))
         return fail(SCG_E_EXCLUSIVE,
                     "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
-    if (shs && f->sh_coeffs < (f->sh_degree + 1) * (f->sh_degree + 1))
+    if (in.shs && f->sh_coeffs < (f->sh_degree + 1) * (f->sh_degree + 1))
         return fail(SCG_E_RANGE, "sh_coeffs %d < (sh_degree+1)^2 = %d", f->sh_coeffs,
                     (f->sh_degree + 1) * (f->sh_degree + 1));
-    if (rotations && !aligned16(rotations)) return fail(SCG_E_ALIGN, "rotations must be 16-byte aligned");
+    if (in.rotations && !aligned16(in.rotations)) return fail(SCG_E_ALIGN, "rotations must be 16-byte aligned");
     return 0;
 }
 
@@ -123,7 +122,8 @@ int scg_geometry_forward(const ScgFrame* frame, const float* means3D, const floa
                          size_t scratch_bytes, void* stream) {
     int rc = validate_frame(frame, false);
     if (rc) return rc;
-    rc = validate_inputs(frame, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp);
+    const GeoInputs in{means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp};
+    rc = validate_inputs(frame, in);
     if (rc) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (frame->P == 0)
@@ -136,8 +136,7 @@ int scg_geometry_forward(const ScgFrame* frame, const float* means3D, const floa
         return fail(SCG_E_SCRATCH, "geometry scratch: %zu < %zu bytes", scratch_bytes, scg_geometry_scratch_bytes(frame->P));
     const FrameDev f = make_frame_dev(frame);
     uint32_t* block_sums = reinterpret_cast<uint32_t*>(scratch);
-    rc = launch_geometry_forward(f, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, splats,
-                                 radii, clamped, rects, depth_keys, block_sums, s);
+    rc = launch_geometry_forward(f, in, GeoOutputs{splats, radii, clamped, rects, depth_keys, block_sums}, s);
     if (rc || !num_rendered_out) return rc;
     return launch_total_from_block_sums(block_sums, (frame->P + kBlock - 1) / kBlock, num_rendered_out, s);
 }
@@ -220,7 +219,7 @@ int scg_binning(const ScgFrame* frame, int64_t num_rendered, const uint32_t* rec
     if (scratch_bytes < need) return fail(SCG_E_SCRATCH, "binning scratch: %zu < %zu bytes", scratch_bytes, need);
 
     if (use_tile_path(n_tiles, num_rendered, algo))
-        return launch_tile_binning(f, num_rendered, rects, depth_keys, point_list, ranges, keys_sorted, scratch, nullptr, false, false, false, false, s);
+        return launch_tile_binning(f, num_rendered, rects, depth_keys, point_list, ranges, keys_sorted, scratch, TileBinningOptions{}, s);
 
     // global 64-bit key sort (the reference's scheme): duplicateWithKeys + 6-pass radix sort + identifyTileRanges
     const LegacyLayout L = legacy_layout(frame->P, num_rendered);
@@ -323,7 +322,8 @@ int scg_geometry_backward(const ScgFrame* frame, const float* means3D, const flo
                           float* dL_dcov3D_precomp, int32_t accumulate, void* stream) {
     int rc = validate_frame(frame, false);
     if (rc) return rc;
-    rc = validate_inputs(frame, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp);
+    const GeoInputs in{means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp};
+    rc = validate_inputs(frame, in);
     if (rc) return rc;
     if (frame->P == 0) return 0;
     if (!radii || !clamped || !dsplats || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacities)
@@ -337,8 +337,7 @@ int scg_geometry_backward(const ScgFrame* frame, const float* means3D, const flo
     if (!aligned64(dsplats) || (dL_drotations && !aligned16(dL_drotations)))
         return fail(SCG_E_ALIGN, "dsplats must be 64-byte, dL_drotations 16-byte aligned");
     const FrameDev f = make_frame_dev(frame);
-    return launch_geometry_backward(f, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, radii,
-                                    clamped, dsplats, dL_dmeans3D, dL_dmeans2D, dL_dopacities, dL_dshs,
+    return launch_geometry_backward(f, in, radii, clamped, dsplats, dL_dmeans3D, dL_dmeans2D, dL_dopacities, dL_dshs,
                                     dL_dcolors_precomp, dL_dscales, dL_drotations, dL_dcov3D_precomp,
                                     accumulate & (SCG_BACKWARD_ACCUMULATE | SCG_BACKWARD_SH_TAIL_ZERO),
                                     reinterpret_cast<hipStream_t>(stream));
@@ -373,17 +372,13 @@ int scg_workspace_layout(int32_t P, int64_t capacity, int32_t width, int32_t hei
     return 0;
 }
 
-// scg_forward / scg_forward_model: the same launch sequence behind two geometry kernels (`model` != NULL: the reference model's
-// raw parameter tensors instead of the seven activated inputs)
-static int forward_impl(const ScgFrame* frame, const ScgModel* model, const float* means3D, const float* opacities,
-                        const float* shs, const float* colors_precomp, const float* scales, const float* rotations,
-                        const float* cov3D_precomp, int64_t capacity, void* workspace, size_t workspace_bytes, int32_t* radii,
-                        float* out_color, float* out_depth, float* out_alpha, uint32_t* partial_sums, void* event,
+// scg_forward / scg_forward_model: the same launch sequence over either source of the geometry stage (GeoInputs)
+static int forward_impl(const ScgFrame* frame, const GeoInputs& in, int64_t capacity, void* workspace, size_t workspace_bytes,
+                        int32_t* radii, float* out_color, float* out_depth, float* out_alpha, uint32_t* partial_sums, void* event,
                         float* dsplats_zero, int32_t options, const ScgStageEvents* stage_events, void* stream) {
     int rc = validate_frame(frame, true);
     if (rc) return rc;
-    rc = model ? validate_model(frame, model)
-               : validate_inputs(frame, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp);
+    rc = validate_inputs(frame, in);
     if (rc) return rc;
     if (!workspace || !out_color || !out_depth || !out_alpha || !partial_sums || (frame->P > 0 && !radii))
         return fail(SCG_E_NULL, "scg_forward: workspace / output / partial_sums pointer is NULL");
@@ -397,10 +392,9 @@ static int forward_impl(const ScgFrame* frame, const ScgModel* model, const floa
     const FrameDev f = make_frame_dev(frame);
     const int n_tiles = f.gx * f.gy;
     char* base = reinterpret_cast<char*>(workspace);
-    float* splats = reinterpret_cast<float*>(base + L.splats);
-    uint32_t* rects = reinterpret_cast<uint32_t*>(base + L.rects);
-    uint32_t* depth_keys = reinterpret_cast<uint32_t*>(base + L.depth_keys);
-    uint8_t* clamped = reinterpret_cast<uint8_t*>(base + L.clamped);
+    const GeoOutputs geo{reinterpret_cast<float*>(base + L.splats), radii, reinterpret_cast<uint8_t*>(base + L.clamped),
+                         reinterpret_cast<uint32_t*>(base + L.rects), reinterpret_cast<uint32_t*>(base + L.depth_keys),
+                         partial_sums};
     uint32_t* point_list = reinterpret_cast<uint32_t*>(base + L.point_list);
     uint32_t* ranges = reinterpret_cast<uint32_t*>(base + L.ranges);
     // a render that will not be differentiated does not write the backward's per-pixel state (8 of the 28 bytes per pixel)
@@ -417,22 +411,20 @@ static int forward_impl(const ScgFrame* frame, const ScgModel* model, const floa
         std::atomic_thread_fence(std::memory_order_release);
     }
     if ((rc = mark(stage_events, 0, false, s))) return rc;
+    // the forward blend sorts the tiles' lists itself (one launch and its drain less) unless the binning stage decides
+    // otherwise (dense scenes)
+    bool fused_sort = !empty && !(options & SCG_DEBUG_SEPARATE_SORT);
+    TileBinningOptions bin;
+    bin.defer_sort = &fused_sort;
     // the slice histograms of the binning stage are built by the geometry kernel itself (one launch and the re-read of the
     // rectangles less) unless the caller or the shape says otherwise
-    const bool hist_in_geometry = !empty && !(options & SCG_DEBUG_SEPARATE_HIST) && tile_binning_hist_in_geometry(f, capacity);
-    if (frame->P == 0) {
-        rc = check_hip(hipMemsetAsync(partial_sums, 0, sizeof(uint32_t), s), "memset partial sums");
-    } else if (hist_in_geometry) {
-        rc = model ? launch_geometry_hist_binned_model(f, capacity, *model, splats, radii, clamped, rects, depth_keys, partial_sums,
-                                                       base + L.bin_scratch, s)
-                   : launch_geometry_hist_binned(f, capacity, means3D, opacities, shs, colors_precomp, scales, rotations,
-                                                 cov3D_precomp, splats, radii, clamped, rects, depth_keys, partial_sums,
-                                                 base + L.bin_scratch, s);
-    } else {
-        rc = model ? launch_geometry_forward_model(f, *model, splats, radii, clamped, rects, depth_keys, partial_sums, s)
-                   : launch_geometry_forward(f, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, splats,
-                                             radii, clamped, rects, depth_keys, partial_sums, s);
-    }
+    bin.hist_done = !empty && !(options & SCG_DEBUG_SEPARATE_HIST) && tile_binning_hist_in_geometry(f, capacity);
+    bin.skip_rare = (options & SCG_FORWARD_SKIP_RARE_SORT) != 0;
+    bin.rare8 = (options & SCG_FORWARD_RARE_8WAVE) != 0;
+    bin.split_long = (options & SCG_FORWARD_SPLIT_LONG_LISTS) != 0;
+    if (frame->P == 0) rc = check_hip(hipMemsetAsync(partial_sums, 0, sizeof(uint32_t), s), "memset partial sums");
+    else if (bin.hist_done) rc = launch_geometry_hist_binned(f, capacity, in, geo, base + L.bin_scratch, s);
+    else rc = launch_geometry_forward(f, in, geo, s);
     if (rc) return rc;
     if ((rc = mark(stage_events, 0, true, s))) return rc;
     if (event) {
@@ -440,23 +432,18 @@ static int forward_impl(const ScgFrame* frame, const ScgModel* model, const floa
         if (rc) return rc;
     }
     if ((rc = mark(stage_events, 1, false, s))) return rc;
-    // the forward blend sorts the tiles' lists itself (one launch and its drain less) unless the binning stage decides
-    // otherwise (dense scenes)
-    bool fused_sort = !empty && !(options & SCG_DEBUG_SEPARATE_SORT);
-    const bool skip_rare = (options & SCG_FORWARD_SKIP_RARE_SORT) != 0;
     if (empty && frame->num_rendered_out)                       // (nothing is binned: the count the caller looks at later is 0)
         if ((rc = check_hip(hipMemsetAsync(frame->num_rendered_out, 0, sizeof(uint32_t), s), "memset num_rendered_out"))) return rc;
     rc = empty ? launch_tile_ranges(nullptr, 0, ranges, n_tiles, s)
-               : launch_tile_binning(f, capacity, rects, depth_keys, point_list, ranges, nullptr, base + L.bin_scratch,
-                                     &fused_sort, hist_in_geometry, skip_rare, (options & SCG_FORWARD_RARE_8WAVE) != 0,
-                                     (options & SCG_FORWARD_SPLIT_LONG_LISTS) != 0, s);
+               : launch_tile_binning(f, capacity, geo.rects, geo.depth_keys, point_list, ranges, nullptr, base + L.bin_scratch,
+                                     bin, s);
     if (rc) return rc;
     if ((rc = mark(stage_events, 1, true, s))) return rc;
     if ((rc = mark(stage_events, 2, false, s))) return rc;
-    rc = fused_sort ? launch_tile_blend_forward(f, ranges, point_list, depth_keys, splats, out_color, out_depth, out_alpha,
+    rc = fused_sort ? launch_tile_blend_forward(f, ranges, point_list, geo.depth_keys, geo.splats, out_color, out_depth, out_alpha,
                                                 final_T, n_contrib, frame->P ? dsplats_zero : nullptr, base + L.bin_scratch,
-                                                capacity, !skip_rare, s)
-                    : launch_blend_forward(f, ranges, point_list, splats, out_color, out_depth, out_alpha, final_T, n_contrib,
+                                                capacity, !bin.skip_rare, s)
+                    : launch_blend_forward(f, ranges, point_list, geo.splats, out_color, out_depth, out_alpha, final_T, n_contrib,
                                            frame->P ? dsplats_zero : nullptr, s);
     if (rc) return rc;
     return mark(stage_events, 2, true, s);
@@ -467,18 +454,19 @@ int scg_forward(const ScgFrame* frame, const float* means3D, const float* opacit
                 int64_t capacity, void* workspace, size_t workspace_bytes, int32_t* radii, float* out_color,
                 float* out_depth, float* out_alpha, uint32_t* partial_sums, void* event, float* dsplats_zero,
                 int32_t options, const ScgStageEvents* stage_events, void* stream) {
-    return forward_impl(frame, nullptr, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, capacity,
-                        workspace, workspace_bytes, radii, out_color, out_depth, out_alpha, partial_sums, event, dsplats_zero,
-                        options, stage_events, stream);
+    const GeoInputs in{means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp};
+    return forward_impl(frame, in, capacity, workspace, workspace_bytes, radii, out_color, out_depth, out_alpha, partial_sums,
+                        event, dsplats_zero, options, stage_events, stream);
 }
 
 int scg_forward_model(const ScgFrame* frame, const ScgModel* model, int64_t capacity, void* workspace, size_t workspace_bytes,
                       int32_t* radii, float* out_color, float* out_depth, float* out_alpha, uint32_t* partial_sums, void* event,
                       float* dsplats_zero, int32_t options, const ScgStageEvents* stage_events, void* stream) {
     if (!model) return fail(SCG_E_NULL, "model is NULL");
-    return forward_impl(frame, model, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, capacity, workspace,
-                        workspace_bytes, radii, out_color, out_depth, out_alpha, partial_sums, event, dsplats_zero, options,
-                        stage_events, stream);
+    GeoInputs in;
+    in.model = model;
+    return forward_impl(frame, in, capacity, workspace, workspace_bytes, radii, out_color, out_depth, out_alpha, partial_sums,
+                        event, dsplats_zero, options, stage_events, stream);
 }
 
 int scg_model_activate(const ScgModel* model, float* means3D, float* opacities, float* scales, float* rotations, void* stream) {
@@ -547,6 +535,29 @@ int scg_event_elapsed_ms(void* begin, void* end, float* ms_out) {
                      "event elapsed time");
 }
 
+// What scg_backward and scg_backward_model share behind their own checks: the forward's workspace carved, the blend backward
+// launched (its two stage events ride on its dispatch packet: begin / end time stamps of the kernel itself), stage 1 opened.
+// *clamped_out: the forward's clamp bits, for the geometry backward that follows.
+static int backward_blend_stage(const ScgFrame* frame, int64_t capacity, const void* workspace, const float* dL_dcolor,
+                                const float* dL_ddepth, const float* dL_dalpha, float* dsplats, int32_t dsplats_prezeroed,
+                                const ScgStageEvents* stage_events, void* stream, const uint8_t** clamped_out) {
+    ScgWorkspaceLayout L;
+    int rc = scg_workspace_layout(frame->P, capacity, frame->width, frame->height, &L);
+    if (rc) return rc;
+    const char* base = reinterpret_cast<const char*>(workspace);
+    *clamped_out = reinterpret_cast<const uint8_t*>(base + L.clamped);
+    hipEvent_t bb_begin = stage_events ? reinterpret_cast<hipEvent_t>(stage_events->begin[0]) : nullptr;
+    hipEvent_t bb_end = stage_events ? reinterpret_cast<hipEvent_t>(stage_events->end[0]) : nullptr;
+    rc = blend_backward_checked(frame, reinterpret_cast<const uint32_t*>(base + L.ranges),
+                                reinterpret_cast<const uint32_t*>(base + L.point_list),
+                                reinterpret_cast<const float*>(base + L.splats),
+                                reinterpret_cast<const float*>(base + L.final_T),
+                                reinterpret_cast<const uint32_t*>(base + L.n_contrib), dL_dcolor, dL_ddepth, dL_dalpha,
+                                dsplats, dsplats_prezeroed, stream, bb_begin, bb_end);
+    if (rc) return rc;
+    return mark(stage_events, 1, false, reinterpret_cast<hipStream_t>(stream));
+}
+
 int scg_backward(const ScgFrame* frame, const float* means3D, const float* opacities, const float* shs,
                  const float* colors_precomp, const float* scales, const float* rotations, const float* cov3D_precomp,
                  const int32_t* radii, int64_t capacity, const void* workspace, const float* dL_dcolor,
@@ -557,28 +568,15 @@ int scg_backward(const ScgFrame* frame, const float* means3D, const float* opaci
     if (!frame) return fail(SCG_E_NULL, "frame is NULL");
     if (frame->P == 0) return 0;
     if (!workspace) return fail(SCG_E_NULL, "workspace is NULL");
-    ScgWorkspaceLayout L;
-    int rc = scg_workspace_layout(frame->P, capacity, frame->width, frame->height, &L);
+    const uint8_t* clamped;
+    int rc = backward_blend_stage(frame, capacity, workspace, dL_dcolor, dL_ddepth, dL_dalpha, dsplats, dsplats_prezeroed,
+                                  stage_events, stream, &clamped);
     if (rc) return rc;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const char* base = reinterpret_cast<const char*>(workspace);
-    // the blend backward's two stage events ride on its dispatch packet (begin / end time stamps of the kernel itself)
-    hipEvent_t bb_begin = stage_events ? reinterpret_cast<hipEvent_t>(stage_events->begin[0]) : nullptr;
-    hipEvent_t bb_end = stage_events ? reinterpret_cast<hipEvent_t>(stage_events->end[0]) : nullptr;
-    rc = blend_backward_checked(frame, reinterpret_cast<const uint32_t*>(base + L.ranges),
-                                reinterpret_cast<const uint32_t*>(base + L.point_list),
-                                reinterpret_cast<const float*>(base + L.splats),
-                                reinterpret_cast<const float*>(base + L.final_T),
-                                reinterpret_cast<const uint32_t*>(base + L.n_contrib), dL_dcolor, dL_ddepth, dL_dalpha,
-                                dsplats, dsplats_prezeroed, stream, bb_begin, bb_end);
+    rc = scg_geometry_backward(frame, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, radii, clamped,
+                               dsplats, dL_dmeans3D, dL_dmeans2D, dL_dopacities, dL_dshs, dL_dcolors_precomp, dL_dscales,
+                               dL_drotations, dL_dcov3D_precomp, accumulate, stream);
     if (rc) return rc;
-    if ((rc = mark(stage_events, 1, false, s))) return rc;
-    rc = scg_geometry_backward(frame, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, radii,
-                               reinterpret_cast<const uint8_t*>(base + L.clamped), dsplats, dL_dmeans3D, dL_dmeans2D,
-                               dL_dopacities, dL_dshs, dL_dcolors_precomp, dL_dscales, dL_drotations, dL_dcov3D_precomp,
-                               accumulate, stream);
-    if (rc) return rc;
-    return mark(stage_events, 1, true, s);
+    return mark(stage_events, 1, true, reinterpret_cast<hipStream_t>(stream));
 }
 
 int scg_backward_model(const ScgFrame* frame, const ScgModel* model, const int32_t* radii, int64_t capacity, const void* workspace,
@@ -601,24 +599,14 @@ int scg_backward_model(const ScgFrame* frame, const ScgModel* model, const int32
         if (!aligned16(gs.rotation) || !aligned16(gs.features_rest) || !aligned16(gs.features_dc))
             return fail(SCG_E_ALIGN, "grads.%s: rotation / features_rest / features_dc must be 16-byte aligned", k ? "bg" : "ray");
     }
-    ScgWorkspaceLayout L;
-    rc = scg_workspace_layout(frame->P, capacity, frame->width, frame->height, &L);
+    const uint8_t* clamped;
+    rc = backward_blend_stage(frame, capacity, workspace, dL_dcolor, dL_ddepth, dL_dalpha, dsplats, dsplats_prezeroed,
+                              stage_events, stream, &clamped);
     if (rc) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const char* base = reinterpret_cast<const char*>(workspace);
-    hipEvent_t bb_begin = stage_events ? reinterpret_cast<hipEvent_t>(stage_events->begin[0]) : nullptr;
-    hipEvent_t bb_end = stage_events ? reinterpret_cast<hipEvent_t>(stage_events->end[0]) : nullptr;
-    rc = blend_backward_checked(frame, reinterpret_cast<const uint32_t*>(base + L.ranges),
-                                reinterpret_cast<const uint32_t*>(base + L.point_list),
-                                reinterpret_cast<const float*>(base + L.splats),
-                                reinterpret_cast<const float*>(base + L.final_T),
-                                reinterpret_cast<const uint32_t*>(base + L.n_contrib), dL_dcolor, dL_ddepth, dL_dalpha,
-                                dsplats, dsplats_prezeroed, stream, bb_begin, bb_end);
-    if (rc) return rc;
-    if ((rc = mark(stage_events, 1, false, s))) return rc;
     const FrameDev f = make_frame_dev(frame);
-    rc = launch_geometry_backward_model(f, *model, *grads, radii, reinterpret_cast<const uint8_t*>(base + L.clamped), dsplats,
-                                        dL_dmeans2D, flags & (SCG_BACKWARD_ACCUMULATE | SCG_BACKWARD_SH_TAIL_ZERO), s);
+    rc = launch_geometry_backward_model(f, *model, *grads, radii, clamped, dsplats, dL_dmeans2D,
+                                        flags & (SCG_BACKWARD_ACCUMULATE | SCG_BACKWARD_SH_TAIL_ZERO), s);
     if (rc) return rc;
     return mark(stage_events, 1, true, s);
 }

@@ -27,6 +27,7 @@
 // fits the 160 KiB LDS of a CU with room to spare.
 #include "scg_common.h"
 #include "host_align.h"
+#include "probe_timeline.h"
 #include "tile_sort.h"
 #include "tile_walk.h"
 
@@ -392,11 +393,9 @@ __global__ __launch_bounds__(kScatterThreads) void tile_scatter_kernel(const uin
                             nr_out);
         return;
     }
-#ifdef SCG_PROBE_TIMELINE
-    uint32_t* tl = cost_out ? cost_out + n_tiles + ((size_t)blockIdx.x * kScatterWaves + wave_id()) * 8 : nullptr;
-    const uint32_t tl0 = (uint32_t)wall_clock64();
-    uint32_t tl_walk = 0, tl_nwalk = 0, tl_most = 0;
-#endif
+    SCG_PROBE(uint32_t* tl = cost_out ? SCG_TL_SCATTER_RECORD(cost_out, n_tiles, (size_t)blockIdx.x * kScatterWaves + wave_id()) : nullptr;
+              const uint32_t tl0 = probe_clock();
+              uint32_t tl_walk = 0, tl_nwalk = 0, tl_most = 0;)
     const int wg = (int)blockIdx.x - kBands;                   // (wg & 7 == blockIdx.x & 7: the band is still the XCD)
     const int band = wg & (kBands - 1), slice = wg >> 3;
     int r0, r1;
@@ -500,9 +499,7 @@ __global__ __launch_bounds__(kScatterThreads) void tile_scatter_kernel(const uin
     }
     __syncthreads();
 
-#ifdef SCG_PROBE_TIMELINE
-    const uint32_t tl1 = (uint32_t)wall_clock64();
-#endif
+    SCG_PROBE(const uint32_t tl1 = probe_clock();)
     uint2* qrect = s_qrect[w];
     uint32_t* qid = s_qid[w];
     auto drop = [&](uint32_t tile, uint32_t id) {
@@ -515,9 +512,7 @@ __global__ __launch_bounds__(kScatterThreads) void tile_scatter_kernel(const uin
     // No branch around an atomic (the compiler would wait behind each): a lane whose rectangle has ended adds to a dump slot
     // in the spare row behind the band's cursors.
     auto scatter_rects = [&](uint2 r, uint32_t g) {
-#ifdef SCG_PROBE_TIMELINE
-        const uint32_t tw0 = (uint32_t)wall_clock64();
-#endif
+        SCG_PROBE(const uint32_t tw0 = probe_clock();)
         const uint32_t wd = r.y & 0xFFFFu, ht = r.y >> 16;
         const uint32_t cnt = wd * ht;
         const uint32_t dump = (uint32_t)nt + (uint32_t)lane;
@@ -541,9 +536,7 @@ __global__ __launch_bounds__(kScatterThreads) void tile_scatter_kernel(const uin
                 if (k + u < small && pos[u] < capacity) point_list[pos[u]] = g;
         }
         walk_rects(cnt > kCoopThreshold ? r : make_uint2(0u, 0u), g, grid_x, drop);     // large rectangles: by the whole wave
-#ifdef SCG_PROBE_TIMELINE
-        tl_walk += (uint32_t)wall_clock64() - tw0; tl_nwalk += 1; tl_most += most;
-#endif
+        SCG_PROBE(tl_walk += probe_clock() - tw0; tl_nwalk += 1; tl_most += most;)
     };
     int qn = 0;                                                // wave-uniform queue length
     for (uint32_t g0 = ga; g0 < gb; g0 += kWave) {
@@ -584,12 +577,10 @@ __global__ __launch_bounds__(kScatterThreads) void tile_scatter_kernel(const uin
         if (lane < qn) { qr = qrect[lane]; qg = qid[lane]; }
         scatter_rects(qr, qg);
     }
-#ifdef SCG_PROBE_TIMELINE
-    if (tl && lane == 0) {
-        tl[0] = tl0; tl[1] = tl1; tl[2] = (uint32_t)wall_clock64(); tl[3] = tl_walk; tl[4] = tl_nwalk; tl[5] = tl_most;
-        tl[6] = gb - ga; tl[7] = 0xC0FFEEu;
-    }
-#endif
+    SCG_PROBE(if (tl && lane == 0) {
+        tl[0] = tl0; tl[1] = tl1; tl[2] = probe_clock(); tl[3] = tl_walk; tl[4] = tl_nwalk; tl[5] = tl_most;
+        tl[6] = gb - ga; tl[7] = kTlSigScatter;
+    })
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -944,8 +935,7 @@ static const DeviceSetup* device_setup() {
             e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(tile_split_long_kernel),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRareLds);
         const hipError_t e2 = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-        hipError_t e3 = geometry_hist_set_max_lds(kMaxDynLds);
-        if (e3 == hipSuccess) e3 = geometry_hist_model_set_max_lds(kMaxDynLds);
+        const hipError_t e3 = geometry_hist_set_max_lds(kMaxDynLds);
         d.n_cus = (e2 == hipSuccess && v > 0) ? v : 256;
         d.ok = (e0 == hipSuccess && e1 == hipSuccess && e3 == hipSuccess);
     });
@@ -995,33 +985,19 @@ bool tile_binning_hist_in_geometry(const FrameDev& f, int64_t R) {
                <= (size_t)kMaxDynLds - 2048;
 }
 
-int launch_geometry_hist_binned(const FrameDev& f, int64_t R, const float* means3D, const float* opacities, const float* shs,
-                                const float* colors_precomp, const float* scales, const float* rotations,
-                                const float* cov3D_precomp, float* splats, int32_t* radii, uint8_t* clamped, uint32_t* rects,
-                                uint32_t* depth_keys, uint32_t* block_sums, void* bin_scratch, hipStream_t stream) {
+int launch_geometry_hist_binned(const FrameDev& f, int64_t R, const GeoInputs& in, const GeoOutputs& out, void* bin_scratch,
+                                hipStream_t stream) {
     const TileBinningLayout L = tile_binning_layout(f.P, R, f.gx * f.gy);
     char* base = reinterpret_cast<char*>(bin_scratch);
     if (!device_setup()) return fail(SCG_E_RANGE, "tile binning: device setup failed (hipFuncSetAttribute / device query)");
-    return launch_geometry_hist(f, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, splats, radii,
-                                clamped, rects, depth_keys, block_sums, L.nblocks,
-                                reinterpret_cast<uint32_t*>(base + L.table), reinterpret_cast<uint32_t*>(base + L.class_counts),
+    return launch_geometry_hist(f, in, out, L.nblocks, reinterpret_cast<uint32_t*>(base + L.table),
+                                reinterpret_cast<uint32_t*>(base + L.class_counts),
                                 reinterpret_cast<uint32_t*>(base + L.len_hist), stream);
-}
-
-int launch_geometry_hist_binned_model(const FrameDev& f, int64_t R, const ScgModel& m, float* splats, int32_t* radii,
-                                      uint8_t* clamped, uint32_t* rects, uint32_t* depth_keys, uint32_t* block_sums,
-                                      void* bin_scratch, hipStream_t stream) {
-    const TileBinningLayout L = tile_binning_layout(f.P, R, f.gx * f.gy);
-    char* base = reinterpret_cast<char*>(bin_scratch);
-    if (!device_setup()) return fail(SCG_E_RANGE, "tile binning: device setup failed (hipFuncSetAttribute / device query)");
-    return launch_geometry_hist_model(f, m, splats, radii, clamped, rects, depth_keys, block_sums, L.nblocks,
-                                      reinterpret_cast<uint32_t*>(base + L.table), reinterpret_cast<uint32_t*>(base + L.class_counts),
-                                      reinterpret_cast<uint32_t*>(base + L.len_hist), stream);
 }
 
 int launch_tile_binning(const FrameDev& f, int64_t R, const uint32_t* rects, const uint32_t* depth_keys,
                         uint32_t* point_list, uint32_t* ranges, uint64_t* keys_sorted, void* scratch,
-                        bool* defer_sort, bool hist_done, bool skip_rare, bool rare8, bool split_long, hipStream_t stream) {
+                        const TileBinningOptions& opt, hipStream_t stream) {
     const int P = f.P;
     const int n_tiles = f.gx * f.gy;
     const TileBinningLayout L = tile_binning_layout(P, R, n_tiles);
@@ -1045,10 +1021,10 @@ int launch_tile_binning(const FrameDev& f, int64_t R, const uint32_t* rects, con
     const int nb = L.nblocks;
     const bool dense = R / n_tiles >= kDenseMeanList;       // R = the capacity the lists were sized for
     // the caller's forward blend sorts the common tiles itself: only the lists it does not take are sorted here
-    const bool deferred = defer_sort && *defer_sort && tile_binning_defers_sort(R, n_tiles) && !keys_sorted;
-    if (defer_sort) *defer_sort = deferred;
+    const bool deferred = opt.defer_sort && *opt.defer_sort && tile_binning_defers_sort(R, n_tiles) && !keys_sorted;
+    if (opt.defer_sort) *opt.defer_sort = deferred;
     const size_t lds_tiles = (size_t)n_tiles * sizeof(uint32_t);
-    if (!hist_done)
+    if (!opt.hist_done)
         hipLaunchKernelGGL(tile_hist_kernel, dim3(nb), dim3(kBinThreads), lds_tiles, stream, rects2, (uint32_t)P, f.gx,
                            n_tiles, table, class_counts, len_hist);
     // length classes: the average list lands around class 16..31
@@ -1061,7 +1037,7 @@ int launch_tile_binning(const FrameDev& f, int64_t R, const uint32_t* rects, con
                        (uint32_t)P, f.gx, f.gy, nb, table, tile_total, tile_part, point_list, (uint32_t)R, tile_start, ranges2,
                        class_counts, mid_tiles, big_tiles,
                        (uint32_t)(deferred ? fused_max_list(R, n_tiles) : dense ? kSortDenseMax : kSortSmallMax), len_hist, tile_class,
-                       f.cost_out, hist_done ? 1 : 0, f.bcost_in, f.nr_out);
+                       f.cost_out, opt.hist_done ? 1 : 0, f.bcost_in, f.nr_out);
     int id_bits = 8;
     while (id_bits < 32 && (1ll << id_bits) < (long long)P) id_bits += 8;
     if (deferred) {
@@ -1077,17 +1053,17 @@ int launch_tile_binning(const FrameDev& f, int64_t R, const uint32_t* rects, con
     // Not launched at all when the caller promises a frame without such lists (skip_rare: the forward blend that sorts its own
     // tiles has a fallback for a list that is longer after all).
     const int n_cus = ds->n_cus;
-    if (!(deferred && skip_rare)) {
-        if (rare8) {
+    if (!(deferred && opt.skip_rare)) {
+        if (opt.rare8) {
             // the camera's previous render is known: lists beyond kSort8Max entries (if it had any) are partitioned by depth,
             // then 8-wave workgroups, three per compute unit, sort the parts and the mid-size tiles
-            if (split_long)
+            if (opt.split_long)
                 hipLaunchKernelGGL(tile_split_long_kernel, dim3(n_tiles < n_cus ? n_tiles : n_cus), dim3(kRareThreads), kRareLds,
                                    stream, ranges2, depth_keys, point_list, spill, spill + R, class_counts, mid_tiles, big_tiles,
                                    segments);
             hipLaunchKernelGGL(tile_sort_list8_kernel, dim3(3 * n_cus), dim3(kList8Threads), 0, stream, ranges2, depth_keys,
                                point_list, id_bits, spill, spill + R, class_counts, mid_tiles, big_tiles, segments,
-                               split_long ? 1 : 0);
+                               opt.split_long ? 1 : 0);
         } else {
             hipLaunchKernelGGL(tile_sort_rare_kernel, dim3(n_tiles < n_cus ? n_tiles : n_cus), dim3(kRareThreads), kRareLds,
                                stream, ranges2, depth_keys, point_list, id_bits, spill, spill + R, class_counts, mid_tiles,

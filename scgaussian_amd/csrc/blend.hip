@@ -36,6 +36,7 @@
 //     instruction count of its trip almost 1:1 (four v_mov more per trip: +6 %; thirteen scalar instructions and
 //     branches less: -4 %).  Hence the hand-written forward trip below.
 #include "scg_common.h"
+#include "probe_timeline.h"
 #include "reduce.h"
 #include "tile_sort.h"
 
@@ -348,30 +349,22 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(WPE,
     if (tile >= n_tiles) return;
     const uint2 range = ranges[tile];
     const int n = (int)(range.y - range.x);
-#ifdef SCG_PROBE_TIMELINE                    // tools/probes/blend_timeline.py: per-workgroup clocks behind the other kernels' logs
-    const uint32_t tp0 = (uint32_t)wall_clock64();
-#endif
+    SCG_PROBE(const uint32_t tp0 = probe_clock();)   // tools/probes/blend_timeline.py: per-workgroup clocks
     const bool ids_in_lds = n >= 2 && n <= MAX_N;
     if (ids_in_lds) sort_one_tile<NW, MAX_N, CNT, true>(L, range, depth_keys, point_list, id_bits);
     else if (n > MAX_N && !long_presorted)
         fused_long_list_fallback<NW>(smem, depth_keys, point_list + range.x, n, spill + range.x, spill2 + range.x);
     // the sorted ids are in L.id (lists this workgroup sorted in LDS; on their way to point_list for the backward) or in
     // point_list (visible to the whole workgroup behind the barrier); the rest of the sort's LDS is free
-#ifdef SCG_PROBE_TIMELINE
-    const uint32_t tp1 = (uint32_t)wall_clock64();
-    uint32_t pr[6];
-    for (int k = 0; k < 6; ++k) pr[k] = L.probe[k];
-    __syncthreads();
-#else
+    SCG_PROBE(const uint32_t tp1 = probe_clock();
+              uint32_t pr[6];
+              for (int k = 0; k < 6; ++k) pr[k] = L.probe[k];)
     // (a list sorted in LDS: the sort's last barrier stands behind its last read of the scratch the record planes overwrite and
-    //  behind the last write of L.id — no second one)
-    if (!ids_in_lds) __syncthreads();
-#endif
+    //  behind the last write of L.id — no second one; the probe build has just read the sort's clocks from that scratch)
+    if (!ids_in_lds || kProbeTimeline) __syncthreads();
     const int quad = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & (kWave - 1);
     if (NW > 4 && quad >= 4) return;                 // the waves that only helped to sort
-#ifdef SCG_PROBE_TIMELINE
-    const uint32_t tp2 = (uint32_t)wall_clock64();
-#endif
+    SCG_PROBE(const uint32_t tp2 = probe_clock();)
     float4* planes = reinterpret_cast<float4*>(smem + kIdsBytes) + quad * 3 * kWave;
     if (ids_in_lds)
         forward_walk(planes, f, tile, quad, lane, range, reinterpret_cast<LdsIds>((uintptr_t)(uint32_t)reinterpret_cast<uintptr_t>(&L.id[0])),
@@ -379,18 +372,16 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(WPE,
     else
         forward_walk(planes, f, tile, quad, lane, range, point_list + range.x, splats, out_color, out_depth, out_alpha, final_T,
                      n_contrib);
-#ifdef SCG_PROBE_TIMELINE
-    if (f.cost_out && lane == 0) {
-        uint32_t* tl = f.cost_out + n_tiles + 65792 + 32768 + ((size_t)blockIdx.x * 4 + quad) * 8;
-        tl[0] = tp0; tl[1] = tp1; tl[2] = tp2; tl[3] = (uint32_t)wall_clock64(); tl[4] = (uint32_t)n; tl[5] = (uint32_t)tile;
-        tl[6] = 0u; tl[7] = 0xB1E9D000u;
-        if (quad == 0) {        // the sort's internal clocks: a second record behind the kernel's (index n_slots * 4 + blockIdx)
-            uint32_t* t2 = f.cost_out + n_tiles + 65792 + 32768 + ((size_t)tile_order_slots(n_tiles) * 4 + blockIdx.x) * 8;
+    SCG_PROBE(if (f.cost_out && lane == 0) {
+        uint32_t* tl = SCG_TL_BLEND_RECORD(f.cost_out, n_tiles, (size_t)blockIdx.x * 4 + quad);
+        tl[0] = tp0; tl[1] = tp1; tl[2] = tp2; tl[3] = probe_clock(); tl[4] = (uint32_t)n; tl[5] = (uint32_t)tile;
+        tl[6] = 0u; tl[7] = kTlSigBlend;
+        if (quad == 0) {        // the sort's internal clocks: a second record behind the quadrant waves'
+            uint32_t* t2 = SCG_TL_BLEND_RECORD(f.cost_out, n_tiles, SCG_TL_SORT_INDEX(n_tiles, blockIdx.x));
             for (int k = 0; k < 6; ++k) t2[k] = pr[k];
-            t2[6] = tp0; t2[7] = 0x50B70000u;
+            t2[6] = tp0; t2[7] = kTlSigSort;
         }
-    }
-#endif
+    })
 }
 
 int launch_tile_blend_forward(const FrameDev& f, const uint32_t* ranges, uint32_t* point_list, const uint32_t* depth_keys,
@@ -988,9 +979,7 @@ __global__ __launch_bounds__(kWave) SCG_BWD_OCCUPANCY void blend_backward_kernel
     // highest list index any pixel of the quadrant blended
     const uint32_t mx = wave_reduce((uint32_t)s.last, Max());
     const int limit = min(n, __builtin_amdgcn_readfirstlane((int)mx));
-#ifdef SCG_PROBE_TIMELINE                // tools/probes/backward_timeline.py
-    const uint32_t tp0 = (uint32_t)wall_clock64();
-#endif
+    SCG_PROBE(const uint32_t tp0 = probe_clock();)   // tools/probes/backward_timeline.py
     if (limit <= 0) {
         if (f.bcost_out && lane == 0) f.bcost_out[4 * tile + quad] = 0u;
         return;
@@ -1001,13 +990,11 @@ __global__ __launch_bounds__(kWave) SCG_BWD_OCCUPANCY void blend_backward_kernel
     // wave's time depends on when it ran — round-5 timeline: waves ordered by their previous time came out uncorrelated.)
     // (trips alone: with the entries walked mixed in — trips + entries / 4 — the same or worse, S2 101.1 vs 100.5 us)
     if (f.bcost_out && lane == 0) f.bcost_out[4 * tile + quad] = (uint32_t)trips;
-#ifdef SCG_PROBE_TIMELINE
-    if (f.cost_out && lane == 0) {
-        uint32_t* tl = f.cost_out + n_tiles + 65792 + 32768 + (size_t)(n_tiles + 8) * 40 + (size_t)blockIdx.x * 4;
-        tl[0] = tp0; tl[1] = (uint32_t)wall_clock64(); tl[2] = ((uint32_t)min(trips, 65535) << 16) | (uint32_t)min(limit, 65535);
-        tl[3] = 0xBAC00000u | (uint32_t)(4 * tile + quad);
-    }
-#endif
+    SCG_PROBE(if (f.cost_out && lane == 0) {
+        uint32_t* tl = SCG_TL_BACKWARD_RECORD(f.cost_out, n_tiles, (size_t)blockIdx.x);
+        tl[0] = tp0; tl[1] = probe_clock(); tl[2] = ((uint32_t)min(trips, 65535) << 16) | (uint32_t)min(limit, 65535);
+        tl[3] = kTlSigBackward | (uint32_t)(4 * tile + quad);
+    })
 }
 
 int launch_blend_backward(const FrameDev& f, const uint32_t* ranges, const uint32_t* point_list,

@@ -15,11 +15,11 @@
 // lane-contiguous; the 192-byte SH record is read with 16-byte loads (12 per lane at degree 3).
 #include "scg_common.h"
 #include "host_align.h"
+#include "probe_timeline.h"
 #include "reduce.h"
 #include "tile_walk.h"
 #include "sh_eval.h"
 
-#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -338,11 +338,8 @@ __device__ __forceinline__ void flush_stage(const float4* stage, int first, int 
 template <int DEG, class Src, class Between>
 __device__ __forceinline__ uint32_t geometry_forward_one(
     const FrameDev& f, const Mat16& V, const Mat16& PM, int i, bool valid, const GeoIn& in,
-    const Src& src, float4* stage /* LDS, kStageVec float4 of this wave */, Between&& between
-#ifdef SCG_PROBE_TIMELINE                       // tools/probes/geometry_timeline.py: per-wave phase clocks
-    , uint32_t* g_tp
-#endif
-    ) {
+    const Src& src, float4* stage /* LDS, kStageVec float4 of this wave */, Between&& between,
+    GeoProbe& probe /* probe_timeline.h: the wave's phase clocks in the probe build, empty otherwise */) {
     uint32_t my_tiles = 0;
     float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = sa, sc = sa;
     int radius_i = 0;
@@ -390,18 +387,15 @@ __device__ __forceinline__ uint32_t geometry_forward_one(
     constexpr bool has_colors = DEG < 0;
     constexpr int K = has_colors ? 1 : (DEG + 1) * (DEG + 1);
     float sh[(3 * K + 3) / 4 * 4];
-#ifdef SCG_PROBE_TIMELINE
-    { float pin = con_a; asm volatile("" : "+v"(pin)); }          // the cull / covariance chain is done (inputs have arrived)
-    const uint32_t tp_math = (uint32_t)wall_clock64();
-#endif
+    SCG_PROBE({ float pin = con_a; asm volatile("" : "+v"(pin)); }          // the cull / covariance chain is done (inputs have arrived)
+              const uint32_t tp_math = probe_clock();)
     if (!has_colors) src.template load_sh<K>(ok ? i : 0, sh);
     between(rect);
-#ifdef SCG_PROBE_TIMELINE
-    const uint32_t tp_between = (uint32_t)wall_clock64();
-    asm volatile("" : "+v"(sh[0]), "+v"(sh[(3 * K + 3) / 4 * 4 - 1]));        // the SH record has arrived
-    const uint32_t tp_sh = (uint32_t)wall_clock64();
-    g_tp[0] += tp_math - g_tp[4]; g_tp[1] += tp_between - tp_math; g_tp[2] += tp_sh - tp_between; g_tp[4] = tp_sh;
-#endif
+    SCG_PROBE(const uint32_t tp_between = probe_clock();
+              asm volatile("" : "+v"(sh[0]), "+v"(sh[(3 * K + 3) / 4 * 4 - 1]));        // the SH record has arrived
+              const uint32_t tp_sh = probe_clock();
+              probe[0] += tp_math - probe[4]; probe[1] += tp_between - tp_math; probe[2] += tp_sh - tp_between;
+              probe[4] = tp_sh;)
     if (ok) {
         float rgb[3];
         if (has_colors) {
@@ -448,15 +442,8 @@ __device__ __forceinline__ void geometry_forward_body(
     const Mat16 V = load16(f.view);
     const Mat16 PM = load16(f.proj);
     float4* stage = s_stage + kStageVec * wave_id();
-#ifdef SCG_PROBE_TIMELINE
-    uint32_t tp_dummy[5] = {0u, 0u, 0u, 0u, 0u};
-#endif
-    const uint32_t my_tiles = geometry_forward_one<DEG>(f, V, PM, i, valid, in, src, stage,
-                                                        [](uint2) {}
-#ifdef SCG_PROBE_TIMELINE
-                                                        , tp_dummy
-#endif
-                                                        );
+    GeoProbe probe = {};                                       // (logged by geometry_hist_kernel only)
+    const uint32_t my_tiles = geometry_forward_one<DEG>(f, V, PM, i, valid, in, src, stage, [](uint2) {}, probe);
     flush_stage(stage, i - lane_id(), f.P, splats, radii, clamped, rects, depth_keys);
 
     // per-block sum of tiles_touched: first phase of the inclusive scan, fused here
@@ -536,11 +523,8 @@ __device__ __forceinline__ void geometry_hist_body(
     if (threadIdx.x == 0) *next_chunk = 4u * blk_a + (uint32_t)kBinWaves;
     __syncthreads();
     int pending = -1;                                          // first Gaussian of the chunk parked in the stage, -1: none
-#ifdef SCG_PROBE_TIMELINE
-    uint32_t g_tp[5] = {0u, 0u, 0u, 0u, (uint32_t)wall_clock64()};
-    const uint32_t tp_begin = g_tp[4];
-    uint32_t tp_iters = 0;
-#endif
+    GeoProbe probe = {};
+    SCG_PROBE(probe[4] = probe_clock(); const uint32_t tp_begin = probe[4]; uint32_t tp_iters = 0;)
     while (chunk < 4u * blk_b) {
         const int i = (int)(chunk * kWave) + lane;
         const GeoIn in = fetch(chunk);
@@ -552,31 +536,21 @@ __device__ __forceinline__ void geometry_hist_body(
                 // (the loads of this chunk's SH records are in flight: now the previous chunk's outputs leave, then the histogram)
                 if (pending >= 0) flush_stage(stage, pending, f.P, splats, radii, clamped, rects, depth_keys);
                 walk_rects(rect, (uint32_t)i, f.gx, [&](uint32_t tile, uint32_t) { atomicAdd(&hist[tile], 1u); });
-            }
-#ifdef SCG_PROBE_TIMELINE
-            , g_tp
-#endif
-            );
-#ifdef SCG_PROBE_TIMELINE
-        { const uint32_t t = (uint32_t)wall_clock64(); g_tp[3] += t - g_tp[4]; g_tp[4] = t; ++tp_iters; }
-#endif
+            }, probe);
+        SCG_PROBE({ const uint32_t t = probe_clock(); probe[3] += t - probe[4]; probe[4] = t; ++tp_iters; })
         pending = i - lane;
         const uint32_t s = wave_reduce(my_tiles, Sum());
         if (lane == 0 && s) atomicAdd(&s_blk[(chunk >> 2) - blk_a], s);
         chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)grabbed);
     }
     if (pending >= 0) flush_stage(stage, pending, f.P, splats, radii, clamped, rects, depth_keys);
-#ifdef SCG_PROBE_TIMELINE
-    const uint32_t tp_loop_end = (uint32_t)wall_clock64();
-#endif
+    SCG_PROBE(const uint32_t tp_loop_end = probe_clock();)
     __syncthreads();
-#ifdef SCG_PROBE_TIMELINE
-    if (f.cost_out && lane == 0) {
-        uint32_t* tl = f.cost_out + n_tiles + 65792 + ((size_t)blockIdx.x * kBinWaves + wave_id()) * 8;   // (behind the scatter's log)
-        tl[0] = tp_begin; tl[1] = g_tp[0]; tl[2] = g_tp[1]; tl[3] = g_tp[2]; tl[4] = g_tp[3]; tl[5] = tp_loop_end;
-        tl[6] = (uint32_t)wall_clock64(); tl[7] = 0xC0FFEE00u | tp_iters;
-    }
-#endif
+    SCG_PROBE(if (f.cost_out && lane == 0) {
+        uint32_t* tl = SCG_TL_GEOMETRY_RECORD(f.cost_out, n_tiles, (size_t)blockIdx.x * kBinWaves + wave_id());
+        tl[0] = tp_begin; tl[1] = probe[0]; tl[2] = probe[1]; tl[3] = probe[2]; tl[4] = probe[3]; tl[5] = tp_loop_end;
+        tl[6] = probe_clock(); tl[7] = kTlSigGeometry | tp_iters;
+    })
     uint32_t* row = table + (size_t)blockIdx.x * n_tiles;
     for (int t = threadIdx.x; t < n_tiles; t += kBinThreads) row[t] = hist[t];
     for (uint32_t k = threadIdx.x; k < blk_b - blk_a; k += kBinThreads) block_sums[blk_a + k] = s_blk[k];
@@ -1309,120 +1283,88 @@ __global__ __launch_bounds__(kBlock) void model_activate_kernel(ScgModel m, int 
 // ---------------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------------
-// degree -> kernel instantiation (-1: precomputed colours)
-template <class F>
-static inline void by_degree(int deg, F&& f) {
-    switch (deg) {
-        case -1: f(std::integral_constant<int, -1>()); break;
-        case 0: f(std::integral_constant<int, 0>()); break;
-        case 1: f(std::integral_constant<int, 1>()); break;
-        case 2: f(std::integral_constant<int, 2>()); break;
-        default: f(std::integral_constant<int, 3>()); break;
-    }
-}
+// (The kernels stand in the code object in the order in which this section names them: the tensor kernels' tables, the
+// backward, the model kernels' tables.)
+// degree -> kernel instantiation: entry D + 1 (-1: precomputed colours; the model has none, its entry 0 is never launched)
+static constexpr decltype(&geometry_forward_kernel<0>) kForwardKernels[5] = {
+    geometry_forward_kernel<-1>, geometry_forward_kernel<0>, geometry_forward_kernel<1>, geometry_forward_kernel<2>,
+    geometry_forward_kernel<3>};
+static constexpr decltype(&geometry_hist_kernel<0>) kHistKernels[5] = {
+    geometry_hist_kernel<-1>, geometry_hist_kernel<0>, geometry_hist_kernel<1>, geometry_hist_kernel<2>, geometry_hist_kernel<3>};
+static inline int degree_entry(const FrameDev& f, const GeoInputs& in) { return ((!in.model && in.colors_precomp) ? -1 : f.D < 3 ? f.D : 3) + 1; }
 
-int launch_geometry_forward(const FrameDev& f, const float* means3D, const float* opacities, const float* shs,
-                            const float* colors_precomp, const float* scales, const float* rotations,
-                            const float* cov3D_precomp, float* splats, int32_t* radii, uint8_t* clamped,
-                            uint32_t* rects, uint32_t* depth_keys, uint32_t* block_sums, hipStream_t stream) {
-    const int blocks = (f.P + kBlock - 1) / kBlock;
-    const int vec16 = (shs && aligned16(shs) && ((f.M * 3 * 4) % 16 == 0)) ? 1 : 0;
-    by_degree(colors_precomp ? -1 : f.D, [&](auto deg) {
-        hipLaunchKernelGGL(geometry_forward_kernel<decltype(deg)::value>, dim3(blocks), dim3(kBlock), 0, stream, f, means3D,
-                           opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, reinterpret_cast<float4*>(splats),
-                           radii, clamped, reinterpret_cast<uint2*>(rects), depth_keys, block_sums, vec16);
-    });
-    return check_hip(hipGetLastError(), "geometry_forward_kernel");
-}
+// the SH records can be read as 16-byte vectors
+static inline int sh_vec16(const GeoInputs& in, int M) { return (in.shs && aligned16(in.shs) && ((M * 3 * 4) % 16 == 0)) ? 1 : 0; }
 
-// the dynamic-LDS ceiling of every instantiation of geometry_hist_kernel (binning_tiles.hip device_setup, once per device)
-hipError_t geometry_hist_set_max_lds(int bytes) {
-    hipError_t rc = hipSuccess;
-    for (int deg = -1; deg <= 3; ++deg)
-        by_degree(deg, [&](auto d) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(geometry_hist_kernel<decltype(d)::value>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e != hipSuccess) rc = e;
-        });
-    return rc;
-}
-
-int launch_geometry_hist(const FrameDev& f, const float* means3D, const float* opacities, const float* shs,
-                         const float* colors_precomp, const float* scales, const float* rotations,
-                         const float* cov3D_precomp, float* splats, int32_t* radii, uint8_t* clamped, uint32_t* rects,
-                         uint32_t* depth_keys, uint32_t* block_sums, int nblocks, uint32_t* table, uint32_t* class_counts,
-                         uint32_t* len_hist, hipStream_t stream) {
-    const int vec16 = (shs && aligned16(shs) && ((f.M * 3 * 4) % 16 == 0)) ? 1 : 0;
-    const int n_tiles = f.gx * f.gy;
-    const int nb256 = (f.P + kBlock - 1) / kBlock;
-    const int max_blocks = nb256 / nblocks + 2;                // 256-Gaussian blocks of one workgroup's slice, at most
-    const size_t lds = geometry_hist_lds_bytes(n_tiles, max_blocks);
-    by_degree(colors_precomp ? -1 : f.D, [&](auto deg) {
-        hipLaunchKernelGGL(geometry_hist_kernel<decltype(deg)::value>, dim3(nblocks), dim3(kBinThreads), lds, stream, f, means3D,
-                           opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, reinterpret_cast<float4*>(splats),
-                           radii, clamped, reinterpret_cast<uint2*>(rects), depth_keys, block_sums, vec16, table, class_counts,
-                           len_hist, max_blocks);
-    });
-    return check_hip(hipGetLastError(), "geometry_hist_kernel");
-}
-
-int launch_geometry_backward(const FrameDev& f, const float* means3D, const float* opacities, const float* shs,
-                             const float* colors_precomp, const float* scales, const float* rotations,
-                             const float* cov3D_precomp, const int32_t* radii, const uint8_t* clamped,
+int launch_geometry_backward(const FrameDev& f, const GeoInputs& in, const int32_t* radii, const uint8_t* clamped,
                              const float* dsplats, float* dmeans3D, float* dmeans2D, float* dopac, float* dshs,
                              float* dcolors, float* dscales, float* drots, float* dcov3D, int flags,
                              hipStream_t stream) {
-    const int vec16 = (shs && aligned16(shs) && ((f.M * 3 * 4) % 16 == 0)) ? 1 : 0;
+    const int vec16 = sh_vec16(in, f.M);
     const bool staged = vec16 && dshs && aligned16(dshs) && f.M == 16;
     const int block = staged ? kWave : kBlock;
     const int recs = staged ? 60 : kBlock;                     // Gaussians per workgroup (geometry_backward_kernel: RECS)
     const int blocks = (f.P + recs - 1) / recs;
     auto kernel = !staged ? geometry_backward_kernel<false, kBlock>
                           : (f.D >= 3 ? geometry_backward_kernel<true, kWave, true> : geometry_backward_kernel<true, kWave, false>);
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(block), 0, stream, f, means3D, opacities, shs, colors_precomp, scales, rotations,
-                       cov3D_precomp, radii, clamped, reinterpret_cast<const float4*>(dsplats), dmeans3D, dmeans2D, dopac,
-                       dshs, dcolors, dscales, drots, dcov3D, vec16, flags);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(block), 0, stream, f, in.means3D, in.opacities, in.shs, in.colors_precomp,
+                       in.scales, in.rotations, in.cov3D_precomp, radii, clamped, reinterpret_cast<const float4*>(dsplats), dmeans3D,
+                       dmeans2D, dopac, dshs, dcolors, dscales, drots, dcov3D, vec16, flags);
     return check_hip(hipGetLastError(), "geometry_backward_kernel");
 }
 
-// ---- model path ------------------------------------------------------------------------------------------------------------
-int launch_geometry_forward_model(const FrameDev& f, const ScgModel& m, float* splats, int32_t* radii, uint8_t* clamped,
-                                  uint32_t* rects, uint32_t* depth_keys, uint32_t* block_sums, hipStream_t stream) {
-    const int blocks = (f.P + kBlock - 1) / kBlock;
-    by_degree(f.D, [&](auto deg) {
-        hipLaunchKernelGGL(geometry_forward_model_kernel<decltype(deg)::value>, dim3(blocks), dim3(kBlock), 0, stream, f, m,
-                           reinterpret_cast<float4*>(splats), radii, clamped, reinterpret_cast<uint2*>(rects), depth_keys,
-                           block_sums);
-    });
-    return check_hip(hipGetLastError(), "geometry_forward_model_kernel");
+static constexpr decltype(&geometry_forward_model_kernel<0>) kForwardModelKernels[5] = {
+    geometry_forward_model_kernel<-1>, geometry_forward_model_kernel<0>, geometry_forward_model_kernel<1>,
+    geometry_forward_model_kernel<2>, geometry_forward_model_kernel<3>};
+static constexpr decltype(&geometry_hist_model_kernel<0>) kHistModelKernels[5] = {
+    geometry_hist_model_kernel<-1>, geometry_hist_model_kernel<0>, geometry_hist_model_kernel<1>, geometry_hist_model_kernel<2>,
+    geometry_hist_model_kernel<3>};
+
+int launch_geometry_forward(const FrameDev& f, const GeoInputs& in, const GeoOutputs& out, hipStream_t stream) {
+    const int blocks = (f.P + kBlock - 1) / kBlock, d = degree_entry(f, in);
+    float4* splats = reinterpret_cast<float4*>(out.splats);
+    uint2* rects = reinterpret_cast<uint2*>(out.rects);
+    if (in.model)
+        hipLaunchKernelGGL(kForwardModelKernels[d], dim3(blocks), dim3(kBlock), 0, stream, f, *in.model, splats, out.radii,
+                           out.clamped, rects, out.depth_keys, out.block_sums);
+    else
+        hipLaunchKernelGGL(kForwardKernels[d], dim3(blocks), dim3(kBlock), 0, stream, f, in.means3D, in.opacities, in.shs,
+                           in.colors_precomp, in.scales, in.rotations, in.cov3D_precomp, splats, out.radii, out.clamped, rects,
+                           out.depth_keys, out.block_sums, sh_vec16(in, f.M));
+    return check_hip(hipGetLastError(), in.model ? "geometry_forward_model_kernel" : "geometry_forward_kernel");
 }
 
-hipError_t geometry_hist_model_set_max_lds(int bytes) {
+// the dynamic-LDS ceiling of every instantiation of geometry_hist_kernel and geometry_hist_model_kernel (binning_tiles.hip
+// device_setup, once per device)
+hipError_t geometry_hist_set_max_lds(int bytes) {
     hipError_t rc = hipSuccess;
-    for (int deg = 0; deg <= 3; ++deg)
-        by_degree(deg, [&](auto d) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(geometry_hist_model_kernel<decltype(d)::value>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    for (int d = 0; d < 5; ++d)
+        for (const void* kernel : {reinterpret_cast<const void*>(kHistKernels[d]), reinterpret_cast<const void*>(kHistModelKernels[d])}) {
+            const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
             if (e != hipSuccess) rc = e;
-        });
+        }
     return rc;
 }
 
-int launch_geometry_hist_model(const FrameDev& f, const ScgModel& m, float* splats, int32_t* radii, uint8_t* clamped,
-                               uint32_t* rects, uint32_t* depth_keys, uint32_t* block_sums, int nblocks, uint32_t* table,
-                               uint32_t* class_counts, uint32_t* len_hist, hipStream_t stream) {
-    const int n_tiles = f.gx * f.gy;
+int launch_geometry_hist(const FrameDev& f, const GeoInputs& in, const GeoOutputs& out, int nblocks, uint32_t* table,
+                         uint32_t* class_counts, uint32_t* len_hist, hipStream_t stream) {
+    const int n_tiles = f.gx * f.gy, d = degree_entry(f, in);
     const int nb256 = (f.P + kBlock - 1) / kBlock;
-    const int max_blocks = nb256 / nblocks + 2;
+    const int max_blocks = nb256 / nblocks + 2;                // 256-Gaussian blocks of one workgroup's slice, at most
     const size_t lds = geometry_hist_lds_bytes(n_tiles, max_blocks);
-    by_degree(f.D, [&](auto deg) {
-        hipLaunchKernelGGL(geometry_hist_model_kernel<decltype(deg)::value>, dim3(nblocks), dim3(kBinThreads), lds, stream, f, m,
-                           reinterpret_cast<float4*>(splats), radii, clamped, reinterpret_cast<uint2*>(rects), depth_keys,
-                           block_sums, table, class_counts, len_hist, max_blocks);
-    });
-    return check_hip(hipGetLastError(), "geometry_hist_model_kernel");
+    float4* splats = reinterpret_cast<float4*>(out.splats);
+    uint2* rects = reinterpret_cast<uint2*>(out.rects);
+    if (in.model)
+        hipLaunchKernelGGL(kHistModelKernels[d], dim3(nblocks), dim3(kBinThreads), lds, stream, f, *in.model, splats, out.radii,
+                           out.clamped, rects, out.depth_keys, out.block_sums, table, class_counts, len_hist, max_blocks);
+    else
+        hipLaunchKernelGGL(kHistKernels[d], dim3(nblocks), dim3(kBinThreads), lds, stream, f, in.means3D, in.opacities, in.shs,
+                           in.colors_precomp, in.scales, in.rotations, in.cov3D_precomp, splats, out.radii, out.clamped, rects,
+                           out.depth_keys, out.block_sums, sh_vec16(in, f.M), table, class_counts, len_hist, max_blocks);
+    return check_hip(hipGetLastError(), in.model ? "geometry_hist_model_kernel" : "geometry_hist_kernel");
 }
 
+// ---- model path ------------------------------------------------------------------------------------------------------------
 int launch_geometry_backward_model(const FrameDev& f, const ScgModel& m, const ScgModelGrads& g, const int32_t* radii,
                                    const uint8_t* clamped, const float* dsplats, float* dmeans2D, int flags, hipStream_t stream) {
     const int blocks_ray = (m.ray.count + kModelRecs - 1) / kModelRecs;

@@ -64,27 +64,26 @@ int check_hip(hipError_t e, const char* what);
 int check_workspace(const char* who, const void* ws, size_t bytes, size_t need);   // NULL, then too small, then not 4-byte aligned
 int validate_frame(const ScgFrame* f, bool need_bg);
 
+// What a geometry launch reads: the operator's seven ACTIVATED tensors or, with `model` set, the reference model's raw parameter
+// tensors (geometry.hip TensorSource / ModelSource).  Each C entry wraps its arguments once; everything below takes the bundle.
+struct GeoInputs {
+    const float* means3D = nullptr; const float* opacities = nullptr; const float* shs = nullptr;
+    const float* colors_precomp = nullptr; const float* scales = nullptr; const float* rotations = nullptr;
+    const float* cov3D_precomp = nullptr;
+    const ScgModel* model = nullptr;
+};
+// ... and what the forward geometry stage writes per Gaussian (block_sums: per 256 of them)
+struct GeoOutputs {
+    float* splats; int32_t* radii; uint8_t* clamped; uint32_t* rects; uint32_t* depth_keys; uint32_t* block_sums;
+};
+
 // stage launchers (each returns 0 or an error code; all work goes on `stream`)
-int launch_geometry_forward(const FrameDev& f, const float* means3D, const float* opacities, const float* shs,
-                            const float* colors_precomp, const float* scales, const float* rotations,
-                            const float* cov3D_precomp, float* splats, int32_t* radii, uint8_t* clamped,
-                            uint32_t* rects, uint32_t* depth_keys, uint32_t* block_sums, hipStream_t stream);
-int launch_geometry_backward(const FrameDev& f, const float* means3D, const float* opacities, const float* shs,
-                             const float* colors_precomp, const float* scales, const float* rotations,
-                             const float* cov3D_precomp, const int32_t* radii, const uint8_t* clamped,
+int launch_geometry_forward(const FrameDev& f, const GeoInputs& in, const GeoOutputs& out, hipStream_t stream);
+int launch_geometry_backward(const FrameDev& f, const GeoInputs& in /* the tensors */, const int32_t* radii, const uint8_t* clamped,
                              const float* dsplats, float* dmeans3D, float* dmeans2D, float* dopac, float* dshs,
                              float* dcolors, float* dscales, float* drots, float* dcov3D, int flags /* SCG_BACKWARD_* */,
                              hipStream_t stream);
-// the model path (ScgModel: the reference model's raw parameter tensors; geometry.hip ModelSource)
-int launch_geometry_forward_model(const FrameDev& f, const ScgModel& m, float* splats, int32_t* radii, uint8_t* clamped,
-                                  uint32_t* rects, uint32_t* depth_keys, uint32_t* block_sums, hipStream_t stream);
-int launch_geometry_hist_model(const FrameDev& f, const ScgModel& m, float* splats, int32_t* radii, uint8_t* clamped,
-                               uint32_t* rects, uint32_t* depth_keys, uint32_t* block_sums, int nblocks, uint32_t* table,
-                               uint32_t* class_counts, uint32_t* len_hist, hipStream_t stream);
-int launch_geometry_hist_binned_model(const FrameDev& f, int64_t R, const ScgModel& m, float* splats, int32_t* radii,
-                                      uint8_t* clamped, uint32_t* rects, uint32_t* depth_keys, uint32_t* block_sums,
-                                      void* bin_scratch, hipStream_t stream);
-hipError_t geometry_hist_model_set_max_lds(int bytes);
+// the model path's own launchers (ScgModel: their outputs differ)
 int launch_geometry_backward_model(const FrameDev& f, const ScgModel& m, const ScgModelGrads& g, const int32_t* radii,
                                    const uint8_t* clamped, const float* dsplats, float* dmeans2D, int flags, hipStream_t stream);
 int launch_model_activate(const ScgModel& m, float* means3D, float* opacities, float* scales, float* rotations,
@@ -140,22 +139,21 @@ __host__ __device__ inline int fused_max_list(int64_t R, int n_tiles) {
 // fallback takes a long list that shows up after all).  rare8: sort the rarer list sizes with 8-wave workgroups, three per
 // compute unit (SCG_FORWARD_RARE_8WAVE); split_long: with rare8, partition the lists beyond 4 096 entries by depth first
 // (tile_split_long_kernel: their parts are sorted by all compute units; SCG_FORWARD_SPLIT_LONG_LISTS).
+struct TileBinningOptions {
+    bool* defer_sort = nullptr;
+    bool hist_done = false, skip_rare = false, rare8 = false, split_long = false;
+};
 int launch_tile_binning(const FrameDev& f, int64_t R, const uint32_t* rects, const uint32_t* depth_keys,
                         uint32_t* point_list, uint32_t* ranges, uint64_t* keys_sorted, void* scratch,
-                        bool* defer_sort, bool hist_done, bool skip_rare, bool rare8, bool split_long, hipStream_t stream);
+                        const TileBinningOptions& opt, hipStream_t stream);
 // geometry_forward + the tile histogram of the tile-first binning in one kernel (the one-call path).  `bin_scratch`, R as
 // for launch_tile_binning, which must follow with hist_done = true.  Returns > 0 (a code of fail()) on error.
 bool tile_binning_hist_in_geometry(const FrameDev& f, int64_t R);
-int launch_geometry_hist_binned(const FrameDev& f, int64_t R, const float* means3D, const float* opacities, const float* shs,
-                                const float* colors_precomp, const float* scales, const float* rotations,
-                                const float* cov3D_precomp, float* splats, int32_t* radii, uint8_t* clamped, uint32_t* rects,
-                                uint32_t* depth_keys, uint32_t* block_sums, void* bin_scratch, hipStream_t stream);
-int launch_geometry_hist(const FrameDev& f, const float* means3D, const float* opacities, const float* shs,
-                         const float* colors_precomp, const float* scales, const float* rotations,
-                         const float* cov3D_precomp, float* splats, int32_t* radii, uint8_t* clamped, uint32_t* rects,
-                         uint32_t* depth_keys, uint32_t* block_sums, int nblocks, uint32_t* table, uint32_t* class_counts,
-                         uint32_t* len_hist, hipStream_t stream);
-hipError_t geometry_hist_set_max_lds(int bytes);      // dynamic-LDS ceiling of every geometry_hist_kernel instantiation
+int launch_geometry_hist_binned(const FrameDev& f, int64_t R, const GeoInputs& in, const GeoOutputs& out, void* bin_scratch,
+                                hipStream_t stream);
+int launch_geometry_hist(const FrameDev& f, const GeoInputs& in, const GeoOutputs& out, int nblocks, uint32_t* table,
+                         uint32_t* class_counts, uint32_t* len_hist, hipStream_t stream);
+hipError_t geometry_hist_set_max_lds(int bytes);      // dynamic-LDS ceiling of every geometry_hist(_model)_kernel instantiation
 bool tile_binning_defers_sort(int64_t R, int n_tiles);      // what launch_tile_binning answers to *defer_sort = true
 // bin_scratch, R: the binning stage's scratch and the capacity it was laid out for (the fallback sort's spill copies and the
 // count of long lists live there); long_presorted: the rare-size kernel ran in front of this launch.

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "scg_common.h"
+#include "probe_timeline.h"
 
 namespace scg {
 
@@ -29,9 +30,7 @@ struct TileSortLds {
     uint32_t scan[NW];
     uint32_t red[2 * NW];
     uint32_t key[MAX_N];
-#ifdef SCG_PROBE_TIMELINE
-    uint32_t probe[8];
-#endif
+    SCG_PROBE(uint32_t probe[8];)                  // the sort's clocks (SCG_TP) — not a byte of LDS in the product build
 };
 
 // One LSD pass over the workgroup's NW*64*ITEMS keys (NW waves; the first 256 threads own the 256 digits).
@@ -115,11 +114,6 @@ __device__ __forceinline__ void lds_radix_pass(TileSortLds<NW, MAX_N, CNT>& L, u
 constexpr int kBucketMax = 24;
 
 // BPT buckets per thread: ITEMS (one bucket per possible entry) normally; fewer = denser buckets in a smaller counter array.
-#ifdef SCG_PROBE_TIMELINE
-#define SCG_TP(k) if (threadIdx.x == 0) L.probe[k] = (uint32_t)wall_clock64();
-#else
-#define SCG_TP(k)
-#endif
 // KEEP: the sorted ids also stay in L.id (the caller walks the list from LDS) and leave for `list` as coalesced stores nobody
 // waits for, instead of one scattered 4-byte store per entry that the workgroup's next barrier has to see completed.
 template <int NW, int MAX_N, int CNT, int ITEMS, int BPT, bool KEEP = false>

@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from scgaussian_amd import _lib, rasterizer as R, synthetic as syn          # noqa: E402
 import bench                                                                   # noqa: E402
+import _timeline_log as TL                                                     # noqa: E402
 
 name = sys.argv[1] if len(sys.argv) > 1 else "S2"
 _lib._lib = _lib.open_library(_lib.LIB_PATH.replace(".so", "_tl.so"))
@@ -29,8 +30,8 @@ means, shs, opac, scales, rots = params
 sett = bench.settings_for(syn.default_camera(W, H), 3, torch.zeros(3, device=dev), dev)
 rast = R.GaussianRasterizer(sett)
 ups = tuple(t.to(dev) for t in syn.make_upstream_grads(W, H, seed=10))
-OFF = 65792 + 32768 + (n_tiles + 8) * 40
-LOG = 65792 + 32768 + (n_tiles + 8) * 40 + (n_tiles + 8) * 16 + 64   # every probe of the tl build logs: all regions must exist
+OFF = TL.backward_at(n_tiles)
+LOG = TL.log_words(n_tiles)                      # every probe of the tl build logs: all regions must exist
 orig = R._hints_for
 
 
@@ -51,8 +52,8 @@ for _ in range(6):
 torch.cuda.synchronize()
 h = next(iter(R._CAM_HINTS.values()))
 log = h.cost[h.cur].cpu().numpy().astype(np.uint32)[n_tiles + OFF:]
-rec = log[: (log.size // 4) * 4].reshape(-1, 4)
-rec = rec[(rec[:, 3] >> 20) == 0xBAC]
+rec = log[: (log.size // TL.BACKWARD_RECORD) * TL.BACKWARD_RECORD].reshape(-1, TL.BACKWARD_RECORD)
+rec = rec[(rec[:, 3] >> 20) == TL.SIG_BACKWARD >> 20]
 t0, t1 = rec[:, 0].astype(np.int64), rec[:, 1].astype(np.int64)
 start = np.percentile(t0, 0.5)          # (a quadrant that returned at once this time keeps an older record)
 us = lambda x: x / 100.0                                                      # noqa: E731

@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from scgaussian_amd import _lib, rasterizer as R, synthetic as syn          # noqa: E402
 import bench                                                                   # noqa: E402
+import _timeline_log as TL                                                     # noqa: E402
 
 name = sys.argv[1] if len(sys.argv) > 1 else "S3"
 _lib._lib = _lib.open_library(_lib.LIB_PATH.replace(".so", "_tl.so"))
@@ -21,8 +22,8 @@ n_tiles = ((W + 15) // 16) * ((H + 15) // 16)
 sc = syn.make_scene(P, W, H, seed=0).to(dev)
 params = [sc.means3D, sc.shs, sc.opacities, sc.scales, sc.rotations]
 sett = bench.settings_for(syn.default_camera(W, H), 3, torch.zeros(3, device=dev), dev)
-OFF = 65792 + 32768
-LOG = 65792 + 32768 + (n_tiles + 8) * 40 + (n_tiles + 8) * 16 + 64   # every probe of the tl build logs: all regions must exist
+OFF = TL.BLEND_AT
+LOG = TL.log_words(n_tiles)                      # every probe of the tl build logs: all regions must exist
 orig = R._hints_for
 
 
@@ -40,8 +41,8 @@ with torch.no_grad():
     torch.cuda.synchronize()
 h = next(iter(R._CAM_HINTS.values()))
 log = h.cost[h.cur].cpu().numpy().astype(np.uint32)[n_tiles + OFF:]
-rec = log[: (log.size // 8) * 8].reshape(-1, 8)
-rec = rec[rec[:, 7] == 0xB1E9D000]
+rec = log[: (log.size // TL.BLEND_RECORD) * TL.BLEND_RECORD].reshape(-1, TL.BLEND_RECORD)
+rec = rec[rec[:, 7] == TL.SIG_BLEND]
 t0, t1, t2, t3 = (rec[:, i].astype(np.int64) for i in range(4))
 start = t0.min()
 us = lambda x: x / 100.0                                                      # noqa: E731
@@ -75,8 +76,8 @@ for label, order in (("as launched", np.argsort(st, kind="stable")), ("longest f
         end = max(end, t)
         heapq.heappush(heap, t)
     print(f"  greedy replay on 2 048 workgroup slots, {label}: makespan {end:.1f} us")
-srt = log[: (log.size // 8) * 8].reshape(-1, 8)
-srt = srt[srt[:, 7] == 0x50B70000]
+srt = log[: (log.size // TL.BLEND_RECORD) * TL.BLEND_RECORD].reshape(-1, TL.BLEND_RECORD)
+srt = srt[srt[:, 7] == TL.SIG_SORT]
 if len(srt):
     c = [srt[:, k].astype(np.int64) for k in range(7)]
     e0 = c[6]

@@ -13,6 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from scgaussian_amd import _lib, rasterizer as R, synthetic as syn          # noqa: E402
 import bench                                                                   # noqa: E402
+import _timeline_log as TL                                                     # noqa: E402
 
 name = sys.argv[1] if len(sys.argv) > 1 else "S3"
 _lib._lib = _lib.open_library(_lib.LIB_PATH.replace(".so", "_tl.so"))
@@ -23,7 +24,7 @@ sc = syn.make_scene(P, W, H, seed=0).to(dev)
 params = [sc.means3D, sc.shs, sc.opacities, sc.scales, sc.rotations]
 sett = bench.settings_for(syn.default_camera(W, H), 3, torch.zeros(3, device=dev), dev)
 n_tiles = ((W + 15) // 16) * ((H + 15) // 16)
-LOG = 65792 + 32768 + (n_tiles + 8) * 40 + (n_tiles + 8) * 16 + 64   # every probe of the tl build logs: all regions must exist
+LOG = TL.log_words(n_tiles)                      # every probe of the tl build logs: all regions must exist
 orig = R._hints_for
 
 
@@ -46,9 +47,9 @@ with torch.no_grad():
         c[n_tiles:].zero_()
     bench.render_once(sett, params)
     torch.cuda.synchronize()
-log = h.cost[h.cur].cpu().numpy().astype(np.uint32)[n_tiles + 65792:]
-rec = log[: (log.size // 8) * 8].reshape(-1, 8)
-rec = rec[(rec[:, 7] >> 8) == 0xC0FFEE]
+log = h.cost[h.cur].cpu().numpy().astype(np.uint32)[n_tiles + TL.GEOMETRY_AT:]
+rec = log[: (log.size // TL.GEOMETRY_RECORD) * TL.GEOMETRY_RECORD].reshape(-1, TL.GEOMETRY_RECORD)
+rec = rec[(rec[:, 7] >> 8) == TL.SIG_GEOMETRY >> 8]
 it = (rec[:, 7] & 0xFF).astype(np.int64)
 t0 = rec[:, 0].astype(np.int64)
 start = t0.min()

@@ -14,6 +14,7 @@ sys.path.insert(0, ROOT)
 from scgaussian_amd import _lib, rasterizer as R, synthetic as syn          # noqa: E402
 sys.path.insert(0, ROOT)
 import bench                                                                   # noqa: E402
+import _timeline_log as TL                                                     # noqa: E402
 
 name = sys.argv[1] if len(sys.argv) > 1 else "S3"
 _lib._lib = _lib.open_library(_lib.LIB_PATH.replace(".so", "_tl.so"))
@@ -24,7 +25,7 @@ sc = syn.make_scene(P, W, H, seed=0).to(dev)
 params = [sc.means3D, sc.shs, sc.opacities, sc.scales, sc.rotations]
 sett = bench.settings_for(syn.default_camera(W, H), 3, torch.zeros(3, device=dev), dev)
 n_tiles = ((W + 15) // 16) * ((H + 15) // 16)
-LOG = 65792 + 32768 + (n_tiles + 8) * 40 + (n_tiles + 8) * 16 + 64   # every probe of the tl build logs: all regions must exist
+LOG = TL.log_words(n_tiles)                      # every probe of the tl build logs: all regions must exist
 orig = R._hints_for
 
 
@@ -43,9 +44,9 @@ with torch.no_grad():
     torch.cuda.synchronize()
 h = next(iter(R._CAM_HINTS.values()))
 n_tiles = ((W + 15) // 16) * ((H + 15) // 16)
-log = h.cost[h.cur].cpu().numpy().astype(np.uint32)[n_tiles: n_tiles + 65792]
-rec = log[: (log.size // 8) * 8].reshape(-1, 8)
-rec = rec[rec[:, 7] == 0xC0FFEE]
+log = h.cost[h.cur].cpu().numpy().astype(np.uint32)[n_tiles + TL.SCATTER_AT: n_tiles + TL.GEOMETRY_AT]
+rec = log[: (log.size // TL.SCATTER_RECORD) * TL.SCATTER_RECORD].reshape(-1, TL.SCATTER_RECORD)
+rec = rec[rec[:, 7] == TL.SIG_SCATTER]
 t0, t1, t2 = rec[:, 0].astype(np.int64), rec[:, 1].astype(np.int64), rec[:, 2].astype(np.int64)
 start = t0.min()
 us = lambda x: x / 100.0                                                      # noqa: E731  (100 MHz ticks -> us)
