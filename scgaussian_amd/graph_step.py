@@ -16,6 +16,8 @@ What a replay cannot do, and how it is handled:
     capacity means an EARLIER replay's lists were clipped (its images and gradients were incomplete) — `overflows` is incremented
     and the step is captured again with room for the count, so the replay that follows is complete: recovery one step late.
   * launch-order hints (tile costs, long-list counts) are frozen with the graph; they never enter a result.
+  * what the closure read on the host is frozen by construction: the camera, the active SH degree, the background colour's
+    address, the number of Gaussians P.  A change of any of them needs a new CapturedStep.
   * the closure must be capturable in everything else it does: no `.item()`, no allocation of pinned memory, no new cameras
     (a camera's first render reads its view matrix once: the warm-up runs take care of that).
 """

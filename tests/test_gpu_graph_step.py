@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import parity_utils as pu
+from captured_refs import grad_noise_ok as _grad_noise_ok
 from scgaussian_amd import graph_step as gs
 from scgaussian_amd import rasterizer as R
 from scgaussian_amd import render as rmod
@@ -37,13 +38,6 @@ def _eager(rast, leaves, ups):
     out = _step(rast, leaves, ups)
     torch.cuda.synchronize()
     return [t.detach().clone() for t in out], [p.grad.detach().clone() for p in leaves]
-
-
-def _grad_noise_ok(got, want, noise):
-    for g, w, n in zip(got, want, noise):
-        scale = float(w.abs().max()) + 1e-30
-        tol = max(4.0 * float((n - w).abs().max()), 2e-5 * scale)
-        assert float((g - w).abs().max()) <= tol, (float((g - w).abs().max()), tol, scale)
 
 
 def test_no_host_read_forward_is_the_default_forward_bit_for_bit():
