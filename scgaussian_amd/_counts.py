@@ -6,10 +6,12 @@ real count either at once (the default: the host waits for the geometry stage's 
 time the camera is rendered.  This module owns the per-device _SpecState and every access to its two capacity tables (lookup,
 lookup_shape, commit, commit_shape, forget: nothing outside this file touches `hint` / `cam_hint`), what a forward takes from the
 state (_PinnedSums, _Plan), and the pinned count words with what a count that has arrived does to the camera's capacity
-(_settle_word -> commit).  rasterizer.py decides in which mode a forward runs, launches it and repeats one that overflowed.
+(_settle_word -> commit; file_word, release, settle_replayed, capture_record: how the words are pooled is known here only).
+rasterizer.py decides in which mode a forward runs, launches it and repeats one that overflowed.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import threading
 
@@ -196,6 +198,7 @@ _COUNT_FREE = []
 _COUNT_SLOTS = 4096
 _OVERFLOW = {"renders": 0, "overflows": 0, "settled": 0}
 _ANON_CAPTURED = []                      # count words of forwards captured by somebody else's graph (kept: the graph writes them)
+_CAPTURE_RECORD = None                   # graph_step's record of the forwards captured right now (None: no capture of ours)
 _QUARANTINE = []                         # pinned blocks of forwards that failed after their launch (never handed out again)
 
 
@@ -236,6 +239,43 @@ def _count_word(cap, P, key, device_index) -> _CountWord:
     return w
 
 
+@contextlib.contextmanager
+def capture_record():
+    """`with capture_record() as words:` — the count words of the forwards captured inside are filed into `words`."""
+    global _CAPTURE_RECORD
+    prev, _CAPTURE_RECORD = _CAPTURE_RECORD, []
+    try:
+        yield _CAPTURE_RECORD
+    finally:
+        _CAPTURE_RECORD = prev
+
+
+def file_word(spec, cw: _CountWord, ckey, capturing: bool):
+    """Who looks at a launched forward's word later: the capture's owner (nobody's: settle_counts) or the camera's next render."""
+    _OVERFLOW["renders"] += 1
+    if capturing:
+        cw.captured = True
+        (_CAPTURE_RECORD if _CAPTURE_RECORD is not None else _ANON_CAPTURED).append(cw)
+    else:
+        spec.pending.setdefault(ckey, []).append(cw)
+
+
+def release(words):
+    """Give the words' slots back (nothing writes them any more: a graph that is gone, a forward the library rejected)."""
+    _COUNT_FREE.extend(w.slot for w in words)
+
+
+def settle_replayed(w: _CountWord):
+    """A word that a graph's replays write: None while no count has arrived, else the latest count, settled; the word is re-armed."""
+    R = w.value()
+    if R is not None:
+        w.np[0] = _COUNT_ARMED
+        spec = _SPEC_STATE.get(w.device_index if w.device_index is not None else torch.cuda.current_device())
+        if spec is not None:
+            _settle_word(spec, w, R)
+    return R
+
+
 def _settle_word(spec, w: _CountWord, R: int):
     """The count of a render that was launched without a host read has arrived: the camera's capacity follows it."""
     _OVERFLOW["settled"] += 1
@@ -273,12 +313,7 @@ def settle_counts(device=None) -> dict:
         for key in list(spec.pending):
             _settle_camera(spec, key)
     for w in _ANON_CAPTURED:                                 # words a foreign graph's replays write: the latest count, once each
-        R = w.value()
-        if R is not None:
-            w.np[0] = _COUNT_ARMED
-            spec = _SPEC_STATE.get(w.device_index)
-            if spec is not None:
-                _settle_word(spec, w, R)
+        settle_replayed(w)
     return overflow_stats()
 
 

@@ -27,7 +27,7 @@ from typing import Callable, Optional
 
 import torch
 
-from . import rasterizer as R
+from . import _counts
 
 
 class CapturedStep:
@@ -70,19 +70,14 @@ class CapturedStep:
                 self.fn()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        R.settle_counts()
-        R._count_pool()
+        _counts.settle_counts()
+        _counts._count_pool()
         self._clear_grads()
         # the words of the graph that is being replaced stay reserved until the old graph is gone (it may still be running)
         old_words, old_graph = self.words, self.graph
-        record = []
         graph = torch.cuda.CUDAGraph()
-        prev, R._CAPTURE_RECORD = R._CAPTURE_RECORD, record
-        try:
-            with torch.cuda.graph(graph, stream=side):
-                outputs = self.fn()
-        finally:
-            R._CAPTURE_RECORD = prev
+        with _counts.capture_record() as record, torch.cuda.graph(graph, stream=side):
+            outputs = self.fn()
         self.graph, self.outputs, self.words = graph, outputs, record
         # the gradients this graph writes: allocated inside ITS capture.  Several captured steps over the same parameters (one per
         # training view) each have their own; replay() points .grad at this step's before it returns
@@ -92,25 +87,14 @@ class CapturedStep:
         if old_graph is not None:
             torch.cuda.synchronize()
             del old_graph
-            for w in old_words:
-                R._COUNT_FREE.append(w.slot)
+            _counts.release(old_words)
 
     # ---- replay ---------------------------------------------------------------------------------------------------------------
     def check(self) -> bool:
         """Look (without waiting) at the counts the latest completed replay left: True when one of them exceeded its capacity.
         Raises the cameras' capacities so that the next capture has room."""
-        clipped = False
-        for w in self.words:
-            Rn = w.value()
-            if Rn is None:
-                continue
-            w.np[0] = R._COUNT_ARMED
-            spec = R._SPEC_STATE.get(w.device_index if w.device_index is not None else torch.cuda.current_device())
-            if spec is not None:
-                R._settle_word(spec, w, Rn)
-            if Rn > w.cap:
-                clipped = True
-        return clipped
+        counts = [(_counts.settle_replayed(w), w.cap) for w in self.words]               # (every word is looked at and re-armed)
+        return any(Rn is not None and Rn > cap for Rn, cap in counts)
 
     def replay(self):
         if self.check():
@@ -131,8 +115,7 @@ class CapturedStep:
         if self.graph is not None:
             torch.cuda.synchronize()
             self.graph = None
-            for w in self.words:
-                R._COUNT_FREE.append(w.slot)
+            _counts.release(self.words)
             self.words = []
 
     def __del__(self):

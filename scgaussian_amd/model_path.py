@@ -187,36 +187,23 @@ def _grad_arena(model: _ModelArgs, into):
     return out
 
 
-def backward_fused_model(model: _ModelArgs, radii, state, dL_dcolor, dL_ddepth, dL_dalpha, timer=None, into=None,
-                         d_means2D_out=None):
-    """Stages 4-5 of the model path in one library call (scg_backward_model, rasterizer._backward_view).  Returns {argument name:
-    gradient} (views of one arena) + "means2D"; `into` as in rasterizer.backward_fused (the kernel adds to an earlier view's
-    gradients)."""
-    return R._backward_view(state, model, radii, dL_dcolor, dL_ddepth, dL_dalpha, timer, into, d_means2D_out)
+def _node_grads(g, d_means2D):
+    """A node's gradients in forward argument order (means2D, ARG_NAMES, settings, model); all None when no view reached the loss."""
+    if g is None:
+        return (None,) * (len(ARG_NAMES) + 3)
+    return (d_means2D,) + tuple(g.get(n) for n in ARG_NAMES) + (None, None)
 
 
 class _RasterizeModel(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means2D, *args):
         *tensors, raster_settings, model = args
-        if model is None:
-            model = _ModelArgs(dict(zip(ARG_NAMES, tensors)))
-        needs_grad = any(ctx.needs_input_grad)
-        color, radii, depth, alpha, _, state = R._forward_view(raster_settings, model, needs_grad)
-        ctx.model = model
-        ctx.fused_state = state
-        ctx.raster_settings = raster_settings
-        if needs_grad:
-            ctx.save_for_backward(*model.tensors, radii)         # in-place updates between forward and backward trip the version check
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return color, radii, depth, alpha
+        ctx.model = model if model is not None else _ModelArgs(dict(zip(ARG_NAMES, tensors)))
+        return R._views_forward(ctx, (raster_settings,), ctx.model, any(ctx.needs_input_grad))[0]
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha):
-        saved = ctx.saved_tensors                                # raises if a parameter was modified in place since forward
-        g = R._backward_view(ctx.fused_state, ctx.model, saved[-1], grad_color, grad_depth, grad_alpha)
-        return (g["means2D"],) + tuple(g.get(n) for n in ARG_NAMES) + (None, None)
+    def backward(ctx, *grads):
+        return _node_grads(*R._views_backward(ctx.states, ctx.model, ctx.saved_tensors[-1:], grads, False))
 
 
 def rasterize_model(raster_settings, means2D: torch.Tensor, _args: Optional[_ModelArgs] = None, **tensors):
@@ -239,38 +226,12 @@ class _RasterizeModelViews(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means2D, *args):
         *tensors, settings_list, model = args
-        if model is None:
-            model = _ModelArgs(dict(zip(ARG_NAMES, tensors)))
-        needs_grad = any(ctx.needs_input_grad)
-        outs, states = [], []
-        for st_ in settings_list:
-            color, radii, depth, alpha, _, state = R._forward_view(st_, model, needs_grad)
-            states.append(state)
-            outs += [color, radii, depth, alpha]
-        ctx.model, ctx.states, ctx.K = model, states, len(settings_list)
-        if needs_grad:
-            ctx.save_for_backward(*model.tensors, *outs[1::4])
-        ctx.mark_non_differentiable(*outs[1::4])
-        ctx.set_materialize_grads(False)
-        return tuple(outs)
+        ctx.model = model if model is not None else _ModelArgs(dict(zip(ARG_NAMES, tensors)))
+        return R._views_forward(ctx, settings_list, ctx.model, any(ctx.needs_input_grad))[0]
 
     @staticmethod
     def backward(ctx, *grads):
-        K, model = ctx.K, ctx.model
-        saved = ctx.saved_tensors
-        radii_all = saved[len(saved) - K:]
-        d_means2D = torch.empty((K, model.P, 3), dtype=torch.float32, device=model.device)
-        acc = None
-        for k in range(K):
-            g_color, _, g_depth, g_alpha = grads[4 * k: 4 * k + 4]
-            if g_color is None and g_depth is None and g_alpha is None:
-                d_means2D[k].zero_()
-                continue                                         # this view's outputs did not reach the loss
-            acc = R._backward_view(ctx.states[k], model, radii_all[k], g_color, g_depth, g_alpha, into=acc,
-                                   d_means2D_out=d_means2D[k])
-        if acc is None:
-            return (None,) * (len(ARG_NAMES) + 3)
-        return (d_means2D,) + tuple(acc.get(n) for n in ARG_NAMES) + (None, None)
+        return _node_grads(*R._views_backward(ctx.states, ctx.model, ctx.saved_tensors[-len(ctx.states):], grads, True))
 
 
 def rasterize_model_views(settings_list, means2D: torch.Tensor, _args: Optional[_ModelArgs] = None, **tensors):

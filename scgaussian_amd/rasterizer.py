@@ -12,10 +12,10 @@ gaussian_renderer/__init__.py:15 and uses at :38-53 and :100-108:
 PyTorch is plumbing here (device memory, the current stream, autograd graph edges); every stage of the
 computation runs in hand-written HIP kernels behind include/scg_raster.h.  There is no fallback path.
 
-What lives where: this module owns the operator, the frames with their per-camera launch hints, and the forwards and the backward
-as sequences of library calls (forward_fused: mode, capacity look-up, _launch_forward per attempt, overflow retry).  The capacity
-policy with its tables, pinned partial sums, workspace plans and count words: _counts.py; the gradient arena: _grads.py; camera
-identity: _cameras.py; the option and flag bits handed to the library: _lib.py's constants, named as in the headers.
+What lives where: this module owns the operator — the forwards and the backward as sequences of library calls (forward_fused: mode,
+capacity look-up, _launch_forward per attempt, overflow retry), the module switches, the K-view core of the four autograd nodes.
+The capacity policy with its tables, pinned partial sums, workspace plans and count words: _counts.py; frames and per-camera launch
+hints: _frames.py; the gradient arena: _grads.py; camera identity: _cameras.py; the stage timer: _timing.py; option and flag bits: _lib.py.
 
 Concurrency: the operator is re-entrant per device and stream, like the upstream extension — every forward takes its own
 pinned scratch (the partial sums of num_rendered) from a per-device pool, so two threads, each on its own stream, may be
@@ -35,10 +35,19 @@ from typing import Callable, NamedTuple, Optional
 import torch
 import torch.nn as nn
 
-from . import _counts, _lib
+from . import _counts, _grads, _lib, _timing
+# (names this module does not use itself are what bench.py, tests and tools read here)
+from ._cameras import _CAM_KEYS, _camera_key, tag_camera                                               # noqa: F401
+from ._counts import (_OVERFLOW, _QUARANTINE, _SPEC_STATE, _CountWord, _capacity_for, _count_word, _next_capacity,      # noqa: F401
+                      _settle_camera, _settle_word, _spec_state, overflow_stats, settle_counts)
+from ._frames import _CAM_HINTS, _FRAME_CACHE, _f32c, _frame_for, _stream                              # noqa: F401
+# _sh_tail_promise is the DECISION about the promise a kept gradient arena carries about its SH tails: the backward of both paths
+# looks it up here at call time (tests spy on it)
+from ._grads import _grad_outputs, grad_arena, sh_tail_flag as _sh_tail_promise                        # noqa: F401
 from ._lib import (BACKWARD_ACCUMULATE, BINNING_AUTO, DEBUG_SEPARATE_HIST, DEBUG_SEPARATE_SORT, DSPLAT_FLOATS,
                    FORWARD_ARM_PARTIAL_SUMS, FORWARD_NO_BACKWARD_STATE, FORWARD_RARE_8WAVE, FORWARD_SKIP_RARE_SORT,
-                   FORWARD_SPLIT_LONG_LISTS, SPLAT_FLOATS, TILE, ScgFrame, check, ptr)
+                   FORWARD_SPLIT_LONG_LISTS, SPLAT_FLOATS, TILE, check, ptr)                           # noqa: F401
+from ._timing import StageTimer, set_stage_timer                                                       # noqa: F401
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -56,161 +65,11 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
-def _f32c(t: Optional[torch.Tensor], device) -> Optional[torch.Tensor]:
-    if t is None or t.numel() == 0:
-        return None
-    if t.dtype == torch.float32 and t.device == device and t.is_contiguous():     # the usual case: nothing to do
-        return t
-    if t.device != device:
-        if not t.is_cuda and device.type == "cuda" and t.numel() <= 64:
-            # a camera's matrices / background handed over in host memory (a caller that builds a camera per frame): through a
-            # pinned block and an asynchronous copy — a pageable-memory upload would wait for everything queued on the stream
-            return t.detach().to(torch.float32).contiguous().pin_memory().to(device, non_blocking=True)
-        t = t.to(device)
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
-
-
 def _kernel_inputs(dev, *tensors):
     """The operator's seven inputs (means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp) as the kernels read
     them (_f32c; None for an absent or empty one) + M, the SH coefficients per Gaussian."""
     inputs = tuple([_f32c(t, dev) for t in tensors])
     return inputs, (inputs[2].shape[1] if inputs[2] is not None else 0)
-
-
-class _Frame:
-    """ScgFrame plus the tensors whose storage it points at (kept alive for the call)."""
-
-    def __init__(self, settings: GaussianRasterizationSettings, P: int, M: int, device):
-        self.keep = [_f32c(settings.viewmatrix, device), _f32c(settings.projmatrix, device),
-                     _f32c(settings.campos, device), _f32c(settings.bg, device)]
-        if any(k is None for k in self.keep[:3]):
-            raise ValueError("viewmatrix / projmatrix / campos must be non-empty tensors")
-        self.vm_src = settings.viewmatrix        # the caller's tensor: what names the camera (host content / tag_camera / content)
-        self.c = ScgFrame(P=int(P), sh_degree=int(settings.sh_degree), sh_coeffs=int(M),
-                          width=int(settings.image_width), height=int(settings.image_height),
-                          tanfovx=float(settings.tanfovx), tanfovy=float(settings.tanfovy),
-                          scale_modifier=float(settings.scale_modifier),
-                          prefiltered=int(bool(settings.prefiltered)), debug=int(bool(settings.debug)),
-                          viewmatrix=ptr(self.keep[0]), projmatrix=ptr(self.keep[1]), campos=ptr(self.keep[2]),
-                          bg=ptr(self.keep[3]))
-        self.H, self.W = int(settings.image_height), int(settings.image_width)
-        self.n_tiles = ((self.W + TILE - 1) // TILE) * ((self.H + TILE - 1) // TILE)
-        # what the previous render of this CAMERA left for the next one (launch-order hint, long-list counts): shared by every
-        # frame of the camera — a frame is (camera, background, ...): a training loop with random backgrounds
-        # (reference train.py:141) builds a new frame per iteration, its hints must not start from nothing each time
-        self.hints = None
-        self.cam_key = None              # identity of the camera (content of its view matrix, _camera_key): set at the first forward
-        self.ref = C.byref(self.c)
-
-    @property
-    def long_np(self):
-        """The camera's two ScgFrame.long_lists_out words as a numpy view (None before the first forward / when switched off)."""
-        return None if self.hints is None else self.hints.long_np
-
-    def next_forward(self, device):
-        """Called once per forward: what the previous render of this camera recorded becomes the hint, the other buffer
-        receives this render's costs.  A hint never changes a result, only which kernels are launched and in which order
-        tiles start."""
-        # (two dictionary look-ups: the matrix itself is read once per tensor; the camera's record moves to the recently-used
-        # end of its table, and one that was evicted meanwhile — its pinned words belong to another camera now — is replaced)
-        self.cam_key = cam = _camera_key(self.vm_src)
-        h = self.hints = _hints_for(cam, self.W, self.H, device, self.n_tiles)
-        if h.cost is not None:
-            cur = _stream(device)
-            if cur not in h.streams:
-                h.streams.add(cur)
-                ts = torch.cuda.current_stream(device)
-                for t in (*h.cost, *h.bcost):
-                    t.record_stream(ts)
-        self.c.long_lists_out = h.long_ptr
-        if h.cost is not None:
-            self.c.tile_cost_in = h.cost[h.cur].data_ptr() if h.cost_valid else None
-            h.cur ^= 1
-            self.c.tile_cost_out = h.cost[h.cur].data_ptr()
-            h.cost_valid = True
-            # the blend backward's own order (ScgFrame.bwd_cost_in / _out, per quadrant): the buffer the camera's latest
-            # BACKWARD wrote becomes the hint; it is swapped only when a backward ran since (renders in between keep it)
-            if h.bwritten:
-                h.bcur ^= 1
-                h.bwritten, h.bvalid = False, True
-            self.c.bwd_cost_in = h.bcost[h.bcur ^ 1].data_ptr() if (h.bvalid and BWD_ORDER_HINT) else None
-            self.c.bwd_cost_out = h.bcost[h.bcur].data_ptr()
-        else:                            # (a cached frame whose camera's record was made with TILE_COST_HINT off)
-            self.c.tile_cost_in = self.c.tile_cost_out = self.c.bwd_cost_in = self.c.bwd_cost_out = None
-
-
-class _CamHints:
-    """Per (camera, image size, device): two buffers of per-tile costs swapped at every forward (ScgFrame.tile_cost_in /
-    _out) and the two pinned words of ScgFrame.long_lists_out (ABI 8: the number of tiles whose list is longer than the
-    forward blend sorts itself / longer than 16 384 entries; -1: no render has completed yet).  Not per Gaussian count: the
-    buffers are per TILE, and a record that died at every densification would leave the camera without history each time."""
-    __slots__ = ("cost", "cur", "cost_valid", "long_np", "long_ptr", "slot", "bcost", "bcur", "bwritten", "bvalid", "streams")
-
-
-from ._cameras import _CAM_KEYS, _CAM_KEYS_MAX, _camera_key, tag_camera          # noqa: E402,F401 - camera identity (split out in round 6)
-
-
-_CAM_HINTS = {}                                  # (camera content, W, H, device) -> _CamHints, least recently used first
-_CAM_HINTS_MAX = 1024
-
-
-def _hints_for(cam_key, W, H, device, n_tiles):
-    key = (cam_key, W, H, device.index)
-    h = _CAM_HINTS.pop(key, None)
-    if h is None:
-        if len(_CAM_HINTS) >= _CAM_HINTS_MAX:                    # the least recently used quarter goes; their pinned words are
-            for k in list(_CAM_HINTS)[: _CAM_HINTS_MAX // 4]:    # handed out again (a render of theirs finished long ago: the
-                _release_long_words(_CAM_HINTS.pop(k))           # records in use sit at the other end of the table)
-        h = _CamHints()
-        h.cost = [torch.zeros(n_tiles, dtype=torch.int32, device=device) for _ in range(2)] if TILE_COST_HINT else None
-        h.cur, h.cost_valid = 0, False
-        # ... and two of per-QUADRANT times of the blend backward's waves (4 words per tile)
-        h.bcost = [torch.zeros(4 * n_tiles, dtype=torch.int32, device=device) for _ in range(2)] if TILE_COST_HINT else None
-        h.bcur, h.bwritten, h.bvalid = 0, False, False
-        # raw streams these buffers have been used on: the one they were allocated on + every other one, each told to the caching
-        # allocator once (Tensor.record_stream), so that an evicted record's memory is not handed out while a kernel of another
-        # stream still writes it (ADVICE r5: the operator is re-entrant per stream since round 5)
-        h.streams = {_stream(device)}
-        h.long_np = h.long_ptr = h.slot = None
-        if SKIP_IDLE_RARE_SORT or RARE_8WAVE:
-            h.slot, h.long_np, h.long_ptr = _long_words()
-    _CAM_HINTS[key] = h                                          # (re-inserted: most recently used last)
-    return h
-
-
-_FRAME_CACHE = {}
-# ScgFrame.long_lists_out words come from ONE pinned allocation per process (a pinned allocation per camera would cost a render
-# loop over hundreds of distinct cameras ~50 us each): one slot of two words per live hint record (_CAM_HINTS), returned to
-# the free list when the record is evicted.  The words are a HINT (which sort kernels to launch) — a wrong one costs time,
-# never a result (the forward blend sorts a list nobody sorted for it,
-# tests/test_gpu_parity.py::test_skipped_rare_sort_launch_...).
-_LONG_POOL = None
-_LONG_FREE = []
-
-
-def _long_words():
-    """(slot index, numpy view of the slot's two words, device-visible address of the slot)."""
-    global _LONG_POOL
-    if _LONG_POOL is None:
-        t = torch.full((2 * (_CAM_HINTS_MAX + 1),), -1, dtype=torch.int32).pin_memory()
-        _LONG_POOL = (t, t.numpy(), t.data_ptr())
-        _LONG_FREE.extend(range(_CAM_HINTS_MAX, -1, -1))
-    _t, arr, base = _LONG_POOL
-    if not _LONG_FREE:                   # records that left the table without passing _release_long_words (a cleared table)
-        used = {h.slot for h in _CAM_HINTS.values()}
-        _LONG_FREE.extend(i for i in range(_CAM_HINTS_MAX, -1, -1) if i not in used)
-    i = _LONG_FREE.pop()
-    view = arr[2 * i: 2 * i + 2]
-    view[:] = -1                         # "no render of this camera has completed yet"
-    return i, view, base + 8 * i
-
-
-def _release_long_words(h):
-    if h.slot is not None:
-        _LONG_FREE.append(h.slot)
-        h.slot = h.long_np = h.long_ptr = None
 
 
 # ---- module switches (round 5: no environment variables in the product — tests and the same-process A/B tool
@@ -231,6 +90,11 @@ SPLIT_LONG_LISTS = True
 RARE_8WAVE = True
 
 
+def _frame_switches():
+    """What _frames needs of the switches, read per forward: cost buffers exist, bwd_cost_in is handed over, long words wanted."""
+    return TILE_COST_HINT, BWD_ORDER_HINT, SKIP_IDLE_RARE_SORT or RARE_8WAVE
+
+
 def _rare_options(words) -> int:
     """scg_forward option bits from what the camera's previous render left in ScgFrame.long_lists_out."""
     if words is None or words[0] < 0:
@@ -242,34 +106,6 @@ def _rare_options(words) -> int:
     if RARE_8WAVE and SPLIT_LONG_LISTS and words[1] > 0:
         return FORWARD_RARE_8WAVE | FORWARD_SPLIT_LONG_LISTS
     return 0
-
-
-def _frame_for(settings: GaussianRasterizationSettings, P: int, M: int, device, forward: bool = False) -> _Frame:
-    """ScgFrame structs are cached by what they contain (pointers + scalars): building the ctypes struct costs more
-    host time than some of the kernels it describes take.  Only frames whose four small tensors are used as they
-    are (fp32, contiguous, on the device) are cached — the cached frame keeps them alive, so their addresses cannot be
-    recycled, and their CONTENT is read by the kernels at launch time, not here."""
-    small = (settings.viewmatrix, settings.projmatrix, settings.campos, settings.bg)
-    for t in small:
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == device and t.is_contiguous()
-                and t.numel() > 0):
-            return _Frame(settings, P, M, device)
-    key = (small[0].data_ptr(), small[1].data_ptr(), small[2].data_ptr(), small[3].data_ptr(),
-           settings.image_height, settings.image_width, settings.tanfovx, settings.tanfovy,
-           settings.scale_modifier, settings.sh_degree, settings.prefiltered, settings.debug, P, M, device.index)
-    fr = _FRAME_CACHE.get(key)
-    if fr is None:
-        if len(_FRAME_CACHE) > 256:
-            _FRAME_CACHE.clear()
-        fr = _FRAME_CACHE[key] = _Frame(settings, P, M, device)
-    if forward:
-        fr.next_forward(device)
-    return fr
-
-
-def _stream(device) -> int:
-    """Raw hipStream_t of torch's current stream on `device` (the C call behind torch.cuda.current_stream)."""
-    return torch._C._cuda_getCurrentRawStream(device.index if device.index is not None else torch.cuda.current_device())
 
 
 class _on_device:
@@ -293,118 +129,6 @@ def _require_cuda(t: torch.Tensor):
     if not t.is_cuda:
         raise _lib.ScgError("scgaussian_amd rasterizer needs tensors on a ROCm GPU ('cuda' device); "
                             "there is no CPU path in the product (the CPU oracle lives under oracle/, tests only)")
-
-
-def _no_timer(name: str):
-    return contextlib.nullcontext()
-
-
-_ACTIVE_TIMER: Callable = _no_timer
-
-
-def set_stage_timer(timer: Optional[Callable]):
-    """Install a StageTimer used by every rasterizer call that does not pass its own (bench.py); None removes it."""
-    global _ACTIVE_TIMER
-    _ACTIVE_TIMER = timer if timer is not None else _no_timer
-
-
-class StageTimer:
-    """Optional per-stage timing with events recorded on the stream the kernels are launched on (torch's
-    current stream).  Usage: t = StageTimer(); forward_stages(..., timer=t); t.summary() after a sync.
-
-    The one-call entry points (scg_forward / scg_backward) record their stages' events themselves
-    (include/scg_raster.h ScgStageEvents): `stage_events()` hands them a struct of raw hipEvent_t pairs from this
-    timer's pool, so the per-stage times of the REAL fast path are measured, not those of a staged replay."""
-
-    FORWARD = ("geometry_forward", "binning", "blend_forward")
-    BACKWARD = ("blend_backward", "geometry_backward")
-
-    def __init__(self, only=None):
-        self.events = {}
-        self.raw = {}                                            # name -> [(begin handle, end handle)]
-        self.only = set(only) if only is not None else None      # restrict to these stages (less event traffic)
-        self._pool = []
-        self._raw_pool = {}                                      # device index -> [hipEvent_t]: an event belongs to a device
-        self._structs = []                                       # keeps the ctypes structs alive until summary()
-
-    def _event(self):
-        if not self._pool:                                       # created in batches, off the per-stage path
-            self._pool = [torch.cuda.Event(enable_timing=True) for _ in range(256)]
-        return self._pool.pop()
-
-    def _raw_event(self, dev):
-        pool = self._raw_pool.setdefault(dev, [])
-        if not pool:                                             # created on the CURRENT device: callers are inside
-            lib = _lib.load()                                    # `with _on_device(dev)`
-            for _ in range(256):
-                h = C.c_void_p()
-                check(lib.scg_event_create(C.byref(h), 1), "scg_event_create")
-                pool.append(h.value)
-        return pool.pop()
-
-    def stage_events(self, direction: str):
-        """ScgStageEvents (by reference) for one scg_forward ('forward') / scg_backward ('backward') call, or None."""
-        names = self.FORWARD if direction == "forward" else self.BACKWARD
-        wanted = [i for i, n in enumerate(names) if self.only is None or n in self.only]
-        if not wanted:
-            return None
-        ev = _lib.ScgStageEvents()
-        dev = torch._C._cuda_getDevice()
-        for i in wanted:
-            a, b = self._raw_event(dev), self._raw_event(dev)
-            ev.begin[i], ev.end[i] = a, b
-            self.raw.setdefault(names[i], []).append((a, b, dev))
-        self._structs.append(ev)
-        return C.byref(ev)
-
-    def __call__(self, name: str):
-        if self.only is not None and name not in self.only:
-            return contextlib.nullcontext()
-        return self._timed(name)
-
-    @contextlib.contextmanager
-    def _timed(self, name: str):
-        a, b = self._event(), self._event()
-        a.record()
-        try:
-            yield
-        finally:
-            b.record()
-            self.events.setdefault(name, []).append((a, b))
-
-    def summary(self):
-        """{stage: (mean ms, calls)}; synchronises."""
-        torch.cuda.synchronize()
-        out = {k: [a.elapsed_time(b) for a, b in v] for k, v in self.events.items()}
-        if self.raw:
-            lib = _lib.load()
-            ms = C.c_float()
-            for k, pairs in self.raw.items():
-                for a, b, _dev in pairs:
-                    check(lib.scg_event_elapsed_ms(a, b, C.byref(ms)), "scg_event_elapsed_ms")
-                    out.setdefault(k, []).append(ms.value)
-        return {k: (sum(v) / len(v), len(v)) for k, v in out.items()}
-
-    def reset(self):
-        for pairs in self.raw.values():                          # completed events go back to their device's pool
-            for a, b, dev in pairs:
-                self._raw_pool.setdefault(dev, []).extend((a, b))
-        self.events, self.raw, self._structs = {}, {}, []
-
-    def close(self):
-        """Destroy the raw hipEvents of this timer (pool and recorded pairs)."""
-        self.reset()
-        pools, self._raw_pool = self._raw_pool, {}
-        try:
-            lib = _lib.load()
-            for pool in pools.values():
-                for h in pool:
-                    lib.scg_event_destroy(h)
-        except Exception:                                        # interpreter shutdown: the driver reclaims them
-            pass
-
-    def __del__(self):
-        self.close()
 
 
 _ELEMENT_SIZE = {torch.float32: 4, torch.int32: 4, torch.uint8: 1, torch.int64: 8}
@@ -434,11 +158,6 @@ class _Arena:
         return self.buf[self.offsets[i]: self.offsets[i] + nbytes].view(dtype).view(shape)
 
 
-# the capacity policy with the per-device state it lives in, the pinned count words of renders launched without a host read and
-# what a settled count does to a camera's capacity, the counters: _counts.py
-from ._counts import (_ANON_CAPTURED, _COUNT_ARMED, _COUNT_FREE, _COUNT_SLOTS, _OVERFLOW, _QUARANTINE, _SPEC_STATE,      # noqa: E402,F401
-                      _CountWord, _capacity_for, _count_pool, _count_word, _next_capacity, _settle_camera, _settle_word,
-                      _spec_state, overflow_stats, settle_counts)
 # what the speculation cost so far (speculation_stats(); bench.py `moving_scene`): forwards on the one-call path, how many of them
 # had to be repeated because num_rendered exceeded the capacity, forwards that took the staged path (first sight of a shape, images
 # beyond the tile-first binning), and how many one-call forwards had a launch-order hint of their camera's previous render
@@ -480,13 +199,13 @@ def forward_stages(settings: GaussianRasterizationSettings, means3D, opacities, 
     _require_cuda(means3D)
     lib = _lib.load()
     _SPEC_STATS["staged_forwards"] += 1
-    timer = timer or _ACTIVE_TIMER
+    timer = timer or _timing.ACTIVE
     dev = means3D.device
     spec = _spec_state(dev)
     inputs, M = _kernel_inputs(dev, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp)
     means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp = inputs
     P = 0 if means3D is None else means3D.shape[0]
-    fr = _frame_for(settings, P, M, dev, forward=True)
+    fr = _frame_for(settings, P, M, dev, True, None, _frame_switches())
     H, W = fr.H, fr.W
     with _on_device(dev):
         stream = _stream(dev)
@@ -592,12 +311,6 @@ class _LazyViews(dict):
         return v
 
 
-# The gradient arena a backward writes into (segment layout, the pool that keeps arenas from step to step, the promise a kept
-# arena carries about its SH gradients): _grads.py.  _sh_tail_promise is the DECISION about that promise: the backward of both
-# paths looks it up here at call time (tests spy on it).
-from . import _grads                                                                                   # noqa: E402
-from ._grads import _GRAD_ORDER, _grad_outputs, _take_arena, grad_arena, sh_tail_flag as _sh_tail_promise      # noqa: E402,F401
-
 ARENA_POOL = True                        # module switch (tests / A-B runs): keep gradient arenas from step to step (_grads.py)
 
 
@@ -623,7 +336,7 @@ def _backward_view(state, inputs, radii, dL_dcolor, dL_ddepth, dL_dalpha, timer:
         dL_dcolor = torch.zeros((3, fr.H, fr.W), dtype=torch.float32, device=dev)
     dL_ddepth = _f32c(dL_ddepth, dev)
     dL_dalpha = _f32c(dL_dalpha, dev)
-    timer = timer or _ACTIVE_TIMER
+    timer = timer or _timing.ACTIVE
     staged = "ptrs" in state
     with _on_device(dev):
         stage_ev = timer.stage_events("backward") if isinstance(timer, StageTimer) and not staged else None
@@ -700,7 +413,6 @@ def backward_stages(settings: GaussianRasterizationSettings, inputs, saved, dL_d
 # iteration one `loss.item()` late (train.py:176).  graph_step.CapturedStep builds on this: forward + backward captured once
 # and replayed, the word checked before every replay, the step re-captured with room for the count after an overflow.
 NO_HOST_READ = False
-_CAPTURE_RECORD = None                   # graph_step's record of the forwards captured right now (None: no capture of ours)
 
 
 @contextlib.contextmanager
@@ -717,11 +429,11 @@ def no_host_read(enabled: bool = True):
 # ---------------------------------------------------------------------------------------------------------------------
 # the fast path: ONE C-ABI call per direction (include/scg_raster.h scg_forward / scg_backward)
 # ---------------------------------------------------------------------------------------------------------------------
-def _launch_forward(lib, fr, P, dev, model, in_ptrs, plan, cap, outs, pinned, ev, ckey, prepare_backward, stage_ev, stream):
+def _launch_forward(lib, fr, P, dev, model, in_ptrs, plan, cap, outs, pinned, ev, cw, prepare_backward, stage_ev, stream):
     """ONE attempt of forward_fused at capacity `cap`: the workspace, the option word, where the count goes, the library call.
     `outs`: the addresses of radii, colour, depth, alpha; `pinned`: this forward's pinned partial sums — None for a forward that
-    does not read the host, whose count arrives in a count word of camera `ckey`.  Returns (workspace, address of the cleared
-    gradient records or None, count word or None)."""
+    does not read the host, whose count arrives in the count word `cw`.  Returns (workspace, address of the cleared gradient
+    records or None)."""
     # the gradient records of the coming backward (cleared by the forward blend) live behind the workspace in the same
     # allocation: one torch.empty less per step (they are only ever addressed by raw pointer); without a host read the geometry
     # kernel's partial sums of num_rendered go to device memory behind the records: nobody reads them — the count comes from
@@ -740,11 +452,10 @@ def _launch_forward(lib, fr, P, dev, model, in_ptrs, plan, cap, outs, pinned, ev
         fr.long_np[:] = -1
         options &= ~(FORWARD_SKIP_RARE_SORT | FORWARD_RARE_8WAVE | FORWARD_SPLIT_LONG_LISTS)
     if pinned is None:
-        cw = _count_word(cap, P, ckey, dev.index)
         fr.c.num_rendered_out = cw.ptr
         sums = (wp + plan.total + ds_bytes + 255) & ~255
     else:
-        cw = fr.c.num_rendered_out = None
+        fr.c.num_rendered_out = None
         sums = pinned.ptr
     try:
         if model is None:
@@ -755,7 +466,7 @@ def _launch_forward(lib, fr, P, dev, model, in_ptrs, plan, cap, outs, pinned, ev
                                         stream), "scg_forward_model")
     finally:
         fr.c.num_rendered_out = None
-    return ws, dsplats, cw
+    return ws, dsplats
 
 
 def forward_fused(settings: GaussianRasterizationSettings, means3D, opacities, shs, colors_precomp, scales, rotations,
@@ -790,19 +501,20 @@ def forward_fused(settings: GaussianRasterizationSettings, means3D, opacities, s
                                 "(scg_binning_accepts_bound): this image / capacity takes the staged path, which reads the host")
         return None
     pinned = None if no_read else spec.take(plan.partial_bytes)   # this forward's pinned words (returned once num_rendered is read)
+    cw = taken = None                        # the count word of a forward that does not read the host; `taken`: not filed yet
     try:
         if model is None:
             inputs, M = _kernel_inputs(dev, means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp)
             in_ptrs = tuple(None if t is None else t.data_ptr() for t in inputs)
         else:
             inputs, M, in_ptrs = model.tensors, 16, None
-        fr = _frame_for(settings, P, M, dev, forward=True)
+        fr = _frame_for(settings, P, M, dev, True, cam, _frame_switches())
         _SPEC_STATS["one_call_forwards"] += 1
         if fr.c.tile_cost_in:
             _SPEC_STATS["tile_cost_hints"] += 1
         if fr.c.bwd_cost_in:
             _SPEC_STATS["bwd_order_hints"] += 1
-        timer = timer or _ACTIVE_TIMER
+        timer = timer or _timing.ACTIVE
         with _on_device(dev):
             stage_ev = timer.stage_events("forward") if isinstance(timer, StageTimer) else None
             stream = _stream(dev)
@@ -812,18 +524,15 @@ def forward_fused(settings: GaussianRasterizationSettings, means3D, opacities, s
             ip, hw4 = img.data_ptr(), H * W * 4
             outs = (radii.data_ptr(), ip, ip + 3 * hw4, ip + 4 * hw4)
             while True:
-                ws, dsplats, cw = _launch_forward(lib, fr, P, dev, model, in_ptrs, plan, cap, outs, pinned, ev, ckey,
-                                                  prepare_backward, stage_ev, stream)
+                if no_read:
+                    cw = taken = _count_word(cap, P, ckey, dev.index)
+                ws, dsplats = _launch_forward(lib, fr, P, dev, model, in_ptrs, plan, cap, outs, pinned, ev, cw,
+                                              prepare_backward, stage_ev, stream)
                 if no_read:
                     # launched, not waited for: the count is looked at when this camera is rendered next (or by settle_counts /
                     # the captured step that owns the word)
-                    _OVERFLOW["renders"] += 1
-                    if capturing:
-                        cw.captured = True
-                        (_CAPTURE_RECORD if _CAPTURE_RECORD is not None else _ANON_CAPTURED).append(cw)
-                    else:
-                        spec.pending.setdefault(ckey, []).append(cw)
-                    R = None
+                    _counts.file_word(spec, cw, ckey, capturing)
+                    taken = R = None
                     break
                 R = lib.scg_wait_num_rendered(ev, pinned.ptr, P)
                 if R < 0:
@@ -850,7 +559,7 @@ def forward_fused(settings: GaussianRasterizationSettings, means3D, opacities, s
     except BaseException:
         # kernels of the failed call may still be writing ws / img / radii and the pinned words: let them finish before Python
         # frees the buffers, and keep the pinned block out of circulation for good (dropping the reference hands it
-        # back to torch's caching host allocator)
+        # back to torch's caching host allocator); a count word nobody was handed goes back (a failed capture launched nothing)
         try:
             if not capturing:
                 torch.cuda.current_stream(dev).synchronize()
@@ -858,14 +567,9 @@ def forward_fused(settings: GaussianRasterizationSettings, means3D, opacities, s
             pass
         if pinned is not None:
             _QUARANTINE.append(pinned)
+        if taken is not None:
+            _counts.release([taken])
         raise
-
-
-def backward_fused(inputs, radii, state, dL_dcolor, dL_ddepth, dL_dalpha, timer: Optional[Callable] = None, into=None,
-                   d_means2D_out=None):
-    """Stages 4-5 over a forward_fused state in one library call (_backward_view); every parameter gradient is a view of ONE
-    flat fp32 allocation (_grads._grad_outputs).  Returns the same dict as backward_stages; `into` as there."""
-    return _backward_view(state, inputs, radii, dL_dcolor, dL_ddepth, dL_dalpha, timer, into, d_means2D_out)
 
 
 def _forward_view(settings: GaussianRasterizationSettings, inputs, needs_grad: bool):
@@ -887,53 +591,93 @@ def _forward_view(settings: GaussianRasterizationSettings, inputs, needs_grad: b
     return st["color"], st["radii"], st["depth"], st["alpha"], st["inputs"], state
 
 
+# ---- the K-view core of the four autograd nodes (_RasterizeGaussians and _RasterizeViews here, model_path's _RasterizeModel and
+# _RasterizeModelViews); a single-view node is K = 1 without a screen-space gradient slot per view -------------------------------
+def _views_forward(ctx, settings_list, inputs, needs_grad):
+    """The K views one after the other (_forward_view, `inputs` as there), each with its own state in ctx.states.  Returns
+    (color_0, radii_0, depth_0, alpha_0, color_1, ...) and the inputs as the kernels read them."""
+    outs, states, kin = [], [], None
+    for st_ in settings_list:
+        color, radii, depth, alpha, kin, state = _forward_view(st_, inputs, needs_grad)
+        states.append(state)
+        outs += [color, radii, depth, alpha]
+    ctx.states = states
+    ctx.inputs_present = tuple(t is not None for t in kin)
+    # the inputs (geometry_backward recomputes the forward chain from them) and radii go through autograd's saved
+    # tensors: an in-place update between forward and backward trips the version counter instead of silently
+    # pairing new parameter values with the splats / radii of the old ones
+    if needs_grad:
+        ctx.save_for_backward(*[t for t in kin if t is not None], *outs[1::4])
+    ctx.mark_non_differentiable(*outs[1::4])
+    ctx.set_materialize_grads(False)       # missing output gradients arrive as None, not as zero-filled tensors
+    return tuple(outs), kin
+
+
+def _views_backward(states, inputs, radii_all, grads, per_view_slots):
+    """Per view blend backward + geometry backward (_backward_view; `grads`: the flat output gradients).  Returns ({name: gradient},
+    dL/dmeans2D).  `per_view_slots`: means2D is (K, P, 3) and the second and later views ADD their parameter gradients to the
+    first one's in the kernel (`into`); (None, None) when no view reached the loss.  Otherwise K = 1 and dL/dmeans2D is (P, 3)."""
+    if not per_view_slots:
+        g = _backward_view(states[0], inputs, radii_all[0], grads[0], grads[2], grads[3])
+        return g, g["means2D"]
+    K = len(states)
+    dev, P = (inputs[0].device, inputs[0].shape[0]) if isinstance(inputs, tuple) else (inputs.device, inputs.P)
+    # the library writes a view's (P, 3) slot completely (zeros for culled Gaussians): no fill launch over K x P x 12 bytes;
+    # only the slot of a view whose outputs did not reach the loss is cleared here
+    d_means2D = torch.empty((K, P, 3), dtype=torch.float32, device=dev)
+    acc = None
+    for k in range(K):
+        g_color, _, g_depth, g_alpha = grads[4 * k: 4 * k + 4]
+        if g_color is None and g_depth is None and g_alpha is None:
+            d_means2D[k].zero_()
+            continue                                             # this view's outputs did not reach the loss
+        acc = _backward_view(states[k], inputs, radii_all[k], g_color, g_depth, g_alpha, into=acc, d_means2D_out=d_means2D[k])
+    return (acc, d_means2D) if acc is not None else (None, None)
+
+
+def _saved_views(ctx):
+    """(the seven kernel inputs, None for an absent one; the K radii) of a tensor-path node's forward."""
+    saved = ctx.saved_tensors                                # raises if an input was modified in place since forward
+    it = iter(saved)
+    return tuple(next(it) if present else None for present in ctx.inputs_present), saved[len(saved) - len(ctx.states):]
+
+
+def _caller_grads(ctx, g, d_means2D):
+    """A tensor-path node's gradients in forward argument order, in the callers' shapes (ctx.shapes)."""
+    means_shape, means2d_shape, sh_shape, opac_shape = ctx.shapes
+
+    def _shape(t, shape):
+        return t if (t is None or t.shape == shape) else t.reshape(shape)
+    return (_shape(g["means3D"], means_shape), _shape(d_means2D, means2d_shape), _shape(g["shs"], sh_shape),
+            g["colors_precomp"], _shape(g["opacities"], opac_shape), g["scales"], g["rotations"], g["cov3D_precomp"])
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings):
-        needs_grad = any(ctx.needs_input_grad)
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
         _require_cuda(means3D)
-        color, radii, depth, alpha, inputs, ctx.state = _forward_view(
-            raster_settings, (means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp), needs_grad)
         ctx.raster_settings = raster_settings
-        ctx.inputs_present = tuple(t is not None for t in inputs)
         ctx.shapes = (means3D.shape, means2D.shape, None if sh is None else sh.shape, opacities.shape)
         # inputs that are not fp32 (converted for the kernels): their gradients are cast back in backward
         odd = tuple(None if (t is None or t.dtype == torch.float32) else t.dtype
                     for t in (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp))
         ctx.odd_dtypes = odd if any(d is not None for d in odd) else None
-        # the inputs (geometry_backward recomputes the forward chain from them) and radii go through autograd's saved
-        # tensors: an in-place update between forward and backward trips the version counter instead of silently
-        # pairing new parameter values with the splats / radii of the old ones
-        if needs_grad:
-            ctx.save_for_backward(*[t for t in inputs if t is not None], radii)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)       # missing output gradients arrive as None, not as zero-filled tensors
-        return color, radii, depth, alpha
+        return _views_forward(ctx, (raster_settings,), (means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp),
+                              any(ctx.needs_input_grad))[0]
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha):
-        saved = ctx.saved_tensors                            # raises if an input was modified in place since forward
-        it = iter(saved)
-        inputs = tuple(next(it) if present else None for present in ctx.inputs_present)
-        radii = saved[-1]
+        inputs, radii = _saved_views(ctx)
         try:
-            g = _backward_view(ctx.state, inputs, radii, grad_color, grad_depth, grad_alpha)
+            g, d_means2D = _views_backward(ctx.states, inputs, radii, (grad_color, grad_radii, grad_depth, grad_alpha), False)
         except Exception:
             if ctx.raster_settings.debug:
                 names = ("means3D", "opacities", "shs", "colors_precomp", "scales", "rotations", "cov3D_precomp")
                 _debug_dump(DEBUG_SNAPSHOT_BW, "backward", ctx.raster_settings,
-                            dict(zip(names, inputs), radii=radii, grad_color=grad_color, grad_depth=grad_depth,
+                            dict(zip(names, inputs), radii=radii[0], grad_color=grad_color, grad_depth=grad_depth,
                                  grad_alpha=grad_alpha))
             raise
-        means_shape, means2d_shape, sh_shape, opac_shape = ctx.shapes
-
-        def _shape(t, shape):
-            return t if (t is None or t.shape == shape) else t.reshape(shape)
-        # order = forward argument order
-        grads = (_shape(g["means3D"], means_shape), _shape(g["means2D"], means2d_shape), _shape(g["shs"], sh_shape),
-                 g["colors_precomp"], _shape(g["opacities"], opac_shape), g["scales"], g["rotations"],
-                 g["cov3D_precomp"])
+        grads = _caller_grads(ctx, g, d_means2D)
         if ctx.odd_dtypes is not None:
             grads = tuple(t if (t is None or d is None) else t.to(d) for t, d in zip(grads, ctx.odd_dtypes))
         return grads + (None,)
@@ -941,6 +685,17 @@ class _RasterizeGaussians(torch.autograd.Function):
 
 def _none_if_empty(t):
     return None if (t is None or (isinstance(t, torch.Tensor) and t.numel() == 0)) else t
+
+
+def _exactly_one_of(shs, colors_precomp, scales, rotations, cov3D_precomp):
+    """The five optional inputs, None for an absent or empty one — or upstream's error when the combination is not a render."""
+    shs, colors_precomp, scales, rotations, cov3D_precomp = map(_none_if_empty, (shs, colors_precomp, scales, rotations, cov3D_precomp))
+    if (shs is None) == (colors_precomp is None):
+        raise Exception("Please provide excatly one of either SHs or precomputed colors!")
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+    return shs, colors_precomp, scales, rotations, cov3D_precomp
 
 
 DEBUG_SNAPSHOT_FW = "snapshot_fw.dump"     # file names of upstream's debug dumps [UPSTREAM-RECALL]
@@ -992,13 +747,7 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):
-        shs, colors_precomp = _none_if_empty(shs), _none_if_empty(colors_precomp)
-        scales, rotations, cov3D_precomp = _none_if_empty(scales), _none_if_empty(rotations), _none_if_empty(cov3D_precomp)
-        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-            raise Exception("Please provide excatly one of either SHs or precomputed colors!")
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _exactly_one_of(shs, colors_precomp, scales, rotations, cov3D_precomp)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                    self.raster_settings)
 
@@ -1017,51 +766,15 @@ class _RasterizeViews(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings_list):
-        needs_grad = any(ctx.needs_input_grad)
         _require_cuda(means3D)
-        outs, states, inputs = [], [], None
-        for st_ in settings_list:
-            color, radii, depth, alpha, inputs, state = _forward_view(
-                st_, (means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp), needs_grad)
-            states.append(state)
-            outs += [color, radii, depth, alpha]
-        ctx.states = states
-        ctx.inputs_present = tuple(t is not None for t in inputs)
         ctx.shapes = (means3D.shape, means2D.shape, None if sh is None else sh.shape, opacities.shape)
-        if needs_grad:
-            ctx.save_for_backward(*[t for t in inputs if t is not None], *outs[1::4])
-        ctx.mark_non_differentiable(*outs[1::4])
-        ctx.set_materialize_grads(False)
-        return tuple(outs)
+        return _views_forward(ctx, settings_list, (means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp),
+                              any(ctx.needs_input_grad))[0]
 
     @staticmethod
     def backward(ctx, *grads):
-        K = len(ctx.states)
-        saved = ctx.saved_tensors
-        it = iter(saved)
-        inputs = tuple(next(it) if present else None for present in ctx.inputs_present)
-        radii_all = saved[len(saved) - K:]
-        means_shape, means2d_shape, sh_shape, opac_shape = ctx.shapes
-        P = inputs[0].shape[0]
-        # scg_backward writes a view's (P, 3) slot completely (zeros for culled Gaussians): no fill launch over K x P x 12 bytes;
-        # only the slot of a view whose outputs did not reach the loss is cleared here
-        d_means2D = torch.empty((K, P, 3), dtype=torch.float32, device=inputs[0].device)
-        acc = None
-        for k in range(K):
-            g_color, _, g_depth, g_alpha = grads[4 * k: 4 * k + 4]
-            if g_color is None and g_depth is None and g_alpha is None:
-                d_means2D[k].zero_()
-                continue                                             # this view's outputs did not reach the loss
-            acc = _backward_view(ctx.states[k], inputs, radii_all[k], g_color, g_depth, g_alpha, into=acc,
-                                 d_means2D_out=d_means2D[k])
-        if acc is None:
-            return (None,) * 9
-
-        def _shape(t, shape):
-            return None if t is None else t.reshape(shape)
-        return (_shape(acc["means3D"], means_shape), d_means2D.reshape(means2d_shape), _shape(acc["shs"], sh_shape),
-                acc["colors_precomp"], _shape(acc["opacities"], opac_shape), acc["scales"], acc["rotations"],
-                acc["cov3D_precomp"], None)
+        acc, d_means2D = _views_backward(ctx.states, *_saved_views(ctx), grads, True)
+        return (None,) * 9 if acc is None else _caller_grads(ctx, acc, d_means2D) + (None,)
 
 
 class GaussianRasterizerViews(nn.Module):
@@ -1076,13 +789,7 @@ class GaussianRasterizerViews(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):
-        shs, colors_precomp = _none_if_empty(shs), _none_if_empty(colors_precomp)
-        scales, rotations, cov3D_precomp = _none_if_empty(scales), _none_if_empty(rotations), _none_if_empty(cov3D_precomp)
-        if (shs is None) == (colors_precomp is None):
-            raise Exception("Please provide excatly one of either SHs or precomputed colors!")
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _exactly_one_of(shs, colors_precomp, scales, rotations, cov3D_precomp)
         K = len(self.raster_settings_list)
         if means2D.dim() != 3 or means2D.shape[0] != K:
             raise ValueError(f"means2D must be ({K}, P, 3): one screen-space gradient slot per view")

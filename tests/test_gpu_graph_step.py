@@ -97,6 +97,35 @@ def test_no_host_read_overflow_is_noticed_at_the_cameras_next_render():
         assert torch.equal(clipped[1], truth[1])                         # radii come from the geometry stage: never clipped
 
 
+def test_a_forward_the_library_rejects_gives_its_count_word_back():
+    """scg_forward rejects sh_degree 4 on the host, before anything is launched: the count word the attempt took goes back to the
+    pool (without the release in forward_fused's error path the free list stays one slot short)."""
+    from scgaussian_amd import _counts, _lib
+    P, W, H = 64, 32, 32
+    sc = syn.make_scene(P, W, H, seed=1).to(DEV)
+    st = pu.hip_settings(syn.default_camera(W, H), 3, (0.0, 0.0, 0.0))
+    args = dict(means3D=sc.means3D, means2D=torch.zeros_like(sc.means3D), opacities=sc.opacities, shs=sc.shs, scales=sc.scales,
+                rotations=sc.rotations)
+    with torch.no_grad():
+        R.GaussianRasterizer(st)(**args)                                 # a normal render: the camera's capacity is known
+        torch.cuda.synchronize()
+        before = R.settle_counts()
+        _counts._count_pool()
+        spec, ckey = R._spec_state(sc.means3D.device), (W, H, R._camera_key(st.viewmatrix))
+        free = len(_counts._COUNT_FREE)
+        with R.no_host_read():
+            with pytest.raises(_lib.ScgError) as err:
+                R.GaussianRasterizer(st._replace(sh_degree=4))(**args)
+            assert "sh_degree 4 not in 0..3" in str(err.value)
+            assert len(_counts._COUNT_FREE) == free
+            assert ckey not in spec.pending
+            R.GaussianRasterizer(st)(**args)
+        torch.cuda.synchronize()
+        after = R.settle_counts()
+    assert after["settled"] == before["settled"] + 1 and after["overflows"] == before["overflows"]
+    assert len(_counts._COUNT_FREE) == free
+
+
 @pytest.mark.parametrize("workload", ["small", "S1"])
 def test_captured_step_replays_the_eager_step(workload):
     P, W, H = (10_000, 256, 256) if workload == "S1" else (4_000, 160, 128)

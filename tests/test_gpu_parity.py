@@ -643,7 +643,7 @@ def test_one_call_path_equals_the_staged_path_and_recovers_from_a_small_bound():
     assert spec.cam_hint[(W, H, R._camera_key(st.viewmatrix))][2] == P2
     # a forward that ran without backward state cannot be differentiated: the binding says so instead of returning garbage
     with pytest.raises(Exception, match="without backward state"):
-        R.backward_fused(out2[4]["inputs"], out2[1], out2[4], torch.zeros(3, H, W, device=dev), None, None)
+        R._backward_view(out2[4], out2[4]["inputs"], out2[1], torch.zeros(3, H, W, device=dev), None, None)
     # gradients: autograd through the one-call path vs through the staged path
     grads = syn.make_upstream_grads(W, H, seed=3)
     timer = R.StageTimer()

@@ -285,3 +285,67 @@ def test_sh_tail_promise_is_decided_before_and_recorded_after_the_launch():
         G.commit_promise(None, 1, False)
     finally:
         del G._ARENA_POOLS[("promise-test", None)]
+
+
+def _hand_built_word(slot, value, cap=100_000, device_index=977):
+    """A _CountWord over a one-element numpy word (no pinned memory); device 977 is nobody's: its state is the test's own."""
+    import numpy as np
+    w = C._CountWord()
+    w.slot, w.np, w.ptr, w.cap, w.P, w.key, w.device_index, w.captured = \
+        slot, np.array([value], dtype=np.uint32), 0, cap, 5000, (640, 480, b"camera"), device_index, False
+    return w
+
+
+def test_capture_record_nests_and_restores_the_outer_list():
+    spec = types.SimpleNamespace(pending={})
+    outer_before = C._CAPTURE_RECORD
+    anon_before, renders = list(C._ANON_CAPTURED), C._OVERFLOW["renders"]
+    a, b, c = (_hand_built_word(i, C._COUNT_ARMED) for i in range(3))
+    with C.capture_record() as outer:
+        assert outer == [] and C._CAPTURE_RECORD is outer
+        C.file_word(spec, a, a.key, True)
+        with C.capture_record() as inner:
+            assert inner == [] and inner is not outer and C._CAPTURE_RECORD is inner
+            C.file_word(spec, b, b.key, True)
+        assert C._CAPTURE_RECORD is outer
+        with pytest.raises(ZeroDivisionError):
+            with C.capture_record():
+                raise ZeroDivisionError
+        assert C._CAPTURE_RECORD is outer
+        C.file_word(spec, c, c.key, False)                       # not captured: the camera's next render looks at it
+    assert C._CAPTURE_RECORD is outer_before
+    assert outer == [a] and inner == [b] and a.captured and b.captured and not c.captured
+    assert spec.pending == {c.key: [c]} and C._ANON_CAPTURED == anon_before and C._OVERFLOW["renders"] == renders + 3
+
+
+def test_release_puts_each_slot_back_once():
+    free_before = list(C._COUNT_FREE)
+    try:
+        C.release([_hand_built_word(s, 0) for s in (900_001, 900_002, 900_003)])
+        assert C._COUNT_FREE == free_before + [900_001, 900_002, 900_003]
+        C.release([])
+        assert C._COUNT_FREE == free_before + [900_001, 900_002, 900_003]
+    finally:
+        C._COUNT_FREE[:] = free_before
+
+
+def test_settle_replayed_rearms_the_word_and_settles_the_count():
+    spec = C._SPEC_STATE[977] = types.SimpleNamespace(hint={}, cam_hint={}, pending={})
+    try:
+        before = dict(C._OVERFLOW)
+        w = _hand_built_word(0, C._COUNT_ARMED)
+        assert C.settle_replayed(w) is None                      # armed: nothing has arrived, nothing is touched
+        assert C._OVERFLOW == before and int(w.np[0]) == C._COUNT_ARMED and spec.cam_hint == {} and spec.hint == {}
+        w.np[0] = 80_000                                         # a count within the capacity
+        assert C.settle_replayed(w) == 80_000
+        assert int(w.np[0]) == C._COUNT_ARMED and w.value() is None
+        assert C._OVERFLOW["settled"] == before["settled"] + 1 and C._OVERFLOW["overflows"] == before["overflows"]
+        assert spec.cam_hint[w.key] == (100_000, 80_000, 5000)
+        w.np[0] = 150_000                                        # beyond it: counted, and the camera has room for it next time
+        assert C.settle_replayed(w) == 150_000
+        assert int(w.np[0]) == C._COUNT_ARMED
+        assert C._OVERFLOW["settled"] == before["settled"] + 2 and C._OVERFLOW["overflows"] == before["overflows"] + 1
+        assert spec.cam_hint[w.key][0] >= 150_000 + 150_000 // 8 and spec.cam_hint[w.key][1:] == (150_000, 5000)
+        assert C._OVERFLOW["renders"] == before["renders"]
+    finally:
+        del C._SPEC_STATE[977]

@@ -31,3 +31,19 @@ def backward_at(n_tiles):
 def log_words(n_tiles):
     """Words behind the cost words that a caller allocates: every probe of the build logs, so all regions must exist."""
     return backward_at(n_tiles) + (n_tiles + TILE_PAD) * BACKWARD_WORDS_PER_TILE + TAIL_WORDS
+
+
+def big_hints(words):
+    """Make every camera's two cost buffers `words` longer than its tile count from now on (the probe build logs behind the cost
+    words): wraps scgaussian_amd._frames._hints_for.  Returns a function that gives the record of the one camera rendered since."""
+    import torch
+    from scgaussian_amd import _frames
+    orig = _frames._hints_for
+
+    def wrapper(*a, **k):
+        h = orig(*a, **k)
+        if h.cost is not None and h.cost[0].numel() < words:
+            h.cost = [torch.zeros(h.cost[0].numel() + words, dtype=torch.int32, device=h.cost[0].device) for _ in range(2)]
+        return h
+    _frames._hints_for = wrapper
+    return lambda: next(iter(_frames._CAM_HINTS.values()))

@@ -32,17 +32,7 @@ rast = R.GaussianRasterizer(sett)
 ups = tuple(t.to(dev) for t in syn.make_upstream_grads(W, H, seed=10))
 OFF = TL.backward_at(n_tiles)
 LOG = TL.log_words(n_tiles)                      # every probe of the tl build logs: all regions must exist
-orig = R._hints_for
-
-
-def big_hints(*a):
-    h = orig(*a)
-    if h.cost is not None and h.cost[0].numel() < LOG:
-        h.cost = [torch.zeros(n_tiles + LOG, dtype=torch.int32, device=dev) for _ in range(2)]
-    return h
-
-
-R._hints_for = big_hints
+record = TL.big_hints(LOG)
 for _ in range(6):
     for p in params:
         p.grad = None
@@ -50,7 +40,7 @@ for _ in range(6):
                           scales=scales, rotations=rots)
     torch.autograd.backward([c, d, a], list(ups))
 torch.cuda.synchronize()
-h = next(iter(R._CAM_HINTS.values()))
+h = record()
 log = h.cost[h.cur].cpu().numpy().astype(np.uint32)[n_tiles + OFF:]
 rec = log[: (log.size // TL.BACKWARD_RECORD) * TL.BACKWARD_RECORD].reshape(-1, TL.BACKWARD_RECORD)
 rec = rec[(rec[:, 3] >> 20) == TL.SIG_BACKWARD >> 20]

@@ -11,7 +11,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from scgaussian_amd import _lib, rasterizer as R, synthetic as syn          # noqa: E402
+from scgaussian_amd import _lib, synthetic as syn                            # noqa: E402
 import bench                                                                   # noqa: E402
 import _timeline_log as TL                                                     # noqa: E402
 
@@ -25,24 +25,13 @@ params = [sc.means3D, sc.shs, sc.opacities, sc.scales, sc.rotations]
 sett = bench.settings_for(syn.default_camera(W, H), 3, torch.zeros(3, device=dev), dev)
 n_tiles = ((W + 15) // 16) * ((H + 15) // 16)
 LOG = TL.log_words(n_tiles)                      # every probe of the tl build logs: all regions must exist
-orig = R._hints_for
-
-
-def big_hints(*a):
-    h = orig(*a)
-    if h.cost is not None and h.cost[0].numel() < LOG:
-        n_tiles = h.cost[0].numel()
-        h.cost = [torch.zeros(n_tiles + LOG, dtype=torch.int32, device=dev) for _ in range(2)]
-    return h
-
-
-R._hints_for = big_hints
+record = TL.big_hints(LOG)
 n_tiles = ((W + 15) // 16) * ((H + 15) // 16)
 with torch.no_grad():
     for _ in range(5):
         bench.render_once(sett, params)
     torch.cuda.synchronize()
-    h = next(iter(R._CAM_HINTS.values()))
+    h = record()
     for c in h.cost:
         c[n_tiles:].zero_()
     bench.render_once(sett, params)

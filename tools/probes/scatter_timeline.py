@@ -11,7 +11,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from scgaussian_amd import _lib, rasterizer as R, synthetic as syn          # noqa: E402
+from scgaussian_amd import _lib, synthetic as syn                            # noqa: E402
 sys.path.insert(0, ROOT)
 import bench                                                                   # noqa: E402
 import _timeline_log as TL                                                     # noqa: E402
@@ -26,23 +26,12 @@ params = [sc.means3D, sc.shs, sc.opacities, sc.scales, sc.rotations]
 sett = bench.settings_for(syn.default_camera(W, H), 3, torch.zeros(3, device=dev), dev)
 n_tiles = ((W + 15) // 16) * ((H + 15) // 16)
 LOG = TL.log_words(n_tiles)                      # every probe of the tl build logs: all regions must exist
-orig = R._hints_for
-
-
-def big_hints(*a):
-    h = orig(*a)
-    if h.cost is not None and h.cost[0].numel() < LOG:
-        n_tiles = h.cost[0].numel()
-        h.cost = [torch.zeros(n_tiles + LOG, dtype=torch.int32, device=dev) for _ in range(2)]
-    return h
-
-
-R._hints_for = big_hints
+record = TL.big_hints(LOG)
 with torch.no_grad():
     for _ in range(5):
         bench.render_once(sett, params)
     torch.cuda.synchronize()
-h = next(iter(R._CAM_HINTS.values()))
+h = record()
 n_tiles = ((W + 15) // 16) * ((H + 15) // 16)
 log = h.cost[h.cur].cpu().numpy().astype(np.uint32)[n_tiles + TL.SCATTER_AT: n_tiles + TL.GEOMETRY_AT]
 rec = log[: (log.size // TL.SCATTER_RECORD) * TL.SCATTER_RECORD].reshape(-1, TL.SCATTER_RECORD)
