@@ -16,11 +16,11 @@ import torch
 
 import geometry_refs as GR
 import loss_refs as LR
+import model_refs as MR
 import parity_utils as pu
 from oracle import torch_rasterizer as orc
 from scgaussian_amd import _lib
 from scgaussian_amd import model_path as mp
-from scgaussian_amd import ply_io
 from scgaussian_amd import rasterizer as R
 from scgaussian_amd import render as rmod
 from scgaussian_amd import synthetic as syn
@@ -44,26 +44,8 @@ def _planted():
     return GR.planted()
 
 
-def _interleaved(pl):
-    """Class order: member j of every class, then member j + 1 of every class — neighbouring lanes differ in class."""
-    per = [pl.members(c).tolist() for c in GR.CLASSES]
-    return [per[c][j] for j in range(GR.PER_CLASS) for c in range(len(per))]
-
-
-def _layout(pl, P, block, all_culled_first=False):
-    """Indices into the planted set for a P-member scene: the interleaved order repeated cyclically, with a culled member first,
-    last and on either side of every workgroup boundary; all_culled_first: the whole first workgroup is culled, and nothing else
-    is moved (the Gaussians behind it are the interleaved order's)."""
-    base = _interleaved(pl)
-    culled = [i for c in GR.CULLED for i in pl.members(c).tolist()]
-    shift = 1 if all_culled_first else 0                    # (the interleaved order starts with a culled member: not behind the workgroup)
-    idx = [base[(i + shift) % len(base)] for i in range(P)]
-    spots = {0, P - 1} | {b for k in range(1, P // block + 1) for b in (k * block - 1, k * block)}
-    if all_culled_first:
-        spots = set(range(min(block, P)))
-    for n, pos in enumerate(sorted(s for s in spots if 0 <= s < P)):
-        idx[pos] = culled[n % len(culled)]
-    return torch.tensor(idx, dtype=torch.long)
+# (shared with tests/test_gpu_model_kernel_edges.py: they live in tests/model_refs.py)
+_interleaved, _layout, _model_members, _raw_model = MR.interleaved, MR.layout, MR.model_members, MR.raw_model
 
 
 def _inputs(pl, deg, mode, M):
@@ -293,36 +275,6 @@ def test_sh_tail_zero_leaves_the_tails_alone_and_writes_the_same_bits(form):
 
 
 # -------------------------------------------------------------------------------------------------------------- model kernel
-
-def _model_members(pl, P=120):
-    """P members of the planted set, classes interleaved, 7 or 8 of each, a clamp_x member first (the set of one of the
-    (1, P - 1) split)."""
-    order = _interleaved(pl)
-    first = GR.CLASSES.index("clamp_x")
-    return torch.tensor((order[first:] + order[:first])[:P], dtype=torch.long)
-
-
-def _raw_model(pl, idx, n_ray):
-    """The planted members as a raw model whose activations reproduce the planted values: rays from the origin with direction
-    (x/z, y/z, 1) and zval = z (the product is exact for the members ON a threshold: z is a power of two there), logit, log-scale
-    (the scale modifier stays with the render call) and un-normalised quaternions."""
-    sc = pl.scene
-    m3, P = sc.means3D[idx], len(idx)
-    z = m3[:, 2:3]
-    rayd = torch.cat([m3[:, :2] / z, torch.ones(P, 1)], 1)
-    g = torch.Generator().manual_seed(17)
-    o = sc.opacities[idx]
-    logit = torch.where(o <= 0, torch.full_like(o, -200.0), torch.where(o >= 1, torch.full_like(o, 30.0), torch.log(o / (1 - o))))
-    logs = torch.log(sc.scales[idx])
-    rot = sc.rotations[idx] * (0.5 + 1.5 * torch.rand(P, 1, generator=g))
-    dc, rest = sc.shs[idx, :1].contiguous(), sc.shs[idx, 1:].contiguous()
-    r, b = slice(0, n_ray), slice(n_ray, P)
-    return ply_io.RayBoundModel(
-        features_dc=dc[r].contiguous(), features_rest=rest[r].contiguous(), opacity=logit[r].contiguous(), scaling=logs[r].contiguous(),
-        rotation=rot[r].contiguous(), zval=z[r].contiguous(), rayo=torch.zeros(n_ray, 3), rayd=rayd[r].contiguous(),
-        bg_xyz=m3[b].contiguous(), bg_features_dc=dc[b].contiguous(), bg_features_rest=rest[b].contiguous(),
-        bg_opacity=logit[b].contiguous(), bg_scaling=logs[b].contiguous(), bg_rotation=rot[b].contiguous(), max_sh_degree=3)
-
 
 @pytest.mark.parametrize("deg", [0, 3])
 @pytest.mark.parametrize("n_ray", [120, 0, 61, 1])
