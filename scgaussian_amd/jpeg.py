@@ -1,0 +1,334 @@
+"""JPEG files and Motion-JPEG video from uint8 device tensors, host side (libscg_jpg.so, csrc/jpg/scg_jpeg.h states the stream).
+
+    packed = jpeg.encode([img0, img1, ...], quality=90, subsampling="4:2:0", bgr=False)     three launches, no host read
+    packed.to_host()                              TWO host reads: the table, then exactly `total` bytes into pinned memory
+    packed.files() / packed.write(paths)          complete JPEG files, the bytes libjpeg writes for the same options
+    plan = jpeg.JpegPlan(shapes, device, ...)     the uploaded tables and the buffers, for repeated and captured calls
+    jpeg.save_jpeg(path, tensor)                  one image; what the kernels do not take goes to Pillow
+    jpeg.write_avi(path, files, fps, W, H)        the files as the frames of a Motion-JPEG AVI: host only, `struct` alone
+
+An image is a contiguous uint8 tensor on the GPU shaped (H, W), (H, W, 1) or (H, W, 3); a list of them or one (N, H, W, 3) tensor
+is a batch.  The output capacity of an image defaults to header + 3 H W bytes, which every real frame stays far below; a file that
+needs more is flagged by the kernels, no byte of it is written, and to_host() encodes the batch once more with what the table says
+each file needs.  A missing library raises: there is no CPU stand-in for a kernel.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import struct
+from fractions import Fraction
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib, _lib_jpg
+from ._lib_jpg import check
+
+SUBSAMPLINGS = {"4:4:4": _lib_jpg.JPEG_444, "4:2:0": _lib_jpg.JPEG_420}
+_WHAT = "jpeg.encode"
+_IMAGE_DTYPE = np.dtype([("src", "<u8"), ("H", "<i4"), ("W", "<i4"), ("channels", "<i4"), ("first_segment", "<i4"), ("segments", "<i4"),
+                         ("mcus", "<i4"), ("header_offset", "<i4"), ("header_bytes", "<i4"), ("capacity", "<u4"), ("reserved", "<i4")])
+_SEGMENT_DTYPE = np.dtype([("image", "<i4"), ("row", "<i4")])
+assert _IMAGE_DTYPE.itemsize == C.sizeof(_lib_jpg.ScgJpegImage) and _SEGMENT_DTYPE.itemsize == C.sizeof(_lib_jpg.ScgJpegSegment)
+AVI_MAX_BYTES = 2 ** 32 - 1
+
+
+def _err(msg: str) -> _lib.ScgError:
+    return _lib.ScgError(f"{_WHAT}: {msg}")
+
+
+def _hwc(shape) -> tuple:
+    shape = tuple(int(s) for s in shape)
+    if len(shape) == 2:
+        shape = shape + (1,)
+    if len(shape) != 3 or shape[2] not in (1, 3):
+        raise _err(f"an image is (H, W), (H, W, 1) or (H, W, 3), not {shape}")
+    return shape
+
+
+def _options(quality, subsampling, bgr):
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+        raise _err(f"quality {quality!r} is not an integer in 1..100")
+    if subsampling not in SUBSAMPLINGS:
+        raise _err(f'subsampling {subsampling!r} is not "4:4:4" or "4:2:0"')
+    return int(quality), str(subsampling), bool(bgr)
+
+
+def takes(t) -> bool:
+    """Is `t` an image the kernels take as it is?  (What they do not take goes to Pillow in save_jpeg.)"""
+    return (isinstance(t, torch.Tensor) and t.device.type == "cuda" and t.dtype == torch.uint8 and t.is_contiguous() and
+            (t.dim() == 2 or (t.dim() == 3 and t.shape[2] in (1, 3))) and t.numel() > 0)
+
+
+def layout(shapes: Sequence, quality: int = 90, subsampling: str = "4:2:0", capacities=None):
+    """scg_jpeg_layout on the host alone (no GPU is touched): (ScgJpegLayout, image records, segment records, header templates)."""
+    quality, subsampling, _ = _options(quality, subsampling, False)
+    shapes = [_hwc(s) for s in shapes]
+    n = len(shapes)
+    lay = _lib_jpg.ScgJpegLayout()
+    images = np.zeros(n, dtype=_IMAGE_DTYPE)
+    if n == 0:
+        return lay, images, np.zeros(0, dtype=_SEGMENT_DTYPE), np.zeros(0, dtype=np.uint8)
+    lib = _lib_jpg.load()
+    hwc = np.ascontiguousarray(np.asarray(shapes, dtype=np.int32).reshape(n, 3))
+    hp = hwc.ctypes.data_as(C.POINTER(C.c_int32))
+    cp = None
+    if capacities is not None:
+        caps = np.ascontiguousarray(np.asarray(capacities, dtype=np.int64).reshape(-1))
+        if caps.shape[0] != n or caps.min() < 0 or caps.max() > 2 ** 32 - 1:
+            raise _err(f"capacities must be {n} values in 0..2^32 - 1")
+        caps = caps.astype(np.uint32)
+        cp = caps.ctypes.data_as(C.POINTER(C.c_uint32))
+    sub = SUBSAMPLINGS[subsampling]
+    check(lib.scg_jpeg_layout(n, hp, quality, sub, cp, C.byref(lay), None, None, None), "scg_jpeg_layout")
+    segments = np.zeros(int(lay.segments), dtype=_SEGMENT_DTYPE)
+    headers = np.zeros(int(lay.headers_bytes), dtype=np.uint8)
+    check(lib.scg_jpeg_layout(n, hp, quality, sub, cp, C.byref(lay), images.ctypes.data_as(C.POINTER(_lib_jpg.ScgJpegImage)),
+                              segments.ctypes.data_as(C.POINTER(_lib_jpg.ScgJpegSegment)),
+                              headers.ctypes.data_as(C.POINTER(C.c_uint8))), "scg_jpeg_layout")
+    return lay, images, segments, headers
+
+
+class JpegPlan:
+    """Everything of a batch that depends on its shapes and options alone: the layout, the image, segment and header tables on the
+    device, the workspace and the output buffer.  encode() on it allocates nothing and reads nothing back, so it can be captured in
+    a graph: `inputs` are the plan's own image tensors (views of one arena), to be rewritten in place between replays."""
+
+    def __init__(self, shapes: Sequence, device="cuda", quality: int = 90, subsampling: str = "4:2:0", bgr: bool = False,
+                 capacities=None, own_inputs: bool = True):
+        self.device = torch.device(device)
+        _lib.stream_of(self.device, "JpegPlan")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.quality, self.subsampling, self.bgr = _options(quality, subsampling, bgr)
+        self.shapes = [_hwc(s) for s in shapes]
+        self.layout, self.images_host, segments, headers = layout(self.shapes, self.quality, self.subsampling, capacities)
+        self.inputs: List[torch.Tensor] = []
+        self._src = None
+        n = len(self.shapes)
+        if n == 0:
+            return
+        with torch.cuda.device(self.device):
+            self.segments_dev = torch.from_numpy(segments.view(np.uint8).reshape(-1).copy()).to(self.device)
+            self.headers_dev = torch.from_numpy(headers.copy()).to(self.device)
+            self.images_dev = torch.empty(n * _IMAGE_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+            self.workspace = torch.empty(int(self.layout.workspace_bytes), dtype=torch.uint8, device=self.device)
+            self.out = torch.empty(int(self.layout.capacity), dtype=torch.uint8, device=self.device)
+            if own_inputs:
+                sizes = [h * w * c for h, w, c in self.shapes]
+                starts = np.concatenate([[0], np.cumsum([(s + 15) // 16 * 16 for s in sizes])])
+                self.arena = torch.zeros(int(starts[-1]), dtype=torch.uint8, device=self.device)
+                self.inputs = [self.arena[int(o):int(o) + s].view(shape) for o, s, shape in zip(starts, sizes, self.shapes)]
+                self._bind(self.inputs)
+        t = self.layout.table_offset
+        self.table = self.workspace[t:t + self.layout.table_bytes].view(torch.int32)
+
+    def _bind(self, images) -> None:
+        """Put the images' addresses into the image table; upload it when they changed (a host-to-device copy, never a read)."""
+        src = [int(t.data_ptr()) for t in images]
+        if src == self._src:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise _err("a captured call must use the tensors of the call before it (JpegPlan.inputs): the image table cannot be "
+                       "uploaded inside a capture")
+        self.images_host["src"] = src
+        self.images_dev.copy_(torch.from_numpy(self.images_host.view(np.uint8).reshape(-1).copy()))
+        self._src = src
+
+    def args(self) -> _lib_jpg.ScgJpegEncode:
+        """The ScgJpegEncode of this plan."""
+        a = _lib_jpg.ScgJpegEncode()
+        a.struct_bytes = C.sizeof(_lib_jpg.ScgJpegEncode)
+        a.images, a.quality, a.subsampling, a.bgr = len(self.shapes), self.quality, SUBSAMPLINGS[self.subsampling], int(self.bgr)
+        a.headers_bytes = int(self.layout.headers_bytes)
+        a.images_host = self.images_host.ctypes.data
+        a.images_dev, a.segments_dev, a.headers_dev = self.images_dev.data_ptr(), self.segments_dev.data_ptr(), self.headers_dev.data_ptr()
+        return a
+
+    @torch.no_grad()
+    def encode(self, images: Optional[Sequence[torch.Tensor]] = None) -> "PackedJpegs":
+        """Three launches on the current stream.  images: None for the plan's own inputs, or tensors of the plan's shapes."""
+        if not self.shapes:
+            return PackedJpegs(self)
+        if images is None:
+            images = self.inputs
+            if not images:
+                raise _err("the plan has no inputs of its own (own_inputs=False): pass the images")
+        images = list(images)
+        if len(images) != len(self.shapes):
+            raise _err(f"{len(images)} images for a plan of {len(self.shapes)}")
+        for i, (t, shape) in enumerate(zip(images, self.shapes)):
+            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.uint8 or not t.is_contiguous() or \
+                    _hwc(t.shape) != shape:
+                raise _err(f"image {i} must be a contiguous uint8 tensor of shape {shape} on {self.device}")
+        stream = _lib.stream_of(self.out, _WHAT)
+        with torch.cuda.device(self.device):
+            self._bind(images)
+            a = self.args()
+            check(_lib_jpg.load().scg_jpeg_encode(C.byref(a), self.out.data_ptr(), self.out.numel(), self.workspace.data_ptr(),
+                                                  self.workspace.numel(), stream), "scg_jpeg_encode")
+        return PackedJpegs(self, keep=images)
+
+
+class PackedJpegs:
+    """The files of a batch in the plan's output buffer, each at a multiple of 16 bytes, and the table that says where."""
+
+    def __init__(self, plan: JpegPlan, keep=None):
+        self.plan, self._keep = plan, keep
+        self.table_host: Optional[np.ndarray] = None      # (images + 1, 4) uint32: offset, bytes, need, overflow
+        self.host: Optional[torch.Tensor] = None
+        self.retried = False
+
+    def __len__(self):
+        return len(self.plan.shapes)
+
+    def to_host(self, retry: bool = True) -> "PackedJpegs":
+        """The batch's TWO host reads: the table, then exactly `total` bytes of the buffer into pinned memory.  When the table flags
+        a file that did not fit its capacity and `retry` holds, the batch is encoded once more with what every file needs (and read
+        again); without `retry` the flagged files stay empty."""
+        n = len(self)
+        if self.host is not None or n == 0:
+            if n == 0 and self.table_host is None:
+                self.table_host = np.zeros((1, 4), dtype=np.uint32)
+            return self
+        plan = self.plan
+        stream = torch.cuda.current_stream(plan.device)
+        table = torch.empty((n + 1, 4), dtype=torch.int32, pin_memory=True)
+        table.copy_(plan.table.view(n + 1, 4), non_blocking=True)
+        stream.synchronize()
+        self.table_host = table.numpy().view(np.uint32)
+        total = int(self.table_host[n, 0])
+        if int(self.table_host[n, 1]) != n or total > plan.out.numel():
+            raise _err(f"the table names {int(self.table_host[n, 1])} images and {total} bytes: not this batch's")
+        if retry and int(self.table_host[n, 2]) and not self.retried:
+            need = np.maximum(self.table_host[:n, 2].astype(np.int64), plan.images_host["capacity"].astype(np.int64))
+            again = JpegPlan(plan.shapes, plan.device, plan.quality, plan.subsampling, plan.bgr, capacities=need, own_inputs=False)
+            self.plan = again.encode(self._keep).plan
+            self.retried = True
+            return self.to_host(retry=False)
+        self.host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        self.host.copy_(plan.out[:total], non_blocking=True)
+        stream.synchronize()
+        return self
+
+    @property
+    def overflowed(self) -> List[int]:
+        """The images whose file did not fit (after to_host)."""
+        self.to_host()
+        return [i for i in range(len(self)) if self.table_host[i, 3]]
+
+    def files(self) -> List[bytes]:
+        """The complete JPEG files (b"" for a file that did not fit and was not encoded again)."""
+        self.to_host()
+        if len(self) == 0:
+            return []
+        data = memoryview(self.host.numpy())
+        return [bytes(data[int(o):int(o) + int(b)]) for o, b, _need, _flag in self.table_host[:len(self)]]
+
+    def write(self, paths: Sequence[str]) -> None:
+        paths = list(paths)
+        if len(paths) != len(self):
+            raise _err(f"{len(paths)} paths for {len(self)} images")
+        for path, f in zip(paths, self.files()):
+            with open(path, "wb") as fh:
+                fh.write(f)
+
+
+def _batch(images) -> list:
+    if isinstance(images, torch.Tensor):
+        if images.dim() != 4:
+            raise _err(f"a batch tensor is (N, H, W, 3) or (N, H, W, 1), not {tuple(images.shape)}")
+        return [images[i] for i in range(images.shape[0])]
+    return list(images)
+
+
+def encode(images, quality: int = 90, subsampling: str = "4:2:0", bgr: bool = False, capacities=None) -> PackedJpegs:
+    """The batch's files on the device: three launches whatever the number of images and their sizes, no host read."""
+    quality, subsampling, bgr = _options(quality, subsampling, bgr)
+    images = _batch(images)
+    for i, t in enumerate(images):
+        if not isinstance(t, torch.Tensor):
+            raise _err(f"image {i} is not a tensor")
+        _lib.stream_of(t, _WHAT)
+        if not takes(t):
+            raise _err(f"image {i} must be a contiguous, non-empty uint8 tensor shaped (H, W), (H, W, 1) or (H, W, 3); it is "
+                       f"{t.dtype} {tuple(t.shape)}")
+    device = images[0].device if images else torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+    if device is None:
+        raise _err("needs the ROCm GPU ('cuda'); there is no CPU path")
+    return JpegPlan([t.shape for t in images], device, quality, subsampling, bgr, capacities, own_inputs=False).encode(images)
+
+
+def save_jpeg(path: str, tensor, quality: int = 90, subsampling: str = "4:2:0", bgr: bool = False) -> None:
+    """One image.  A uint8 device tensor of one or three channels goes through the kernels; CPU tensors, arrays, other dtypes and
+    other modes go to Pillow, with the same options where it takes them."""
+    quality, subsampling, bgr = _options(quality, subsampling, bgr)
+    if takes(tensor):
+        encode([tensor], quality, subsampling, bgr).write([path])
+        return
+    from PIL import Image
+    arr = tensor.detach().cpu().numpy() if isinstance(tensor, torch.Tensor) else np.asarray(tensor)
+    if arr.ndim == 3 and arr.shape[2] == 1:
+        arr = arr[:, :, 0]
+    if arr.ndim == 3 and arr.shape[2] == 3 and bgr:
+        arr = np.ascontiguousarray(arr[:, :, ::-1])
+    kw = {"subsampling": {"4:4:4": 0, "4:2:0": 2}[subsampling]} if arr.ndim == 3 else {}
+    Image.fromarray(arr).save(path, format="JPEG", quality=quality, optimize=False, restart_marker_rows=1, **kw)
+
+
+def _chunk(name: bytes, body: bytes) -> bytes:
+    return name + struct.pack("<I", len(body)) + body + (b"\0" if len(body) & 1 else b"")
+
+
+def write_avi(path: str, files: Sequence[bytes], fps, width: int, height: int) -> None:
+    """The JPEG files as the frames of a Motion-JPEG AVI (AVI 1.0, one video stream, an idx1 index): RIFF 'AVI ', LIST hdrl (avih,
+    LIST strl (strh 'vids' / 'MJPG', strf: a BITMAPINFOHEADER, 'MJPG', 24 bit)), LIST movi of '00dc' chunks padded to even length,
+    idx1 with offsets counted from the 'movi' name.  A file of more than 2^32 - 1 bytes raises: no OpenDML extension is written."""
+    files = [bytes(f) for f in files]
+    width, height = int(width), int(height)
+    if not files:
+        raise ValueError("write_avi needs at least one frame")
+    if not (1 <= width <= 65535 and 1 <= height <= 65535):
+        raise ValueError(f"a frame of {width} x {height} pixels (1..65535)")
+    for i, f in enumerate(files):
+        if f[:2] != b"\xff\xd8" or f[-2:] != b"\xff\xd9":
+            raise ValueError(f"frame {i} is not a JPEG file")
+    rate = Fraction(fps).limit_denominator(100000)
+    if rate <= 0:
+        raise ValueError(f"fps = {fps!r} must be positive")
+    n, biggest = len(files), max(len(f) for f in files)
+    movi_bytes = 4 + sum(8 + len(f) + (len(f) & 1) for f in files)
+    total = 12 + (8 + 4 + (8 + 56) + (8 + 4 + (8 + 56) + (8 + 40))) + (8 + movi_bytes) + (8 + 16 * n)
+    if total > AVI_MAX_BYTES:
+        raise ValueError(f"the video needs {total} bytes: more than 2^32 - 1 (AVI 1.0, no OpenDML)")
+    us = int(round(1e6 * rate.denominator / rate.numerator))
+    avih = struct.pack("<14I", us, int(biggest * float(rate)) & 0xFFFFFFFF, 0, 0x10, n, 0, 1, biggest, width, height, 0, 0, 0, 0)
+    strh = b"vidsMJPG" + struct.pack("<IHHIIIIIIII4H", 0, 0, 0, 0, rate.denominator, rate.numerator, 0, n, biggest, 0xFFFFFFFF, 0,
+                                     0, 0, width, height)
+    strf = struct.pack("<IiiHH4sIiiII", 40, width, height, 1, 24, b"MJPG", width * height * 3, 0, 0, 0, 0)
+    strl = b"LIST" + struct.pack("<I", 4 + 8 + len(strh) + 8 + len(strf)) + b"strl" + _chunk(b"strh", strh) + _chunk(b"strf", strf)
+    hdrl = b"LIST" + struct.pack("<I", 4 + 8 + len(avih) + len(strl)) + b"hdrl" + _chunk(b"avih", avih) + strl
+    index, at = [], 4
+    for f in files:
+        index.append(b"00dc" + struct.pack("<III", 0x10, at, len(f)))
+        at += 8 + len(f) + (len(f) & 1)
+    with open(path, "wb") as fh:
+        fh.write(b"RIFF" + struct.pack("<I", total - 8) + b"AVI " + hdrl + b"LIST" + struct.pack("<I", movi_bytes) + b"movi")
+        for f in files:
+            fh.write(_chunk(b"00dc", f))
+        fh.write(_chunk(b"idx1", b"".join(index)))
+
+
+def check_options(quality, subsampling, fps) -> None:
+    """What render_video(video="mjpeg") validates before its first launch."""
+    _options(quality, subsampling, True)
+    if not Fraction(fps).limit_denominator(100000) > 0:
+        raise ValueError(f"fps = {fps!r} must be positive")
+
+
+def check_route(video) -> bool:
+    """The `video` keyword of render_video: False for None, True for "mjpeg"."""
+    if video not in (None, "mjpeg"):
+        raise ValueError(f'video must be None or "mjpeg", not {video!r}')
+    return video == "mjpeg"

@@ -10,7 +10,8 @@ The reference leaves the GPU twice per frame (the normalised depth and the clamp
 core and maps it through a float64 RGBA image.  Every pixel is decided from that pixel and two scalars of the image, its minimum
 and one percentile: here a frame is an exact selection (scg_viz_select) and one per-pixel launch (scg_viz_frame), nothing is read
 on the host, and a whole video is ONE copy to the host after the loop.  cv2 and the .mp4 container are not part of this: the
-frames go to two caller-supplied sinks (`cv2.VideoWriter.write` fits them).  CPU tensors raise ScgError."""
+frames go to two caller-supplied sinks (`cv2.VideoWriter.write` fits them), and with video="mjpeg" the two videos are written as
+Motion-JPEG AVI files whose frames are encoded on the GPU (jpeg.py).  CPU tensors raise ScgError."""
 from __future__ import annotations
 
 import os
@@ -157,7 +158,8 @@ VIDEO_KEYS = ("renders", "depth", "depth_color", "frames_bgr", "depth_frames_bgr
 
 
 def render_video(views, gaussians, pipe, background, out_dir=None, name="video", iteration=0, render=_render.render,
-                 frame_sink=None, depth_sink=None, lut=TURBO, percentile: float = 98.0, png="pillow"):
+                 frame_sink=None, depth_sink=None, lut=TURBO, percentile: float = 98.0, png="pillow", video=None, fps=30,
+                 jpeg_quality: int = 90, jpeg_subsampling: str = "4:2:0"):
     """render_video.py:129-152 over `views` under torch.no_grad().  Per frame: render, the depth's range, the select and the frame
     kernel — at most eight launches behind the rasteriser's and no host read —, written into buffers allocated before the loop;
     after the loop ONE copy to the host.  Returns a dict of uint8 numpy arrays over the F frames:
@@ -169,11 +171,18 @@ def render_video(views, gaussians, pipe, background, out_dir=None, name="video",
     With `out_dir` the three PNGs per frame are written under <out_dir>/<name>/ours_<iteration>/{renders,depth}/.  `frame_sink` and
     `depth_sink` are called with each frame's B, G, R array in order (cv2.VideoWriter.write fits them); no video library is
     imported and no .mp4 is written here.  All views must have one size, as the reference's single VideoWriter size implies.
+    video="mjpeg" (with `out_dir`) encodes frames_bgr and depth_frames_bgr as JPEG files on the GPU in one batch behind the loop
+    (jpeg.py, bgr=True, `jpeg_quality`, `jpeg_subsampling`; two more host reads) and writes them as the frames of
+    <out_dir>/<name>/ours_<iteration>/render_video.avi and depth_video.avi at `fps`; the default, None, writes no video.
     png="device" encodes the 3 F files on the GPU in one batch behind the loop (png.py; two more host reads) and writes the same
     tree; every file decodes to the pixels that the default, "pillow", writes."""
     from . import png as _png
+    from . import jpeg as _jpeg
     from .evaluate import _save_png
     on_device = _png.check_route(png)
+    mjpeg = _jpeg.check_route(video) and out_dir is not None
+    if video is not None:
+        _jpeg.check_options(jpeg_quality, jpeg_subsampling, fps)      # before the first launch
     views = list(views)
     if not views:
         raise ValueError("render_video needs at least one view")
@@ -200,6 +209,10 @@ def render_video(views, gaussians, pipe, background, out_dir=None, name="video",
         packed = None
         if out_dir is not None and on_device:
             packed = _png.encode([buf[k][idx] for idx in range(F) for k in ("renders", "depth", "depth_color")])
+        movie = None
+        if mjpeg:
+            movie = _jpeg.encode([buf[k][idx] for k in ("frames_bgr", "depth_frames_bgr") for idx in range(F)], jpeg_quality,
+                                 jpeg_subsampling, bgr=True)
         host = flat.cpu().numpy()          # the video's one host read
     out = {k: host[o:o + s].reshape((F, H, W) if k == "depth" else (F, H, W, 3)) for k, o, s in zip(VIDEO_KEYS, starts, sizes)}
     if out_dir is not None:
@@ -213,6 +226,10 @@ def render_video(views, gaussians, pipe, background, out_dir=None, name="video",
             _save_png(os.path.join(base, "renders", f"{idx:05d}.png"), out["renders"][idx])
             _save_png(os.path.join(base, "depth", f"{idx:05d}.png"), out["depth"][idx])
             _save_png(os.path.join(base, "depth", f"color_{idx:05d}.png"), out["depth_color"][idx])
+        if movie is not None:
+            files = movie.files()
+            _jpeg.write_avi(os.path.join(base, "render_video.avi"), files[:F], fps, W, H)
+            _jpeg.write_avi(os.path.join(base, "depth_video.avi"), files[F:], fps, W, H)
     for idx in range(F):
         if frame_sink is not None:
             frame_sink(out["frames_bgr"][idx])
