@@ -1,10 +1,10 @@
-/* scg_jpeg.h — C ABI of libscg_jpg.so: baseline JPEG files packed on the GPU (csrc/jpg/jpegpack.hip, gfx950).  The frames of
+/* scg_jpeg.h — C ABI of libscg_jpg.so: baseline JPEG files packed on the GPU (csrc/jpegpack.hip, gfx950).  The frames of
  * render_video already lie on the device as uint8; here they become complete JPEG files — the frames of a Motion-JPEG video — in
  * three launches per batch, whatever the number of images and their sizes.  The bytes are libjpeg's: Pillow's
  * Image.save(format="JPEG", quality=q, subsampling=s, optimize=False, restart_marker_rows=1) writes the same file.
  *
- * An eighth library next to libscg_raster.so and the six side libraries; its header lives with its source, outside include/.  Its
- * entry points are declared here and in no other header.  Conventions as there: plain C, `void* stream` is a hipStream_t (NULL =
+ * An eighth library next to libscg_raster.so and the six other side libraries.  Its
+ * entry points are declared here and in no other header. Conventions as there: plain C, `void* stream` is a hipStream_t (NULL =
  * the default stream), every launch is asynchronous on it, return value 0 = ok, < 0 = invalid argument (the SCG_E_* codes of
  * scg_raster.h), > 0 = a hipError_t; the message of the last failure of the calling thread is scg_jpg_last_error().  Every argument
  * is validated before anything touches a device.  The caller owns all buffers; nothing is allocated, nothing is read back.  No
@@ -69,7 +69,7 @@
 #ifndef SCG_JPEG_H
 #define SCG_JPEG_H
 
-#include "../../../include/scg_raster.h"
+#include "../scg_raster.h"
 
 #define SCG_JPG_ABI_VERSION 1
 #define SCG_JPEG_THREADS 256          /* threads of a workgroup in all three kernels: blocks per round */

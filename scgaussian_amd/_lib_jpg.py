@@ -1,8 +1,8 @@
-"""ctypes binding of libscg_jpg.so (csrc/jpg/scg_jpeg.h): baseline JPEG files packed on the GPU.
+"""ctypes binding of libscg_jpg.so (include/jpg/scg_jpeg.h): baseline JPEG files packed on the GPU.
 
-An eighth library next to libscg_raster.so with a version and an error string of its own; its header lives with its source
-(build.DETACHED_LIBRARIES).  As there: a missing library raises, there is no quiet stand-in for a kernel.  tests/test_jpeg_cpu.py
-holds SYMBOLS, the structs and the constants to the header's text.
+An eighth library next to libscg_raster.so with a version and an error string of its own (build.SIDE_LIBRARIES["jpg"]).  As there:
+a missing library raises, there is no quiet stand-in for a kernel.  tests/test_jpeg_cpu.py holds SYMBOLS, the structs and the
+constants to the header's text.
 """
 from __future__ import annotations
 
@@ -15,7 +15,6 @@ from ._lib import open_library, raise_last_error
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libscg_jpg.so")
-HEADER_PATH = os.path.join(_HERE, "csrc", "jpg", "scg_jpeg.h")
 
 # the header's integer #defines under their own names minus "SCG_"
 JPG_ABI_VERSION = ABI_VERSION = 1
@@ -24,7 +23,7 @@ JPEG_444, JPEG_420 = 0, 2
 
 
 class ScgJpegLayout(C.Structure):
-    """Sizes of a batch and the regions of its workspace (csrc/jpg/scg_jpeg.h ScgJpegLayout)."""
+    """Sizes of a batch and the regions of its workspace (include/jpg/scg_jpeg.h ScgJpegLayout)."""
     _fields_ = [(n, C.c_uint64) for n in ("images", "segments", "headers_bytes", "capacity", "workspace_bytes", "base_offset",
                                           "scan_offset", "table_offset", "table_bytes")]
 

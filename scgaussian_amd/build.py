@@ -1,5 +1,5 @@
 """Build the HIP libraries in-tree with hipcc for gfx950: libscg_raster.so (SOURCES) and, behind it, one side library per entry
-of SIDE_LIBRARIES, each with a header directory, an ABI version and an error string of its own, then the DETACHED_LIBRARIES.
+of SIDE_LIBRARIES, each with a header directory, an ABI version and an error string of its own.
 
     python -m scgaussian_amd.build [--force] [--verbose]
 
@@ -9,7 +9,7 @@ of SIDE_LIBRARIES, each with a header directory, an ABI version and an error str
     libscg_vw.so    include/vw    the virtual-view warp loss and the depth smoothness, forward and backward
     libscg_lp.so    include/lp    the LPIPS metric (VGG16 on the fp32 matrix pipe)
     libscg_png.so   include/png   PNG files' zlib streams
-    libscg_jpg.so   csrc/jpg      JPEG files, the frames of a Motion-JPEG video (DETACHED_LIBRARIES: header and source in one directory)
+    libscg_jpg.so   include/jpg   JPEG files, the frames of a Motion-JPEG video
 
 hipcc cross-compiles without a GPU; the libraries are git-ignored.  A source whose results are held to another
 implementation's bits is compiled with -ffp-contract=off, one rounding per operation: the comment next to each such source in the
@@ -78,31 +78,15 @@ SIDE_LIBRARIES = {
     "png": ("png", {    # include/png/scg_png.h
         "pngpack.hip": [],                        # integer arithmetic only
     }),
-}
-
-
-# The detached libraries: short name -> (directory under csrc/ that holds BOTH the header and the sources, {source: extra flags}).
-# Built and loaded like a side library; the header is not under include/ and is no part of HEADERS: the objects' stamps cover the
-# directory's own headers next to HEADERS.
-DETACHED_LIBRARIES = {
-    "jpg": ("jpg", {    # csrc/jpg/scg_jpeg.h
+    "jpg": ("jpg", {    # include/jpg/scg_jpeg.h
         "jpegpack.hip": ["-ffp-contract=off"],    # integer arithmetic only; the flag says that the bytes are held to libjpeg's
     }),
 }
 
 
 def side_library(key: str):
-    """(path of libscg_<key>.so, its {source: extra flags}) of one entry of SIDE_LIBRARIES or DETACHED_LIBRARIES; the sources of a
-    detached library are named relative to csrc/.  An unknown key raises KeyError."""
-    if key in DETACHED_LIBRARIES:
-        d, sources = DETACHED_LIBRARIES[key]
-        return os.path.join(HERE, f"libscg_{key}.so"), {os.path.join(d, src): extra for src, extra in sources.items()}
+    """(path of libscg_<key>.so, its {source: extra flags}) of one entry of SIDE_LIBRARIES.  An unknown key raises KeyError."""
     return os.path.join(HERE, f"libscg_{key}.so"), SIDE_LIBRARIES[key][1]
-
-
-def detached_headers(key: str):
-    """The headers in a detached library's own directory."""
-    return _h(CSRC, DETACHED_LIBRARIES[key][0])
 
 
 def _h(*parts):
@@ -151,11 +135,11 @@ def build_probe_timeline_variant(verbose: bool = False) -> str:
     return build(verbose=verbose, tag=PROBE_TIMELINE_TAG, defines=("SCG_PROBE_TIMELINE",), only=PROBE_TIMELINE_SOURCES)
 
 
-def _compile(hipcc: str, src: str, extra, obj: str, force: bool, verbose: bool, more_headers=()) -> bool:
+def _compile(hipcc: str, src: str, extra, obj: str, force: bool, verbose: bool) -> bool:
     """Compile csrc/<src> to `obj` unless its stamp says that source, headers and flags are the ones it was built from."""
     src_path = os.path.join(CSRC, src)
     stamp = obj + ".sha"
-    dig = _digest([src_path] + HEADERS + list(more_headers), " ".join(COMMON + extra))
+    dig = _digest([src_path] + HEADERS, " ".join(COMMON + extra))
     if not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == dig:
         return False
     cmd = [hipcc] + COMMON + extra + ["-c", src_path, "-o", obj]
@@ -175,16 +159,15 @@ def _link(hipcc: str, lib_path: str, objs, verbose: bool) -> None:
 
 
 def build_side(key: str, force: bool = False, verbose: bool = False) -> str:
-    """libscg_<key>.so from its entry of SIDE_LIBRARIES or DETACHED_LIBRARIES."""
+    """libscg_<key>.so from its entry of SIDE_LIBRARIES."""
     lib_path, sources = side_library(key)
-    more = detached_headers(key) if key in DETACHED_LIBRARIES else ()
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
     objs, rebuilt = [], False
     for src, extra in sources.items():
         obj = os.path.join(OBJ_DIR, os.path.basename(src).replace(".hip", ".o"))
         objs.append(obj)
-        rebuilt |= _compile(hipcc, src, list(extra), obj, force, verbose, more)
+        rebuilt |= _compile(hipcc, src, list(extra), obj, force, verbose)
     if rebuilt or force or not os.path.exists(lib_path):
         _link(hipcc, lib_path, objs, verbose)
     return lib_path
@@ -209,7 +192,7 @@ def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(),
     if rebuilt or force or not os.path.exists(lib_path):
         _link(hipcc, lib_path, objs, verbose)
     if not tag:
-        for key in list(SIDE_LIBRARIES) + list(DETACHED_LIBRARIES):
+        for key in SIDE_LIBRARIES:
             build_side(key, force=force, verbose=verbose)
     return lib_path
 

@@ -1,4 +1,4 @@
-// jpegpack.hip — libscg_jpg.so: baseline JPEG files packed on the GPU (csrc/jpg/scg_jpeg.h states the stream; it is the contract,
+// jpegpack.hip — libscg_jpg.so: baseline JPEG files packed on the GPU (include/jpg/scg_jpeg.h states the stream; it is the contract,
 // and tests/jpeg_refs.py restates it in numpy).
 //
 // A JPEG is a per-block transform, a bit count, a scan and a bit pack; with one restart interval per MCU row nothing but the byte
@@ -18,10 +18,11 @@
 //                       it behind a scan of the FF counts, then the marker; the first segment of an image copies its header.
 //
 // No workgroup waits for another, nothing is allocated, nothing is read back; the same input gives the same bytes.
-#include "scg_jpeg.h"
-#include "../compact.h"
-#include "../host_align.h"
-#include "../host_error.h"
+#include "../../include/jpg/scg_jpeg.h"
+#include "bitwindow.h"
+#include "compact.h"
+#include "host_align.h"
+#include "host_error.h"
 
 #include <map>
 #include <tuple>
@@ -262,11 +263,8 @@ struct PutBits {
     uint32_t* win;
     uint32_t wlo, at;
     __device__ __forceinline__ void put(uint32_t val, int n) {
-        const uint32_t w = at >> 5;
         const uint64_t v = (uint64_t)val << (64 - (int)(at & 31u) - n);
-        const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
-        if (hi && w >= wlo && w < wlo + kWinWords) atomicOr(&win[w - wlo], hi);
-        if (lo && w + 1u >= wlo && w + 1u < wlo + kWinWords) atomicOr(&win[w + 1u - wlo], lo);
+        window_or(win, wlo, wlo + kWinWords, at >> 5, (uint32_t)(v >> 32), (uint32_t)v);
         at += (uint32_t)n;
     }
 };
@@ -302,7 +300,7 @@ __device__ uint32_t walk_segment(const JpegArgs& a, const ScgJpegImage& im, int 
     __shared__ uint32_t s_wave[kT / kWave];
     __shared__ uint32_t s_ff[kT / kWave];
 
-    const int t = threadIdx.x, lane = lane_id(), w = wave_id();
+    const int t = threadIdx.x;
     Geometry g;
     g.px.src = reinterpret_cast<const uint8_t*>(im.src);
     g.px.H = im.H;
@@ -331,20 +329,10 @@ __device__ uint32_t walk_segment(const JpegArgs& a, const ScgJpegImage& im, int 
         const int k0 = t * kMine, k1 = min(k0 + kMine, (int)nb);
         uint32_t ff = 0u;
         for (int k = k0; k < k1; ++k) ff += window_byte(s_win, k) == 255u;
-        uint32_t inc = ff;
-        for (int o = 1; o < kWave; o <<= 1) {
-            const uint32_t y = (uint32_t)__shfl_up((int)inc, o, kWave);
-            if (lane >= o) inc += y;
-        }
-        if (lane == kWave - 1) s_ff[w] = inc;
-        __syncthreads();
-        uint32_t before = 0u, all = 0u;
-        for (int j = 0; j < kT / kWave; ++j) {
-            if (j < w) before += s_ff[j];
-            all += s_ff[j];
-        }
+        uint32_t before, all;
+        block_exclusive_sum<kT>(ff, s_ff, before, all);
         if (kWrite) {
-            uint32_t pos = cur * (uint32_t)kWinBytes + (uint32_t)k0 + stuffed + before + inc - ff;
+            uint32_t pos = cur * (uint32_t)kWinBytes + (uint32_t)k0 + stuffed + before;
             for (int k = k0; k < k1; ++k) {
                 const uint32_t b = window_byte(s_win, k);
                 if (pos < limit) dst[pos] = (uint8_t)b;
@@ -386,19 +374,9 @@ __device__ uint32_t walk_segment(const JpegArgs& a, const ScgJpegImage& im, int 
             diff = coef[0] - (k.pred ? s_dc[kHist + t - k.pred] : 0);
             for_each_code(coef, diff, dc_code, ac_code, cb);
         }
-        uint32_t inc = cb.bits;                                      // the workgroup-exclusive scan of the blocks' bit counts
-        for (int o = 1; o < kWave; o <<= 1) {
-            const uint32_t y = (uint32_t)__shfl_up((int)inc, o, kWave);
-            if (lane >= o) inc += y;
-        }
-        if (lane == kWave - 1) s_wave[w] = inc;
-        __syncthreads();
-        uint32_t before = 0u, R = 0u;
-        for (int j = 0; j < kT / kWave; ++j) {
-            if (j < w) before += s_wave[j];
-            R += s_wave[j];
-        }
-        const uint32_t my_lo = P + before + inc - cb.bits, my_hi = my_lo + cb.bits;
+        uint32_t before, R;                                          // the blocks' bit counts in front of this one, and the round's
+        block_exclusive_sum<kT>(cb.bits, s_wave, before, R);         // (s_wave, not s_ff: no barrier between this scan and a flush's)
+        const uint32_t my_lo = P + before, my_hi = my_lo + cb.bits;
         // the windows this round's bits [P, P + R) touch, in order; R > 0: a block has at least four bits
         for (uint32_t j = P / kWinBits; j <= (P + R - 1u) / kWinBits; ++j) {
             if (j != cur) {                                          // `cur` is full
@@ -688,15 +666,9 @@ int scg_jpeg_encode(const ScgJpegEncode* p, void* out, size_t out_bytes, void* w
     l.headers_bytes = p->headers_bytes;
     l.capacity = capacity;
     place(&l);
-    if (!out) return g_err.fail(SCG_E_NULL, "%s: out is NULL", who);
-    if (out_bytes < l.capacity) return g_err.fail(SCG_E_SCRATCH, "%s: out of %zu bytes < %llu", who, out_bytes, (unsigned long long)l.capacity);
-    if (reinterpret_cast<uintptr_t>(out) % 16) return g_err.fail(SCG_E_ALIGN, "%s: out not 16-byte aligned", who);
-    if (!workspace) return g_err.fail(SCG_E_NULL, "%s: workspace is NULL", who);
-    if (workspace_bytes < l.workspace_bytes)
-        return g_err.fail(SCG_E_SCRATCH, "%s: workspace of %zu bytes < %llu", who, workspace_bytes, (unsigned long long)l.workspace_bytes);
-    if (reinterpret_cast<uintptr_t>(workspace) % 16) return g_err.fail(SCG_E_ALIGN, "%s: workspace not 16-byte aligned", who);
-    if (reinterpret_cast<uintptr_t>(p->images_dev) % 8 || reinterpret_cast<uintptr_t>(p->segments_dev) % 4)
-        return g_err.fail(SCG_E_ALIGN, "%s: a device table is not aligned to its records", who);
+    if (int rc = g_err.check_batch_buffers(who, out, out_bytes, l.capacity, workspace, workspace_bytes, l.workspace_bytes, p->images_dev, 8,
+                                           p->segments_dev, 4))
+        return rc;
 
     JpegArgs a;
     a.images = p->images;

@@ -19,6 +19,7 @@
 //
 // No workgroup waits for another, nothing is allocated, nothing is read back; the same input gives the same bytes.
 #include "../../include/png/scg_png.h"
+#include "bitwindow.h"
 #include "compact.h"
 #include "host_align.h"
 #include "host_error.h"
@@ -420,10 +421,8 @@ struct Window {
     uint32_t* img;
     uint32_t wlo, whi;          // the words of the block that the LDS image holds
     __device__ __forceinline__ void put(uint32_t bitpos, uint32_t val) const {         // val: at most 21 bits, the first one lowest
-        const uint32_t w = bitpos >> 5;
         const uint64_t v = (uint64_t)val << (bitpos & 31u);
-        if (w >= wlo && w < whi && (uint32_t)v) atomicOr(&img[w - wlo], (uint32_t)v);
-        if ((uint32_t)(v >> 32) && w + 1u >= wlo && w + 1u < whi) atomicOr(&img[w + 1u - wlo], (uint32_t)(v >> 32));
+        window_or(img, wlo, whi, bitpos >> 5, (uint32_t)v, (uint32_t)(v >> 32));
     }
 };
 
@@ -479,7 +478,7 @@ __global__ __launch_bounds__(kT) void png_encode_kernel(PngArgs a) {
     __shared__ uint32_t s_wave[kT / kWave];
     __shared__ int s_scan[8];
 
-    const int c = blockIdx.x, t = threadIdx.x, lane = lane_id(), w = wave_id();
+    const int c = blockIdx.x, t = threadIdx.x;
     if (c >= a.chunks) return;
     const ScgPngChunk ck = a.chunk[c];
     if (ck.image < 0 || ck.image >= a.images) return;
@@ -535,19 +534,9 @@ __global__ __launch_bounds__(kT) void png_encode_kernel(PngArgs a) {
 
     BitTokens bt{s_code, 0u};
     for_each_token(g, s_data, bt);
-    uint32_t inc = bt.bits;                                          // the workgroup-exclusive scan of the threads' bit counts
-    for (int o = 1; o < kWave; o <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)inc, o, kWave);
-        if (lane >= o) inc += y;
-    }
-    if (lane == kWave - 1) s_wave[w] = inc;
-    __syncthreads();
-    uint32_t before = 0u, all = 0u;
-    for (int j = 0; j < kT / kWave; ++j) {
-        if (j < w) before += s_wave[j];
-        all += s_wave[j];
-    }
-    const uint32_t my_lo = SCG_PNG_HEADER_BITS + before + inc - bt.bits, my_hi = my_lo + bt.bits;
+    uint32_t before, all;                                            // the threads' bit counts in front of this one, and all of them
+    block_exclusive_sum<kT>(bt.bits, s_wave, before, all);
+    const uint32_t my_lo = SCG_PNG_HEADER_BITS + before, my_hi = my_lo + bt.bits;
     const uint32_t eob_at = SCG_PNG_HEADER_BITS + all;
     const uint32_t end_bits = eob_at + (s_code[kEob] >> 16);
     const uint32_t tail = (end_bits + 3u + 7u) >> 3;                 // non-final: the empty stored block's LEN begins here
@@ -704,15 +693,9 @@ int scg_png_encode(const ScgPngEncode* p, void* out, size_t out_bytes, void* wor
         l.capacity = capacity;
         place(&l);
     }
-    if (!out) return g_err.fail(SCG_E_NULL, "%s: out is NULL", who);
-    if (out_bytes < l.capacity) return g_err.fail(SCG_E_SCRATCH, "%s: out of %zu bytes < %llu", who, out_bytes, (unsigned long long)l.capacity);
-    if (reinterpret_cast<uintptr_t>(out) % 16) return g_err.fail(SCG_E_ALIGN, "%s: out not 16-byte aligned", who);
-    if (!workspace) return g_err.fail(SCG_E_NULL, "%s: workspace is NULL", who);
-    if (workspace_bytes < l.workspace_bytes)
-        return g_err.fail(SCG_E_SCRATCH, "%s: workspace of %zu bytes < %llu", who, workspace_bytes, (unsigned long long)l.workspace_bytes);
-    if (reinterpret_cast<uintptr_t>(workspace) % 16) return g_err.fail(SCG_E_ALIGN, "%s: workspace not 16-byte aligned", who);
-    if (reinterpret_cast<uintptr_t>(p->images_dev) % 8 || reinterpret_cast<uintptr_t>(p->chunks_dev) % 4)
-        return g_err.fail(SCG_E_ALIGN, "%s: a device table is not aligned to its records", who);
+    if (int rc = g_err.check_batch_buffers(who, out, out_bytes, l.capacity, workspace, workspace_bytes, l.workspace_bytes, p->images_dev, 8,
+                                           p->chunks_dev, 4))
+        return rc;
 
     PngArgs a;
     a.images = p->images;

@@ -1,4 +1,4 @@
-"""JPEG files and Motion-JPEG video from uint8 device tensors, host side (libscg_jpg.so, csrc/jpg/scg_jpeg.h states the stream).
+"""JPEG files and Motion-JPEG video from uint8 device tensors, host side (libscg_jpg.so, include/jpg/scg_jpeg.h states the stream).
 
     packed = jpeg.encode([img0, img1, ...], quality=90, subsampling="4:2:0", bgr=False)     three launches, no host read
     packed.to_host()                              TWO host reads: the table, then exactly `total` bytes into pinned memory
@@ -17,12 +17,13 @@ from __future__ import annotations
 import ctypes as C
 import struct
 from fractions import Fraction
-from typing import List, Optional, Sequence
+from typing import List, Sequence
 
 import numpy as np
 import torch
 
-from . import _lib, _lib_jpg
+from . import _filebatch, _lib, _lib_jpg
+from ._filebatch import takes        # noqa: F401  (jpeg.takes)
 from ._lib_jpg import check
 
 SUBSAMPLINGS = {"4:4:4": _lib_jpg.JPEG_444, "4:2:0": _lib_jpg.JPEG_420}
@@ -38,15 +39,6 @@ def _err(msg: str) -> _lib.ScgError:
     return _lib.ScgError(f"{_WHAT}: {msg}")
 
 
-def _hwc(shape) -> tuple:
-    shape = tuple(int(s) for s in shape)
-    if len(shape) == 2:
-        shape = shape + (1,)
-    if len(shape) != 3 or shape[2] not in (1, 3):
-        raise _err(f"an image is (H, W), (H, W, 1) or (H, W, 3), not {shape}")
-    return shape
-
-
 def _options(quality, subsampling, bgr):
     if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
         raise _err(f"quality {quality!r} is not an integer in 1..100")
@@ -55,16 +47,10 @@ def _options(quality, subsampling, bgr):
     return int(quality), str(subsampling), bool(bgr)
 
 
-def takes(t) -> bool:
-    """Is `t` an image the kernels take as it is?  (What they do not take goes to Pillow in save_jpeg.)"""
-    return (isinstance(t, torch.Tensor) and t.device.type == "cuda" and t.dtype == torch.uint8 and t.is_contiguous() and
-            (t.dim() == 2 or (t.dim() == 3 and t.shape[2] in (1, 3))) and t.numel() > 0)
-
-
 def layout(shapes: Sequence, quality: int = 90, subsampling: str = "4:2:0", capacities=None):
     """scg_jpeg_layout on the host alone (no GPU is touched): (ScgJpegLayout, image records, segment records, header templates)."""
     quality, subsampling, _ = _options(quality, subsampling, False)
-    shapes = [_hwc(s) for s in shapes]
+    shapes = [_filebatch.hwc(s, _err) for s in shapes]
     n = len(shapes)
     lay = _lib_jpg.ScgJpegLayout()
     images = np.zeros(n, dtype=_IMAGE_DTYPE)
@@ -90,126 +76,51 @@ def layout(shapes: Sequence, quality: int = 90, subsampling: str = "4:2:0", capa
     return lay, images, segments, headers
 
 
-class JpegPlan:
-    """Everything of a batch that depends on its shapes and options alone: the layout, the image, segment and header tables on the
-    device, the workspace and the output buffer.  encode() on it allocates nothing and reads nothing back, so it can be captured in
-    a graph: `inputs` are the plan's own image tensors (views of one arena), to be rewritten in place between replays."""
+class JpegPlan(_filebatch.FilePlan):
+    """The plan of a batch of JPEG files (FilePlan): the image, segment and header tables on the device, the workspace, the output
+    buffer with every file's capacity."""
+
+    LIB, WHAT, ENTRY, ENCODE, COLUMNS = _lib_jpg, _WHAT, "scg_jpeg_encode", _lib_jpg.ScgJpegEncode, 4
 
     def __init__(self, shapes: Sequence, device="cuda", quality: int = 90, subsampling: str = "4:2:0", bgr: bool = False,
                  capacities=None, own_inputs: bool = True):
-        self.device = torch.device(device)
-        _lib.stream_of(self.device, "JpegPlan")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        super().__init__(shapes, device, own_inputs, quality=quality, subsampling=subsampling, bgr=bgr, capacities=capacities)
+
+    def _configure(self, quality, subsampling, bgr, capacities) -> None:
         self.quality, self.subsampling, self.bgr = _options(quality, subsampling, bgr)
-        self.shapes = [_hwc(s) for s in shapes]
-        self.layout, self.images_host, segments, headers = layout(self.shapes, self.quality, self.subsampling, capacities)
-        self.inputs: List[torch.Tensor] = []
-        self._src = None
-        n = len(self.shapes)
-        if n == 0:
-            return
-        with torch.cuda.device(self.device):
-            self.segments_dev = torch.from_numpy(segments.view(np.uint8).reshape(-1).copy()).to(self.device)
-            self.headers_dev = torch.from_numpy(headers.copy()).to(self.device)
-            self.images_dev = torch.empty(n * _IMAGE_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
-            self.workspace = torch.empty(int(self.layout.workspace_bytes), dtype=torch.uint8, device=self.device)
-            self.out = torch.empty(int(self.layout.capacity), dtype=torch.uint8, device=self.device)
-            if own_inputs:
-                sizes = [h * w * c for h, w, c in self.shapes]
-                starts = np.concatenate([[0], np.cumsum([(s + 15) // 16 * 16 for s in sizes])])
-                self.arena = torch.zeros(int(starts[-1]), dtype=torch.uint8, device=self.device)
-                self.inputs = [self.arena[int(o):int(o) + s].view(shape) for o, s, shape in zip(starts, sizes, self.shapes)]
-                self._bind(self.inputs)
-        t = self.layout.table_offset
-        self.table = self.workspace[t:t + self.layout.table_bytes].view(torch.int32)
+        self._capacities = capacities
 
-    def _bind(self, images) -> None:
-        """Put the images' addresses into the image table; upload it when they changed (a host-to-device copy, never a read)."""
-        src = [int(t.data_ptr()) for t in images]
-        if src == self._src:
-            return
-        if torch.cuda.is_current_stream_capturing():
-            raise _err("a captured call must use the tensors of the call before it (JpegPlan.inputs): the image table cannot be "
-                       "uploaded inside a capture")
-        self.images_host["src"] = src
-        self.images_dev.copy_(torch.from_numpy(self.images_host.view(np.uint8).reshape(-1).copy()))
-        self._src = src
+    def _lay_out(self):
+        lay, images, segments, headers = layout(self.shapes, self.quality, self.subsampling, self._capacities)
+        return lay, images, {"segments_dev": segments, "headers_dev": headers}
 
-    def args(self) -> _lib_jpg.ScgJpegEncode:
-        """The ScgJpegEncode of this plan."""
-        a = _lib_jpg.ScgJpegEncode()
-        a.struct_bytes = C.sizeof(_lib_jpg.ScgJpegEncode)
-        a.images, a.quality, a.subsampling, a.bgr = len(self.shapes), self.quality, SUBSAMPLINGS[self.subsampling], int(self.bgr)
+    def _fill(self, a) -> None:
+        a.quality, a.subsampling, a.bgr = self.quality, SUBSAMPLINGS[self.subsampling], int(self.bgr)
         a.headers_bytes = int(self.layout.headers_bytes)
-        a.images_host = self.images_host.ctypes.data
-        a.images_dev, a.segments_dev, a.headers_dev = self.images_dev.data_ptr(), self.segments_dev.data_ptr(), self.headers_dev.data_ptr()
-        return a
-
-    @torch.no_grad()
-    def encode(self, images: Optional[Sequence[torch.Tensor]] = None) -> "PackedJpegs":
-        """Three launches on the current stream.  images: None for the plan's own inputs, or tensors of the plan's shapes."""
-        if not self.shapes:
-            return PackedJpegs(self)
-        if images is None:
-            images = self.inputs
-            if not images:
-                raise _err("the plan has no inputs of its own (own_inputs=False): pass the images")
-        images = list(images)
-        if len(images) != len(self.shapes):
-            raise _err(f"{len(images)} images for a plan of {len(self.shapes)}")
-        for i, (t, shape) in enumerate(zip(images, self.shapes)):
-            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.uint8 or not t.is_contiguous() or \
-                    _hwc(t.shape) != shape:
-                raise _err(f"image {i} must be a contiguous uint8 tensor of shape {shape} on {self.device}")
-        stream = _lib.stream_of(self.out, _WHAT)
-        with torch.cuda.device(self.device):
-            self._bind(images)
-            a = self.args()
-            check(_lib_jpg.load().scg_jpeg_encode(C.byref(a), self.out.data_ptr(), self.out.numel(), self.workspace.data_ptr(),
-                                                  self.workspace.numel(), stream), "scg_jpeg_encode")
-        return PackedJpegs(self, keep=images)
+        a.segments_dev, a.headers_dev = self.segments_dev.data_ptr(), self.headers_dev.data_ptr()
 
 
-class PackedJpegs:
-    """The files of a batch in the plan's output buffer, each at a multiple of 16 bytes, and the table that says where."""
+class PackedJpegs(_filebatch.PackedFiles):
+    """The files of a batch in the plan's output buffer (PackedFiles; the table's row: offset, bytes, need, overflow)."""
 
     def __init__(self, plan: JpegPlan, keep=None):
-        self.plan, self._keep = plan, keep
-        self.table_host: Optional[np.ndarray] = None      # (images + 1, 4) uint32: offset, bytes, need, overflow
-        self.host: Optional[torch.Tensor] = None
+        super().__init__(plan, keep)
         self.retried = False
-
-    def __len__(self):
-        return len(self.plan.shapes)
 
     def to_host(self, retry: bool = True) -> "PackedJpegs":
         """The batch's TWO host reads: the table, then exactly `total` bytes of the buffer into pinned memory.  When the table flags
         a file that did not fit its capacity and `retry` holds, the batch is encoded once more with what every file needs (and read
         again); without `retry` the flagged files stay empty."""
-        n = len(self)
-        if self.host is not None or n == 0:
-            if n == 0 and self.table_host is None:
-                self.table_host = np.zeros((1, 4), dtype=np.uint32)
+        if not self._read_table():
             return self
-        plan = self.plan
-        stream = torch.cuda.current_stream(plan.device)
-        table = torch.empty((n + 1, 4), dtype=torch.int32, pin_memory=True)
-        table.copy_(plan.table.view(n + 1, 4), non_blocking=True)
-        stream.synchronize()
-        self.table_host = table.numpy().view(np.uint32)
-        total = int(self.table_host[n, 0])
-        if int(self.table_host[n, 1]) != n or total > plan.out.numel():
-            raise _err(f"the table names {int(self.table_host[n, 1])} images and {total} bytes: not this batch's")
+        n, plan = len(self), self.plan
         if retry and int(self.table_host[n, 2]) and not self.retried:
             need = np.maximum(self.table_host[:n, 2].astype(np.int64), plan.images_host["capacity"].astype(np.int64))
             again = JpegPlan(plan.shapes, plan.device, plan.quality, plan.subsampling, plan.bgr, capacities=need, own_inputs=False)
             self.plan = again.encode(self._keep).plan
             self.retried = True
             return self.to_host(retry=False)
-        self.host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-        self.host.copy_(plan.out[:total], non_blocking=True)
-        stream.synchronize()
+        self._read_files()
         return self
 
     @property
@@ -227,12 +138,12 @@ class PackedJpegs:
         return [bytes(data[int(o):int(o) + int(b)]) for o, b, _need, _flag in self.table_host[:len(self)]]
 
     def write(self, paths: Sequence[str]) -> None:
-        paths = list(paths)
-        if len(paths) != len(self):
-            raise _err(f"{len(paths)} paths for {len(self)} images")
-        for path, f in zip(paths, self.files()):
+        for path, f in zip(self._paths(paths), self.files()):
             with open(path, "wb") as fh:
                 fh.write(f)
+
+
+JpegPlan.PACKED = PackedJpegs
 
 
 def _batch(images) -> list:
@@ -246,18 +157,7 @@ def _batch(images) -> list:
 def encode(images, quality: int = 90, subsampling: str = "4:2:0", bgr: bool = False, capacities=None) -> PackedJpegs:
     """The batch's files on the device: three launches whatever the number of images and their sizes, no host read."""
     quality, subsampling, bgr = _options(quality, subsampling, bgr)
-    images = _batch(images)
-    for i, t in enumerate(images):
-        if not isinstance(t, torch.Tensor):
-            raise _err(f"image {i} is not a tensor")
-        _lib.stream_of(t, _WHAT)
-        if not takes(t):
-            raise _err(f"image {i} must be a contiguous, non-empty uint8 tensor shaped (H, W), (H, W, 1) or (H, W, 3); it is "
-                       f"{t.dtype} {tuple(t.shape)}")
-    device = images[0].device if images else torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
-    if device is None:
-        raise _err("needs the ROCm GPU ('cuda'); there is no CPU path")
-    return JpegPlan([t.shape for t in images], device, quality, subsampling, bgr, capacities, own_inputs=False).encode(images)
+    return _filebatch.encode(_batch(images), JpegPlan, quality=quality, subsampling=subsampling, bgr=bgr, capacities=capacities)
 
 
 def save_jpeg(path: str, tensor, quality: int = 90, subsampling: str = "4:2:0", bgr: bool = False) -> None:

@@ -6,13 +6,14 @@ import re
 import subprocess
 import sys
 
-from .build import COMMON, CSRC, SOURCES, _hipcc
+from .build import COMMON, CSRC, SIDE_LIBRARIES, SOURCES, _hipcc, side_library
 import os
 
 
 def report():
     rows = []
-    for src, extra in SOURCES.items():
+    tables = [SOURCES] + [side_library(key)[1] for key in SIDE_LIBRARIES]
+    for src, extra in ((s, e) for table in tables for s, e in table.items()):
         if src == "api.hip":
             continue
         cmd = [_hipcc()] + COMMON + extra + ["-c", os.path.join(CSRC, src), "-o", "/tmp/scg_ru.o",
@@ -26,7 +27,8 @@ def report():
             t = m.group(1)
             if t.startswith("Function Name:"):
                 mangled = t.split(":", 1)[1].strip()
-                name = subprocess.run(["c++filt", mangled], capture_output=True, text=True).stdout.split("(")[0].strip()
+                name = subprocess.run(["c++filt", mangled], capture_output=True, text=True).stdout
+                name = name.replace("(anonymous namespace)::", "").split("(")[0].strip()       # (the side libraries' kernels)
                 cur = {"name": name}
                 rows.append(cur)
             elif cur is not None and ":" in t:
@@ -38,7 +40,7 @@ def report():
 def main():
     for r in report():
         print("%-34s VGPR %4s AGPR %3s SGPR %4s spill %s/%s scratch %5s LDS %6s occ %s" % (
-            r["name"].replace("scg::", ""), r.get("VGPRs", "?"), r.get("AGPRs", "?"), r.get("SGPRs", "?"),
+            r["name"].replace("scg::", ""), r.get("VGPRs", "?"), r.get("AGPRs", "?"), r.get("SGPRs", r.get("TotalSGPRs", "?")),
             r.get("VGPRs Spill", "?"), r.get("SGPRs Spill", "?"), r.get("ScratchSize [bytes/lane]", "?"),
             r.get("LDS Size [bytes/block]", "?"), r.get("Occupancy [waves/SIMD]", "?")))
 

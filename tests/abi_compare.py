@@ -76,14 +76,14 @@ def side_header(key, name):
     return os.path.join(build.INCLUDE, build.SIDE_LIBRARIES[key][0], name)
 
 
-def check_side_library(module, key, header, pointers, prefixes=None):
+def check_side_library(module, key, header, pointers, prefixes=None, constant_prefixes=None):
     """The part every side library's test shares; returns the Abi of the header for the test's own literals.
 
     The header is read alone; it alone declares the names, each with one of the library's prefixes; `nm -D` of the library, the
     header and the binding's SYMBOLS name the same functions, none of them one of the main library's (whose glob does not see
     this header); every prototype is bound as declared under the library's pointer rule; the header's structs are the binding's
     STRUCTS in order, field by field, a pointer member being exactly c_void_p; every #define SCG_<NAME> is the binding's <NAME>
-    and the binding has no <KEY>_* constant the header lacks; the version is the same in the library, the binding, the header."""
+    and the binding has no <KEY>_* constant (or one with another of constant_prefixes) the header lacks; the version is the same in the library, the binding, the header."""
     abi = abi_text.read([side_header(key, header)])
     where = abi_text.declared_in(abi)
     assert set(where.values()) == {header}
@@ -100,7 +100,7 @@ def check_side_library(module, key, header, pointers, prefixes=None):
     assert not diffs, "\n".join(diffs)
     defined = {n[4:]: v for n, v in abi.defines.items()}
     assert {n: getattr(module, n, None) for n in defined} == defined
-    assert {n for n in vars(module) if n.startswith(key.upper() + "_")} <= set(defined)
+    assert {n for n in vars(module) if n.startswith(tuple(constant_prefixes or (key.upper() + "_",)))} <= set(defined)
     version = getattr(module.load(), f"scg_{key}_abi_version")()
     assert version == module.ABI_VERSION == abi.defines[f"SCG_{key.upper()}_ABI_VERSION"]
     return abi

@@ -1,4 +1,4 @@
-"""The JPEG stream of scgaussian_amd/csrc/jpg/scg_jpeg.h restated in numpy, one function per rule, and a small RIFF parser for the
+"""The JPEG stream of include/jpg/scg_jpeg.h restated in numpy, one function per rule, and a small RIFF parser for the
 Motion-JPEG files of jpeg.write_avi.  tests/test_jpeg_cpu.py holds this file to Pillow (libjpeg-turbo) byte for byte; tests/test_gpu_jpeg.py
 holds the kernels to it.  `encode(..., mutant=NAME)` breaks one rule on purpose: a test shows that the sweep notices.
 

@@ -28,7 +28,9 @@ Index reads, audited by reading the kernels before the first guarded run (the wi
 the same; none needed a fix): the segment tables of seed.hip and matchpoint.hip are copied to LDS with s < nseg and searched inside
 [0, nseg - 1], a segment's view is used only when 0 <= view < V, and a winner index only when 0 <= wi < N; mono.hip reads its group,
 segment and view tables at blockIdx (the launch dimensions are their lengths) and checks segment, partner and view before use;
-pngpack.hip checks a chunk's image index against the image count; resample.hip clamps the column index to wout - 1 and a bound to
+pngpack.hip checks a chunk's image index against the image count; jpegpack.hip takes a segment record only when its image lies in
+[0, images) and its row in [0, the image's segments) and names this very workgroup (segment_of), clamps every pixel index to the
+image, and reads a header template at the offset the entry point checked against the templates' size; resample.hip clamps the column index to wout - 1 and a bound to
 [0, win - 1]; the geocheck pair table is written by scg_geocheck_setup itself; scg_sort_pairs and scg_inclusive_scan_u32 take
 their integers as values, never as addresses; scg_densify_stats compares radii with 0.
 
@@ -73,6 +75,11 @@ on this reading and on the cases below, not on a proof.
   resample.hip        mid: K, whole dwords of every row; the bytes of a row's pitch behind its last dword are never read
   pngpack.hip         lengths, info, base, ioff, table: K for every chunk and image; the image table is uploaded by _bind before
                       the first launch; the gaps between the streams in `out` belong to nobody and reach no file
+  jpegpack.hip        base[s]: K, the count kernel's one store per segment (0 for a record that names nothing), base[segments] and
+                      the exclusive offsets by the scan kernel; ioff, table: K, the scan kernel writes every image's row and the
+                      last one before the encode kernel reads flag, offset and base[s], base[s + 1]; the window, the code tables and
+                      the DC history are LDS, cleared behind a barrier; the image table is uploaded by _bind, the segment and header
+                      tables by the plan; a flagged file's capacity and the gaps between the files in `out` belong to nobody
   plypack.hip, mono.hip: no scratch; every byte of the buffer / arena region an entry owns is written by it; the tables the mono
                       kernels index are uploaded from the host copy
 """
@@ -132,8 +139,8 @@ def _name_of(entry, path):
 # ---- the binding's libraries, traced ---------------------------------------------------------------------------------------------
 
 def _lib_modules():
-    from scgaussian_amd import _lib, _lib_img, _lib_io, _lib_lp, _lib_mp, _lib_png, _lib_vw
-    return (_lib, _lib_io, _lib_img, _lib_mp, _lib_vw, _lib_lp, _lib_png)
+    from scgaussian_amd import _lib, _lib_img, _lib_io, _lib_jpg, _lib_lp, _lib_mp, _lib_png, _lib_vw
+    return (_lib, _lib_io, _lib_img, _lib_mp, _lib_vw, _lib_lp, _lib_png, _lib_jpg)
 
 
 @contextlib.contextmanager
@@ -877,6 +884,80 @@ def _png_edges(gray):
                 excused={"scg_png_encode": {"args.images_host": "host copy of the image table"}})
 
 
+# ---- JPEG (jpg/scg_jpeg.h) -------------------------------------------------------------------------------------------------------------
+
+JPEG_EXCUSED = {"scg_jpeg_encode": {"args.images_host": "host copy of the image table"}}
+
+
+def _jpeg_batch(T):
+    """The smallest images of the module's own tests: one block, sizes that are no multiple of the MCU either way, one component."""
+    rng = np.random.default_rng(6)
+    return [T.noise(rng, 1, 1), T.noise(rng, 7, 9), T.noise(rng, 9, 9), T.smooth(24, 8), T.noise(rng, 5, 7, 1), T.smooth(31, 45),
+            T.noise(rng, 8, 24)]
+
+
+def _jpeg(sub):
+    def run(home):
+        import test_gpu_jpeg as T
+        from scgaussian_amd import jpeg
+        arrays = _jpeg_batch(T)
+        imgs = [home(T._t(a)) for a in arrays]
+        plan = jpeg.JpegPlan([t.shape for t in imgs], DEV, 90, sub, own_inputs=False)
+        packed = plan.encode(imgs)
+        files = packed.files()                                    # (1 x 1 and its like do not fit header + 3 H W: encoded once more)
+        T.check_files(files, arrays, 90, sub, what="guarded")
+        return dict(files=files, table=packed.table_host.copy())  # (the buffer's gaps between the files belong to nobody)
+    return Case(f"jpeg-{sub}", run, ["scg_jpeg_encode"], excused=JPEG_EXCUSED)
+
+
+def _jpeg_shortfall():
+    """The same batch with exactly the bytes every file needs, the third one byte short: without the retry no byte of that file is
+    written and the others are the restatement's; with it all seven are."""
+    def run(home):
+        import jpeg_refs
+        import test_gpu_jpeg as T
+        from scgaussian_amd import jpeg
+        arrays = _jpeg_batch(T)
+        imgs = [home(T._t(a)) for a in arrays]
+        caps = [len(jpeg_refs.encode(a, 90, "4:2:0")) for a in arrays]
+        caps[2] -= 1
+        plan = jpeg.JpegPlan([t.shape for t in imgs], DEV, 90, "4:2:0", capacities=caps, own_inputs=False)
+        packed = plan.encode(imgs).to_host(retry=False)
+        files = packed.files()
+        assert files[2] == b"" and packed.overflowed == [2] and not packed.retried
+        T.check_files(files[:2] + files[3:], arrays[:2] + arrays[3:], what="one byte short")
+        again = plan.encode(imgs)
+        whole = again.files()
+        assert again.retried and again.overflowed == []
+        T.check_files(whole, arrays, what="encoded again")
+        return dict(files=files, table=packed.table_host.copy(), whole=whole, whole_table=again.table_host.copy())
+    return Case("jpeg-shortfall", run, ["scg_jpeg_encode"], excused=JPEG_EXCUSED)
+
+
+def _jpeg_edges():
+    """1 x 1 alone; a 4:2:0 row of 43 MCUs x 6 = 258 blocks (two rounds of 256) whose file lies inside one 16 KiB window; two noise
+    rows at quality 100, 4:2:0 and 4:4:4, whose single segment crosses the window and flushes a full one.  The sizes are the
+    restatement's, on the CPU.  The default capacity (header + 3 H W) holds the two 4:2:0 rows; 1 x 1 and the 4:4:4 row (noise at
+    quality 100 takes more than three bytes per pixel: 34 315 > 629 + 24 576) are flagged and encoded once more."""
+    def run(home):
+        import test_gpu_jpeg as T
+        from scgaussian_amd import jpeg
+        rng = np.random.default_rng(6)
+        wide100, wide90, flat100 = T.noise(rng, 16, 1024), T.noise(rng, 16, 688), T.noise(rng, 8, 1024)
+        out = {}
+        for name, a, quality, sub, size in (("one_pixel", T.noise(rng, 1, 1), 90, "4:2:0", None), ("two_rounds", wide90, 90, "4:2:0", 10543),
+                                            ("window_420", wide100, 100, "4:2:0", 32992), ("window_444", flat100, 100, "4:4:4", 34315)):
+            img = home(T._t(a))
+            packed = jpeg.JpegPlan([img.shape], DEV, quality, sub, own_inputs=False).encode([img])
+            files = packed.files()
+            T.check_files(files, [a], quality, sub, what="poisoned " + name)
+            assert size is None or len(files[0]) == size, (name, len(files[0]))
+            assert packed.retried == (name in ("one_pixel", "window_444")), name
+            out[name] = files
+        return out
+    return Case("jpeg-edges", run, ["scg_jpeg_encode"], excused=JPEG_EXCUSED)
+
+
 # ---- the rasterizer: the staged geometry stage, the one-call entries, the model path (scg_raster.h) ------------------------------
 
 PINNED = "pinned host words (the camera's long-list counts, the forward's partial sums of num_rendered)"
@@ -1079,6 +1160,7 @@ CASES = (
     + [_lp_layer(3, 64, 1, LP_TM + 1, False), _lp_layer(64, 128, 3, 2 * LP_TM + 3, True)] + [_lp_metric(16, 16), _lp_metric(17, 16)]
     + [_lp_metric(16, 16, equal=True)]
     + [_png(True), _png(False)] + [_png_edges(True), _png_edges(False)]
+    + [_jpeg("4:2:0"), _jpeg("4:4:4"), _jpeg_shortfall(), _jpeg_edges()]
     + [_raster("sh_sr", 0, 1), _raster("sh_sr", 3, 63), _raster("col_cov", 3, 65), _raster("sh_sr", 0, 257), _raster("sh_sr", 3, 257),
        _raster("col_cov", 3, 257)]
     + [_raster("sh_sr", 3, 65, "culled"), _raster("col_cov", 3, 65, "culled"), _raster("sh_sr", 3, 65, "one_tile"),
@@ -1136,7 +1218,8 @@ QUERIES = {
     "scg_img_last_error", "scg_img_abi_version", "scg_resample_pitch", "scg_resample_mid_bytes", "scg_io_last_error", "scg_io_abi_version",
     "scg_ply_layout_bytes", "scg_ply_layout", "scg_lp_last_error", "scg_lp_abi_version", "scg_lp_scratch_bytes", "scg_lp_feature_floats",
     "scg_mp_last_error", "scg_mp_abi_version", "scg_mp_struct_bytes", "scg_mp_layout", "scg_mp_workspace_bytes", "scg_png_last_error",
-    "scg_png_abi_version", "scg_png_struct_bytes", "scg_png_layout", "scg_vw_last_error", "scg_vw_abi_version", "scg_vw_warp_scratch_bytes",
+    "scg_png_abi_version", "scg_png_struct_bytes", "scg_png_layout", "scg_jpg_last_error", "scg_jpg_abi_version", "scg_jpg_struct_bytes",
+    "scg_jpeg_layout", "scg_vw_last_error", "scg_vw_abi_version", "scg_vw_warp_scratch_bytes",
     "scg_vw_smooth_scratch_bytes",
 }
 

@@ -1,4 +1,4 @@
-"""JPEG files packed on the GPU (scgaussian_amd/jpeg.py, csrc/jpg/jpegpack.hip) against the numpy restatement of tests/jpeg_refs.py
+"""JPEG files packed on the GPU (scgaussian_amd/jpeg.py, csrc/jpegpack.hip) against the numpy restatement of tests/jpeg_refs.py
 (held to Pillow's libjpeg by tests/test_jpeg_cpu.py) and, where Pillow has the codec, against Pillow itself.
 
 The feature is integer arithmetic from end to end, so there is no tolerance anywhere: the device's file equals the restatement's and
@@ -232,27 +232,6 @@ def test_exactly_two_host_reads_per_batch(monkeypatch):
     assert len(reads) == 2 and packed.host.is_pinned() and not packed.retried
     monkeypatch.undo()
     check_files(files, images)
-
-
-def test_under_guard_bands_no_band_is_touched_and_both_fills_agree():
-    import guarded_alloc as G
-    rng = np.random.default_rng(6)
-    arrays = [noise(rng, 1, 1), noise(rng, 7, 9), noise(rng, 9, 9), smooth(24, 8), noise(rng, 5, 7, 1), smooth(31, 45), noise(rng, 8, 24)]
-    got = {}
-    for fill in (G.FILL_A, G.FILL_B):
-        with G.guarded(fill) as reg:
-            imgs = [reg.rehome(_t(a)) for a in arrays]
-            caps = [len(R.encode(a, 90, "4:2:0")) for a in arrays]
-            caps[2] -= 1                                         # one file that must not be written
-            plan = jpeg.JpegPlan([t.shape for t in imgs], DEV, 90, "4:2:0", capacities=caps, own_inputs=False)
-            assert reg.covers(plan.out.data_ptr()) and reg.covers(plan.workspace.data_ptr())
-            packed = plan.encode(imgs).to_host(retry=False)
-            got[fill] = (packed.files(), packed.table_host.copy())
-        assert reg.check() == []
-    assert got[G.FILL_A][0] == got[G.FILL_B][0] and np.array_equal(got[G.FILL_A][1], got[G.FILL_B][1])
-    files = got[G.FILL_A][0]
-    assert files[2] == b""
-    check_files(files[:2] + files[3:], arrays[:2] + arrays[3:])
 
 
 def test_what_the_entry_points_refuse(tmp_path):

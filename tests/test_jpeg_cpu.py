@@ -1,4 +1,4 @@
-"""The JPEG stream of scgaussian_amd/csrc/jpg/scg_jpeg.h without a GPU: the numpy restatement (tests/jpeg_refs.py) held to Pillow's
+"""The JPEG stream of include/jpg/scg_jpeg.h without a GPU: the numpy restatement (tests/jpeg_refs.py) held to Pillow's
 libjpeg whole file by whole file, a mutant per rule that must break the equality, the quality tables, the quantiser's division; then
 the eighth library's header text against its exports and its binding, every argument code, the layout's arithmetic, the header
 templates, and the AVI writer parsed back.  Nothing here launches a kernel.
@@ -12,10 +12,9 @@ import struct
 import numpy as np
 import pytest
 
-import abi_text
 import jpeg_refs as R
-from abi_compare import TYPED, VOID, bound_structs, exported_names, prototype_differences, struct_differences
-from scgaussian_amd import _lib, _lib_jpg, build, jpeg
+from abi_compare import TYPED, check_side_library
+from scgaussian_amd import _lib, _lib_jpg, jpeg
 
 u8 = np.uint8
 needs_pillow_jpeg = pytest.mark.skipif(not R.pillow_has_jpeg(), reason="Pillow has no JPEG codec here")
@@ -113,35 +112,8 @@ def test_the_quantisers_division_is_exact_and_the_dc_is_the_sum():
 
 
 # ---- the library: header text, exports, binding -----------------------------------------------------------------------------------------
-def test_the_tree_the_other_tests_pin_is_unchanged():
-    assert list(build.SIDE_LIBRARIES) == ["io", "img", "mp", "vw", "lp", "png"] and list(build.DETACHED_LIBRARIES) == ["jpg"]
-    want = sorted(build._h(build.CSRC)) + sorted(build._h(build.INCLUDE)) + [h for d in ("io", "img", "mp", "vw", "lp", "png")
-                                                                             for h in build._h(build.INCLUDE, d)]
-    assert build.HEADERS == want and not any("jpg" in h or "jpeg" in h for h in build.HEADERS)
-    assert not any("jpeg" in s for s in build.SOURCES)
-    lib_path, sources = build.side_library("jpg")
-    assert lib_path == _lib_jpg.LIB_PATH and list(sources) == [os.path.join("jpg", "jpegpack.hip")]
-    assert build.detached_headers("jpg") == [_lib_jpg.HEADER_PATH]
-    with pytest.raises(KeyError):
-        build.side_library("mjpg")
-
-
 def test_header_text_exports_and_binding_agree():
-    """abi_compare.check_side_library reads SIDE_LIBRARIES; the same comparison from its pieces for the detached library."""
-    abi = abi_text.read([_lib_jpg.HEADER_PATH])
-    where = abi_text.declared_in(abi)
-    assert set(where.values()) == {"scg_jpeg.h"} and all(n.startswith(("scg_jpg_", "scg_jpeg_")) for n in where)
-    assert exported_names(_lib_jpg.LIB_PATH) == sorted(where) == sorted(_lib_jpg.SYMBOLS)
-    main = abi_text.declared_in(abi_text.read())
-    assert not set(where) & set(main) and not set(_lib_jpg.SYMBOLS) & set(_lib.SYMBOLS)
-    structs = dict(bound_structs(_lib), **bound_structs(_lib_jpg))
-    diffs = [d for fn in abi.functions for d in prototype_differences(fn, *_lib_jpg.SYMBOLS[fn.name], structs, TYPED)]
-    assert list(abi.structs) == [s.__name__ for s in _lib_jpg.STRUCTS]
-    diffs += [d for s in _lib_jpg.STRUCTS for d in struct_differences(s.__name__, abi.structs[s.__name__], s, structs, VOID)]
-    assert not diffs, "\n".join(diffs)
-    defined = {n[4:]: v for n, v in abi.defines.items()}
-    assert {n: getattr(_lib_jpg, n, None) for n in defined} == defined
-    assert {n for n in vars(_lib_jpg) if n.startswith(("JPG_", "JPEG_"))} <= set(defined)
+    abi = check_side_library(_lib_jpg, "jpg", "scg_jpeg.h", TYPED, prefixes=("scg_jpg_", "scg_jpeg_"), constant_prefixes=("JPG_", "JPEG_"))
     lib = _lib_jpg.load()
     assert lib.scg_jpg_abi_version() == _lib_jpg.ABI_VERSION == abi.defines["SCG_JPG_ABI_VERSION"]
     assert [lib.scg_jpg_struct_bytes(i) for i in range(5)] == [C.sizeof(s) for s in _lib_jpg.STRUCTS] + [0]
