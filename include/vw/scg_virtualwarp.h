@@ -40,6 +40,17 @@
  * each y-side term multiplied by d y_{w(p),c}(q) / d depth = dsample/dgx * dgx/dd + dsample/dgy * dgy/dd, with
  * dx/dd = (a_x (Z + 1e-8) - X a_z) / (Z + 1e-8)^2 and dgx/dx = W / (W - 1); taps outside the image contribute nothing.
  *
+ * NON-FINITE VALUES of virtual_img or img_colors.  Everything above is formed as written, in IEEE arithmetic, except that a window
+ * whose winner is not v (w(p) = -1 included) is SKIPPED in view v's sum, not multiplied by zero.  A tap inside the image enters the
+ * sample whatever its weight (0 * NaN = NaN, as torch's sampler).  A window that holds a non-finite x or y_v has a NaN term, so
+ * s_v(p) is a NaN; a NaN is the minimum and the FIRST view with one wins (torch.min); loss_map(p) and loss are NaN unless the mask
+ * removes p.  Such a window's coefficients are zero, so it gives its finite members nothing: the gradients stay finite around the
+ * value.  AT the element q that holds it the zero coefficients meet x_q or y_v(q) itself, and 0 * NaN = 0 * inf = NaN: d_img(c, q)
+ * and d_depth(q) are NaN where any window within 2 of q has a winner, and d_img(c, q) is exactly 0 where none has.  d_depth(q) adds
+ * (y-side sum) * dy_v,c(q)/ddepth over EVERY view and channel, a view that wins nothing near q with a sum of 0: where that
+ * derivative is not finite (a non-finite texel under q's taps, a NaN depth) d_depth(q) is NaN, masked out or not.  (Autograd of the
+ * reference's expression divides a zero upstream by the NaN denominator and marks the whole 9 x 9 block, masked out or not.)
+ *
  * WHAT IS STORED, WHAT RECOMPUTED.  The forward WRITES to scratch the warped images y (nv,3,H,W) and the sampler's derivative
  * dy/ddepth (nv,3,H,W), both fp64, and the four coefficient maps (4,3,H,W) of the winning view, fp32; the backward reads them and
  * recomputes nothing.

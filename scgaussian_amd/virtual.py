@@ -125,7 +125,8 @@ def warp_loss_torch(virtual_img, virtual_depth, vir_mask, img_colors, records):
     s = torch.where(inb, s, torch.full_like(s, 1000.0))
     low = s.detach().amin(dim=0)
     idx = torch.arange(nv, device=dev).reshape(nv, 1, 1)
-    w = torch.where(s.detach() == low, idx, nv).amin(dim=0).clamp_max(nv - 1)      # the lowest index attaining the minimum
+    hit = (s.detach() == low) | (s.detach().isnan() & low.isnan())
+    w = torch.where(hit, idx, nv).amin(dim=0).clamp_max(nv - 1)      # the lowest index attaining the minimum; the first NaN (torch.min)
     best = s.gather(0, w.unsqueeze(0))[0]
     none = (best.detach() >= 1000) | ~vir_mask.reshape(H, W).to(torch.bool)
     loss_map = torch.where(none, torch.zeros_like(best), best)

@@ -7,7 +7,8 @@ expression in fp32 on the CPU, held to the reference's recorded results by tests
 Every comparison prints the kernel's deviation beside e_ref.  A near tie is a quantity within 16 e_ref of a decision's edge
 (two views' s_v, a channel term and a clamp bound, a normalised coordinate and +-1, a tap coordinate and an integer); on every
 small scene the set is asserted EMPTY before anything is compared (the seeds were chosen on the CPU from the reference's fp32 run
-alone, with four times the margin: another CPU's fp32 run has another e_ref), on the 96 x 128 scene it may hold 1 % of the pixels.
+alone, with four times the margin: another CPU's fp32 run has another e_ref), on the 96 x 128 scene and the three one-view scenes
+of 255 to 272 tiles it may hold 1 % of the pixels.
 
 What fp64 is.  The kernels' input is the composed record of 12 fp32 numbers per view, so the truth they are held to is the fp64
 restatement of the header's rule ON THOSE RECORDS; e_ref is the reference-shaped expression's fp32 run against its own fp64 run
@@ -49,8 +50,11 @@ def refs_of(key, scene, upstream=1.0, eps=1e-8):
     return _REFS[key]
 
 
-def run_kernels(scene, upstream=1.0, warp=None):
+def run_kernels(scene, upstream=1.0, warp=None, mask=None):
+    """mask: the bytes handed to the kernels in place of the scene's bool mask (uint8, any values)."""
     t = VR.tensors(scene, device=DEV)
+    if mask is not None:
+        t["vir_mask"] = torch.from_numpy(np.ascontiguousarray(mask)).to(DEV)
     if warp is None:
         warp = virtual.VirtualWarp(t["intrs"], t["w2cs"], t["img_colors"])
         warp.set_pose(scene["vir_c2w"])
@@ -195,6 +199,25 @@ def test_planted_coordinates_on_0_on_the_last_column_on_minus_a_half_and_on_inte
     assert np.abs(r64["d_depth"]).max() > 0 and (np.abs(tap - np.round(tap)) < 1e-7).any()      # taps 1e-8 short of an integer: one side, both
 
 
+def test_points_in_the_camera_plane_are_divided_by_1e_minus_8():
+    """x = X / (Z + 1e-8): at depths around 3 the 1e-8 is below fp32's resolution of every output, so it shows only where Z = 0
+    EXACTLY.  View 1 of a dyadic pair is moved back by the depth: Z = 0 at every pixel, X = 2 (px - cx), Y = 2 (py - cy).  By the
+    rule the centre pixel is 0 / 1e-8 = 0, in bounds on the corner (nx = ny = -1, tap -0.5), every other pixel 2e8 px and more
+    away, out of bounds and outside every image, and the depth gradient is finite everywhere.  (Without the 1e-8: 0 / 0 and
+    x / 0, the centre out of bounds and dy/ddepth not finite at every pixel.)"""
+    H, W = 6, 9
+    sc = VR.exact_scene(H, W, nv=2, depth=2.0)
+    sc["w2cs"][1, 2, 3] = -2.0
+    rec = virtual.compose_records(sc["intrs"], sc["w2cs"], sc["vir_c2w"])
+    assert np.array_equal(rec[1], np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, -2 * (W // 2), -2 * (H // 2), -2], dtype=np.float32))
+    got, truth = check("camera plane", sc, planted=True)
+    centre = np.zeros((H, W), dtype=bool)
+    centre[H // 2, W // 2] = True
+    assert np.array_equal(got["in_bounds"][1], centre) and got["in_bounds"][0].all()
+    assert np.abs(truth["tap"][1][:, ~centre]).max(axis=0).min() > 2e8 and np.array_equal(truth["tap"][1][:, centre].ravel(), [-0.5, -0.5])
+    assert np.isfinite(got["d_depth"]).all() and np.isfinite(got["d_img"]).all() and np.isfinite(got["loss"])
+
+
 def test_identical_virtual_image_and_warped_image_sit_on_the_clamp():
     """The warp of the identity pose is not the photograph (normalised with W - 1, sampled with W), so the warped image is taken
     from where the forward leaves it: the head of the scratch, (nv,3,H,W) fp64 (the header's layout), rounded to fp32.  With it as
@@ -223,6 +246,104 @@ def test_identical_virtual_image_and_warped_image_sit_on_the_clamp():
     assert np.array_equal(got["winner"], np.where(seen, 0, -1))
     assert float(got["loss"]) == 0.0 and not got["loss_map"].any()
     assert not got["d_img"].any() and not got["d_depth"].any()
+
+
+# ---- rules of the header no scene above reaches ------------------------------------------------------------------------------------
+def test_mask_bytes_other_than_one_are_true():
+    """vir_mask: "non-zero = true".  The same scene with its true pixels written as 1, 2, 0x80 and 0xFF: every output bit for bit
+    the bool mask's."""
+    sc = VR.make_scene(12, 20, 3, SEEDS[(12, 20, 3)])
+    values = np.array([1, 2, 0x80, 0xFF], dtype=np.uint8)
+    draw = values[np.random.default_rng(3).integers(0, 4, sc["vir_mask"].shape)]
+    mask = np.where(sc["vir_mask"], draw, 0).astype(np.uint8)
+    assert all((mask == b).any() for b in values) and (mask == 0).any() and np.array_equal(mask != 0, sc["vir_mask"])
+    want, got = run_kernels(sc), run_kernels(sc, mask=mask)
+    assert (want["winner"] >= 0).any() and (want["winner"][~sc["vir_mask"]] == -1).all()
+    for k in want:
+        assert np.array_equal(got[k], want[k]), k
+
+
+@pytest.mark.parametrize("variant", ["inside", "masked_out"])
+@pytest.mark.parametrize("case", list(VR.NONFINITE_CASES))
+def test_nonfinite_image_values(case, variant):
+    """One element of virtual_img set to NaN, +inf or -inf, or one texel of img_colors[1] to NaN or +inf, with every affected
+    window inside the mask and with all of them masked out.
+
+    Forward, against the restatement (whose winner is torch.min's: the first NaN view): the windows that hold the value have a
+    NaN s_v (an infinity gives inf - inf in the variance), loss_map's NaN pattern is exact, the winner there is the first view
+    with a NaN, the loss is NaN inside the mask and finite and within the bar masked out.
+
+    Gradients, against the header's gather rule in fp64 (virtualwarp_refs.gather_gradients: window_gradients per view on the
+    windows that view won, the y side times the sampler's own fp64 derivative), NOT against autograd.  Where they differ (printed):
+    autograd of the expression sends the clamp's zero through n / dd, 0 / NaN, and marks the whole 9 x 9 block of pixels whose
+    windows hold the value — 81 elements of d_img's channel and of d_depth for the image cases, 90 for the texel (it lies under
+    two pixels' taps) — masked out or not.  The header's rule (its paragraph on non-finite values) marks only the element itself:
+    d_img and d_depth at the one pixel (the two pixels under the texel) inside the mask; masked out d_img is all finite, d_depth
+    all finite for the image cases and NaN at the two pixels whose dy/ddepth holds the texel (0 * NaN over every view).  The
+    finite values are held under the suite's bar everywhere, the 9 x 9 block included; e_ref is autograd's own fp32 deviation
+    where autograd is finite."""
+    H, W, nv, seed = VR.NONFINITE_SCENE
+    assert SEEDS[(H, W, nv)] == seed and (H, W) == (T + 1, T - 1)
+    clean = VR.make_scene(H, W, nv, seed)
+    rec = virtual.compose_records(clean["intrs"], clean["w2cs"], clean["vir_c2w"])
+    sc, affected = VR.nonfinite_scene(case, variant, rec)
+    with np.errstate(invalid="ignore"):
+        r64, r32 = VR.warp_reference(sc), VR.warp_reference(sc, torch.float32)
+        truth = VR.warp_reference(sc, records=rec, sampler=True)
+        ties = VR.near_ties(r64, r32, truth)
+        truth["d_img"], truth["d_depth"] = VR.gather_gradients(sc["virtual_img"], truth)
+    assert ties["share"] == 0 and affected.sum() >= 25
+    got = run_kernels(sc)
+    name = f"{case} {variant}"
+    assert np.array_equal(got["winner"], truth["winner"]) and np.array_equal(got["in_bounds"], truth["in_bounds"]), name
+    first = np.where((np.isnan(truth["s"]) & truth["in_bounds"]), np.arange(nv).reshape(nv, 1, 1), nv).min(axis=0)
+    if variant == "inside":
+        assert np.isnan(got["loss"]) and np.array_equal(np.isnan(got["loss_map"]), affected), name
+        assert np.array_equal(got["winner"][affected], first[affected]), name
+    else:
+        assert np.isfinite(got["loss"]) and np.isfinite(got["loss_map"]).all() and (got["winner"][affected] == -1).all(), name
+    for k in ("loss", "loss_map", "d_img", "d_depth"):
+        dev, e_ref, bound = VR.compare(k, got[k], r64, r32, None, truth)      # asserts the NaN pattern against truth's, everywhere
+        ok = np.isfinite(truth[k])
+        dev = max(dev, float(np.abs(got[k][ok] - truth[k][ok]).max()) if ok.any() else 0.0)      # ... and where autograd is NaN
+        print(f"  {name} {k}: kernel deviation {dev:.3e}  e_ref {e_ref:.3e}  bound {bound:.3e}")
+        assert dev <= bound, (name, k, dev, e_ref, bound)
+    for k in ("d_img", "d_depth"):
+        print(f"  {name} {k}: NaN in the kernel's at {np.argwhere(np.isnan(got[k])).tolist()}; autograd's has {int(np.isnan(r64[k]).sum())}"
+              f" in rows {np.unique(np.argwhere(np.isnan(r64[k]))[:, -2]).tolist()}")
+        assert (np.isnan(r64[k]) | ~np.isnan(got[k])).all()                   # the rule's NaNs are among autograd's
+    key, at, _ = VR.NONFINITE_CASES[case]
+    under = np.argwhere(~np.isfinite(truth["warp"]).all(axis=(0, 1))).tolist() if key == "img_colors" else [list(at[1:])]
+    want_img = [[at[-3]] + q for q in under] if variant == "inside" else []
+    want_depth = under if variant == "inside" or key == "img_colors" else []
+    assert np.argwhere(np.isnan(got["d_img"])).tolist() == want_img and np.argwhere(np.isnan(got["d_depth"])).tolist() == want_depth
+
+
+def loss_is_the_mean_of_its_map(name, got):
+    """The header's identity, loss = sum of loss_map / (H W), on what the kernels returned: |loss - mean64(loss_map)| <=
+    2^-25 max(loss_map) + ulp32(loss) / 2, mean64 the fp64 mean of the fp32 map; the first term for the rounding of the map's
+    elements (the kernel sums them before they are rounded), the second for the rounding of the scalar."""
+    m, loss = got["loss_map"].astype(np.float64), float(got["loss"])
+    dev, bound = abs(loss - m.mean()), 2.0 ** -25 * m.max() + VR.ulp32(loss) / 2
+    print(f"  {name} loss against the fp64 mean of its map: deviation {dev:.3e}  bound {bound:.3e}")
+    assert m.max() > 0 and dev <= bound, (name, dev, bound)
+
+
+def test_loss_is_the_mean_of_its_map_on_a_small_scene():
+    """12 x 20 is two tiles: a failure of the identity HERE is not the fold's second trip."""
+    loss_is_the_mean_of_its_map("12x20x3", run_kernels(VR.make_scene(12, 20, 3, SEEDS[(12, 20, 3)])))
+
+
+@pytest.mark.parametrize("H,W", list(VR.LARGE_SCENES))
+def test_more_tiles_than_the_fold_has_threads(H, W):
+    """255, 256 and 272 tiles (the last with a partial tile row) of one view: above 256 a thread of vw_fold_kernel adds a second
+    partial sum.  Everything against fp64 as on the 96 x 128 scene (near-tie share at most 1 %: check() then leaves the scalar out),
+    and the scalar by the identity above."""
+    tiles = -(-H // T) * -(-W // T)
+    assert tiles == {(240, 272): 255, (256, 256): 256, (241, 272): 272}[(H, W)] and T * T == 256
+    got, truth = check(f"{H}x{W}x1", VR.make_scene(H, W, 1, VR.LARGE_SCENES[(H, W)]), max_share=0.01)
+    assert (got["winner"] == 0).mean() > 0.5
+    loss_is_the_mean_of_its_map(f"{H}x{W}x1", got)
 
 
 # ---- determinism, graphs, host reads --------------------------------------------------------------------------------------------
@@ -344,31 +465,98 @@ def _smooth(depth, guide, upstream=1.0):
     return loss.detach().cpu().numpy(), grad.cpu().numpy()
 
 
-@pytest.mark.parametrize("H,W", SMOOTH_SHAPES)
-@pytest.mark.parametrize("form", ["none", "hw", "chw", "1hw"])
-def test_smooth_loss_shapes_and_guides(H, W, form):
-    rng = np.random.default_rng(H * 1000 + W)
-    depth = (3 + rng.uniform(-1, 1, (H, W))).astype(np.float32)
-    guide = {"none": None, "hw": rng.uniform(0, 1, (H, W)), "chw": rng.uniform(0, 1, (3, H, W)), "1hw": rng.uniform(0, 1, (1, H, W))}[form]
-    guide = None if guide is None else guide.astype(np.float32)
-    loss, grad = _smooth(depth, guide, upstream=0.5)
-    l64, g64 = VR.smooth_reference(depth, guide, upstream=0.5)
-    l32, g32 = VR.smooth_reference(depth, guide, torch.float32, upstream=0.5)
+def check_smooth(name, depth, guide, upstream=0.5):
+    """Loss and gradient of the kernels against fp64 under max(4 e_ref, 1 ulp); the empty means' NaN and the gradient's pattern."""
+    H, W = depth.shape
+    loss, grad = _smooth(depth, guide, upstream=upstream)
+    l64, g64 = VR.smooth_reference(depth, guide, upstream=upstream)
+    l32, g32 = VR.smooth_reference(depth, guide, torch.float32, upstream=upstream)
     if H == 1 or W == 1:
         assert np.isnan(loss) and np.isnan(l64)                                # an empty mean, as torch's
         if H == 1 and W == 1:
             assert not grad.any()
     else:
         e = abs(float(l32) - float(l64))
-        print(f"smooth {H}x{W} {form}: loss deviation {abs(float(loss) - float(l64)):.3e} e_ref {e:.3e}")
+        print(f"smooth {name}: loss deviation {abs(float(loss) - float(l64)):.3e} e_ref {e:.3e} bound {VR.bar(e, l64):.3e}")
         assert abs(float(loss) - float(l64)) <= VR.bar(e, l64)
     fin = np.isfinite(g64)
     assert np.array_equal(np.isfinite(grad), fin)
     if fin.any():
         e = np.abs(g32[fin] - g64[fin]).max()
         dev = np.abs(grad[fin] - g64[fin]).max()
-        print(f"smooth {H}x{W} {form}: gradient deviation {dev:.3e} e_ref {e:.3e}")
+        print(f"smooth {name}: gradient deviation {dev:.3e} e_ref {e:.3e} bound {VR.bar(e, g64[fin]):.3e}")
         assert dev <= VR.bar(e, g64[fin])
+
+
+@pytest.mark.parametrize("H,W", SMOOTH_SHAPES)
+@pytest.mark.parametrize("form", ["none", "hw", "chw", "1hw"])
+def test_smooth_loss_shapes_and_guides(H, W, form):
+    rng = np.random.default_rng(H * 1000 + W)
+    depth = (3 + rng.uniform(-1, 1, (H, W))).astype(np.float32)
+    guide = {"none": None, "hw": rng.uniform(0, 1, (H, W)), "chw": rng.uniform(0, 1, (3, H, W)), "1hw": rng.uniform(0, 1, (1, H, W))}[form]
+    check_smooth(f"{H}x{W} {form}", depth, None if guide is None else guide.astype(np.float32))
+
+
+# 255, 256, 257 and 514 workgroups of B pixels: 65 280, 65 536, 65 538 and 131 330 pixels.  (As 2 x 32640 ... 2 x 65665 the widths
+# would pass SCG_VW_MAX_DIM = 16384 and the library would refuse them — test_virtualwarp_cpu.py asserts that — so the same pixel
+# counts are laid out 4, 4, 6 and 10 rows high; the second is as wide as the library takes.)
+SMOOTH_MANY_GROUPS = {(4, 16320): 255, (4, 16384): 256, (6, 10923): 257, (10, 13133): 514}
+
+
+@pytest.mark.parametrize("H,W", list(SMOOTH_MANY_GROUPS))
+@pytest.mark.parametrize("form", ["none", "chw"])
+def test_smooth_loss_more_workgroups_than_the_fold_has_threads(H, W, form):
+    """Above 256 workgroups a thread of vw_smooth_fold_kernel adds a second pair of partial sums."""
+    assert -(-H * W // B) == SMOOTH_MANY_GROUPS[(H, W)] and B == 256
+    rng = np.random.default_rng(H * 1000 + W)
+    depth = (3 + rng.uniform(-1, 1, (H, W))).astype(np.float32)
+    check_smooth(f"{H}x{W} {form}", depth, None if form == "none" else rng.uniform(0, 1, (3, H, W)).astype(np.float32))
+
+
+@pytest.mark.parametrize("C", [2, 4, 5, 64])
+def test_smooth_loss_guide_channels(C):
+    """The guide's mean is the sum over C in channel order and ONE division by C, C up to 64."""
+    H, W = T - 1, T + 1
+    rng = np.random.default_rng(C)
+    depth = (3 + rng.uniform(-1, 1, (H, W))).astype(np.float32)
+    check_smooth(f"{H}x{W} C={C}", depth, rng.uniform(0, 1, (C, H, W)).astype(np.float32))
+
+
+def test_smooth_loss_refuses_65_guide_channels_before_any_launch():
+    H, W, C = T - 1, T + 1, _lib_vw.VW_MAX_GUIDE_CHANNELS + 1
+    depth, guide = torch.full((H, W), 3.0, device=DEV), torch.zeros((C, H, W), device=DEV)
+    with pytest.raises(Exception, match="65 channels"):
+        virtual.smooth_loss(depth, guide)
+    lib = _lib_vw.load()
+    out = torch.full((2, H, W), 7.0, device=DEV)                                # loss in out[0, 0, 0], d_depth in out[1]
+    scratch = torch.full((4,), 7.0, device=DEV)
+    up = torch.ones(1, device=DEV)
+    assert lib.scg_vw_smooth_forward(H, W, C, depth.data_ptr(), guide.data_ptr(), out.data_ptr(), scratch.data_ptr(), 16, None) == -2
+    assert b"C = 65" in lib.scg_vw_last_error()
+    assert lib.scg_vw_smooth_backward(H, W, C, depth.data_ptr(), guide.data_ptr(), up.data_ptr(), out[1].data_ptr(), None) == -2
+    torch.cuda.synchronize()
+    assert (out == 7.0).all().item() and (scratch == 7.0).all().item()         # SCG_E_RANGE, and nothing was launched
+
+
+@pytest.mark.parametrize("kind", ["spread", "deep"])
+def test_smooth_loss_exp_far_from_zero(kind):
+    """"exp is the accurate expf": every other guide lies in [0, 1], so the exponent never leaves [-1, 0].  spread: one channel
+    drawn from [0, 20], neighbours' differences all over [0, 20], the exponent over [-20, 0].  deep: multiples of 1/64 (fp32
+    forms their differences exactly, so e_ref is the fp32 exp's own error) alternating between [0, 2] and [18, 20] in a
+    chequerboard, every exponent in [-20, -16]: there the weights are all of one size, and an exp whose relative error grows
+    with |x| is measured against weights it is wrong about, not against the weights near 1 that set the bar of `spread`."""
+    H, W = 37, 29
+    rng = np.random.default_rng(20)
+    depth = (3 + rng.uniform(-1, 1, (H, W))).astype(np.float32)
+    if kind == "spread":
+        guide = rng.uniform(0, 20, (H, W)).astype(np.float32)
+    else:
+        yy, xx = np.mgrid[0:H, 0:W]
+        guide = (rng.integers(0, 129, (H, W)) / 64.0 + 18.0 * ((yy + xx) % 2)).astype(np.float32)
+    gx, gy = np.abs(np.diff(guide.astype(np.float64), axis=1)), np.abs(np.diff(guide.astype(np.float64), axis=0))
+    lo, hi = min(gx.min(), gy.min()), max(gx.max(), gy.max())
+    assert (lo < 0.1 and hi > 19 and np.histogram(gx, 4, (0, 20))[0].min() > 20) if kind == "spread" else (lo >= 16 and hi <= 20)
+    check_smooth(f"{H}x{W} exp {kind}", depth, guide)
 
 
 def test_smooth_loss_equal_neighbours_have_sign_zero():

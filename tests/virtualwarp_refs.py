@@ -82,6 +82,30 @@ def exact_scene(H, W, nv=1, shift_px=0.0, depth=2.0):
     return s
 
 
+# (H, W, nv, seed) of the scene the non-finite image values are planted in, and the cases: tensor, element, value.  Pixel (8, 7) is
+# interior (its 5x5 windows reach no border), three views see it, and texel (8, 7) of view 1 lies under the taps of two pixels.
+NONFINITE_SCENE = (17, 15, 3, 28)
+NONFINITE_CASES = {"img_nan": ("virtual_img", (1, 8, 7), np.nan), "img_pinf": ("virtual_img", (1, 8, 7), np.inf),
+                   "img_ninf": ("virtual_img", (1, 8, 7), -np.inf), "colors_nan": ("img_colors", (1, 1, 8, 7), np.nan),
+                   "colors_pinf": ("img_colors", (1, 1, 8, 7), np.inf)}
+# (H, W): seed of the one-view scenes with 255, 256 and 272 tiles of 16 x 16 (the last with a partial tile row)
+LARGE_SCENES = {(240, 272): 2, (256, 256): 1, (241, 272): 4}
+
+
+def nonfinite_scene(case, variant, records):
+    """(scene, affected): one value of NONFINITE_CASES planted; affected (H,W): the pixels with a NaN s_v in some view that sees them, by the fp64
+    restatement on `records`.  variant "inside": the mask keeps every affected pixel; "masked_out": it removes them all."""
+    H, W, nv, seed = NONFINITE_SCENE
+    sc = make_scene(H, W, nv, seed)
+    key, at, value = NONFINITE_CASES[case]
+    sc[key][at] = value
+    with np.errstate(invalid="ignore"):
+        r = warp_reference(sc, grads=False, records=records)
+    affected = (np.isnan(r["s"]) & r["in_bounds"]).any(axis=0)
+    sc["vir_mask"] = (sc["vir_mask"] | affected) if variant == "inside" else (sc["vir_mask"] & ~affected)
+    return sc, affected
+
+
 def tensors(scene, dtype=torch.float32, device="cpu"):
     out = {k: torch.from_numpy(np.ascontiguousarray(scene[k])) for k in KEYS}
     return {k: (v.to(device) if v.dtype == torch.bool else v.to(device, dtype)) for k, v in out.items()}
@@ -99,13 +123,15 @@ def ssim_terms(x, y):
     return raw, torch.clamp(raw, 0, 1)
 
 
-def warp_reference(scene, dtype=torch.float64, upstream=1.0, grads=True, records=None, eps=1e-8):
+def warp_reference(scene, dtype=torch.float64, upstream=1.0, grads=True, records=None, eps=1e-8, sampler=False):
     """The loss as the reference's function shapes it (unprojection through K_0^-1, the virtual pose, each view's w2c and K, one
     matrix product after the other; grid_sample; SSIM; the 1000 marker; min over views), in `dtype` on the CPU.  Returns a dict of
     numpy arrays: loss, d_img, d_depth (for loss * upstream), loss_map, winner, in_bounds, s (nv,H,W) before the marker, raw
     (nv,3,H,W), norm (nv,2,H,W), tap (nv,2,H,W).
     records (nv,12): THE RESTATEMENT of the rule the header states — (X, Y, Z) = d * (M_v (px, py, 1)) + t_v from the composed
-    matrices the kernels are given, everything behind it the same; eps: the 1e-8 of the division (0 where fp32 absorbs it)."""
+    matrices the kernels are given, everything behind it the same; eps: the 1e-8 of the division (0 where fp32 absorbs it).
+    sampler (with grads): also "dyd" (nv,3,H,W), d warp[v,c](q) / d depth(q) by autograd of the projection and the sampler ALONE
+    (a pixel's sample depends on that pixel's depth only, so the gradient of a channel's sum is the per-pixel derivative)."""
     t = tensors(scene, dtype)
     img, depth = t["virtual_img"].requires_grad_(grads), t["virtual_depth"].requires_grad_(grads)
     H, W = img.shape[1:]
@@ -137,9 +163,12 @@ def warp_reference(scene, dtype=torch.float64, upstream=1.0, grads=True, records
     raw, term = ssim_terms(img.unsqueeze(0), warp)
     s = term.mean(dim=1)
     marked = torch.where(inb, s, torch.full_like(s, 1000.0))
+    # torch.min(dim=0) written out: the lowest index attaining the minimum; a NaN IS the minimum and the first NaN view wins
+    # (tests/test_virtualwarp_cpu.py holds this to the installed torch.min)
     low = marked.detach().amin(dim=0)
     idx = torch.arange(nv).reshape(nv, 1, 1)
-    w = torch.where(marked.detach() == low, idx, nv).amin(dim=0).clamp_max(nv - 1)
+    hit = (marked.detach() == low) | (marked.detach().isnan() & low.isnan())
+    w = torch.where(hit, idx, nv).amin(dim=0).clamp_max(nv - 1)
     best = marked.gather(0, w.unsqueeze(0))[0]
     none = (best.detach() >= 1000) | ~t["vir_mask"].reshape(H, W)
     loss_map = torch.where(none, torch.zeros_like(best), best)
@@ -148,6 +177,13 @@ def warp_reference(scene, dtype=torch.float64, upstream=1.0, grads=True, records
            "in_bounds": inb.numpy(), "s": s.detach().numpy(), "raw": raw.detach().numpy(), "warp": warp.detach().numpy(),
            "norm": torch.stack([nx, ny], dim=1).reshape(nv, 2, H, W).detach().numpy()}
     out["tap"] = np.stack([((out["norm"][:, 0] + 1) * W - 1) / 2, ((out["norm"][:, 1] + 1) * H - 1) / 2], axis=1)
+    if grads and sampler:
+        # one (view, channel) plane at a time: torch's sampler backward multiplies every channel's texel by its upstream, and a zero
+        # upstream times a NaN texel of ANOTHER channel or view would mark derivatives that do not depend on it
+        one = lambda v, c: F.grid_sample(t["img_colors"][v:v + 1, c:c + 1], grid[v:v + 1], mode="bilinear", padding_mode="zeros",      # noqa: E731
+                                         align_corners=False).sum()
+        out["dyd"] = np.stack([np.stack([torch.autograd.grad(one(v, c), depth, retain_graph=True)[0].numpy() for c in range(3)])
+                               for v in range(nv)])
     if grads:
         (loss * upstream).backward()
         out["d_img"], out["d_depth"] = img.grad.numpy(), depth.grad.numpy()
@@ -186,20 +222,43 @@ def window_coefficients(x, y):
     return A, Ap, np.where(open_, r * d1 / dd, 0), np.where(open_, -n1 / dd, 0)
 
 
-def window_gradients(x, y, up):
+def window_gradients(x, y, up, enters=None):
     """d/dx and d/dy of sum over p, c of up[p] * term_c(p), gathered per pixel q over the window centres within 2 of q, each
-    counted fold_count times per axis: the rule the backward kernel follows.  fp64 numpy, x, y (3,H,W), up (H,W)."""
+    counted fold_count times per axis: the rule the backward kernel follows.  fp64 numpy, x, y (3,H,W), up (H,W).
+    enters (H,W) bool: the windows that enter the sum at all (default: every one).  A window that does not is SKIPPED, not
+    multiplied by zero: the difference shows where x or y is not finite."""
     _, H, W = x.shape
-    A, Ap, B, C = window_coefficients(x, y)
+    with np.errstate(invalid="ignore"):
+        A, Ap, B, C = window_coefficients(x, y)
     gx, gy = np.zeros_like(x), np.zeros_like(y)
     for qy in range(H):
         for qx in range(W):
             for py in range(max(qy - 2, 0), min(qy + 2, H - 1) + 1):
                 for px in range(max(qx - 2, 0), min(qx + 2, W - 1) + 1):
+                    if enters is not None and not enters[py, px]:
+                        continue
                     k = fold_count(py, qy, H) * fold_count(px, qx, W) * up[py, px] / 25
                     gy[:, qy, qx] += k * (A[:, py, px] + B[:, py, px] * y[:, qy, qx] + C[:, py, px] * x[:, qy, qx])
                     gx[:, qy, qx] += k * (Ap[:, py, px] + B[:, py, px] * x[:, qy, qx] + C[:, py, px] * y[:, qy, qx])
     return gx, gy
+
+
+def gather_gradients(img, truth, upstream=1.0):
+    """(d_img, d_depth) by THE HEADER'S GATHER RULE in fp64, in plain IEEE arithmetic: per view v the windows p with w(p) = v
+    enter (the others are skipped), each with the coefficient maps of (virtual_img, y_v) — zero where the clamp is active or the
+    term is a NaN — and upstream / (3 H W); d_img is the sum of the x sides over the views, d_depth the sum over views and channels
+    of the y side times dy_v,c / ddepth, over EVERY view (a view that wins no window near q contributes 0 * dy/ddepth, which is
+    a NaN where the derivative is not finite).  truth: warp_reference(..., sampler=True)'s dict ("warp", "winner", "dyd")."""
+    x = np.asarray(img, dtype=np.float64)
+    _, H, W = x.shape
+    d_img, d_depth = np.zeros_like(x), np.zeros((H, W))
+    with np.errstate(invalid="ignore"):
+        for v in range(truth["warp"].shape[0]):
+            won = truth["winner"] == v
+            gx, gy = window_gradients(x, truth["warp"][v].astype(np.float64), np.full((H, W), upstream / (3.0 * H * W)), enters=won)
+            d_img += gx
+            d_depth += (gy * truth["dyd"][v]).sum(axis=0)
+    return d_img, d_depth
 
 
 # ---- e_ref, near ties, the bar --------------------------------------------------------------------------------------------------
