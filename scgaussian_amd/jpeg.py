@@ -6,6 +6,7 @@
     plan = jpeg.JpegPlan(shapes, device, ...)     the uploaded tables and the buffers, for repeated and captured calls
     jpeg.save_jpeg(path, tensor)                  one image; what the kernels do not take goes to Pillow
     jpeg.write_avi(path, files, fps, W, H)        the files as the frames of a Motion-JPEG AVI: host only, `struct` alone
+    jpeg.read_avi(path)                           the frames' files of such a video, for jpeg_decode.decode: host only, `struct` alone
 
 An image is a contiguous uint8 tensor on the GPU shaped (H, W), (H, W, 1) or (H, W, 3); a list of them or one (N, H, W, 3) tensor
 is a batch.  The output capacity of an image defaults to header + 3 H W bytes, which every real frame stays far below; a file that
@@ -218,6 +219,33 @@ def write_avi(path: str, files: Sequence[bytes], fps, width: int, height: int) -
         for f in files:
             fh.write(_chunk(b"00dc", f))
         fh.write(_chunk(b"idx1", b"".join(index)))
+
+
+def read_avi(path: str) -> List[bytes]:
+    """The frames' JPEG files of a Motion-JPEG AVI that write_avi wrote (RIFF 'AVI ', the '00dc' chunks of LIST movi, in order).
+    Host only.  With jpeg_decode.decode the project reads back its own videos: their frames carry one restart interval per MCU row."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"AVI ":
+        raise ValueError(f"{path} is not a RIFF AVI file")
+    end = min(len(data), 8 + struct.unpack_from("<I", data, 4)[0])
+    at, frames = 12, None
+    while at + 8 <= end:
+        name, size = data[at:at + 4], struct.unpack_from("<I", data, at + 4)[0]
+        if name == b"LIST" and data[at + 8:at + 12] == b"movi":
+            frames, p, stop = [], at + 12, min(end, at + 8 + size)
+            while p + 8 <= stop:
+                cname, csize = data[p:p + 4], struct.unpack_from("<I", data, p + 4)[0]
+                if p + 8 + csize > stop:
+                    raise ValueError(f"{path}: the chunk at byte {p} runs past its list")
+                if cname == b"00dc":
+                    frames.append(data[p + 8:p + 8 + csize])
+                p += 8 + csize + (csize & 1)
+            break
+        at += 8 + size + (size & 1)
+    if frames is None:
+        raise ValueError(f"{path} has no LIST movi")
+    return frames
 
 
 def check_options(quality, subsampling, fps) -> None:
