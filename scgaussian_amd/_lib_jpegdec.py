@@ -18,17 +18,22 @@ LIB_PATH = os.path.join(_HERE, "libscg_jpegdec.so")
 HEADER_PATH = os.path.join(_HERE, "csrc", "dec", "scg_jpegdec.h")
 
 # the header's integer #defines under their own names minus "SCG_"
-JPEGDEC_ABI_VERSION = ABI_VERSION = 1
+JPEGDEC_ABI_VERSION = ABI_VERSION = 2
 JPEGDEC_SUBSEQ, JPEGDEC_THREADS, JPEGDEC_MAX_DIM, JPEGDEC_MAX_SEGMENT = 128, 256, 65535, 2 ** 28 - 1
-JPEGDEC_HEADER_BYTES, JPEGDEC_FRAME_WORDS = 4096, 16
+JPEGDEC_HEADER_BYTES, JPEGDEC_FRAME_WORDS, JPEGDEC_IMAGE_WORDS, JPEGDEC_MAX_BATCH = 4096, 16, 48, 65535
 JPEGDEC_BAD_CODE, JPEGDEC_BAD_ZIGZAG, JPEGDEC_BAD_COUNT, JPEGDEC_BAD_SYNC, JPEGDEC_BAD_RESTART = 1, 2, 4, 8, 16
 
 _P = C.c_void_p
+_U64P = C.POINTER(C.c_uint64)
 SYMBOLS = {
     "scg_jpegdec_last_error": (C.c_char_p, []),
     "scg_jpegdec_abi_version": (C.c_int32, []),
     "scg_jpegdec_sizes": (C.c_int, [C.POINTER(C.c_int32), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     "scg_jpegdec_decode": (C.c_int, [C.POINTER(C.c_int32), _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_size_t, C.c_int32, C.c_int32, _P]),
+    "scg_jpegdec_batch_plan": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), _U64P, _U64P, _U64P, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
+                                         _U64P, _U64P, _U64P, C.POINTER(C.c_int32)]),
+    "scg_jpegdec_decode_batch": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), _P, _P, C.c_uint64, _P, C.c_size_t, _P,
+                                           C.c_size_t, C.c_int32, _P]),
 }
 
 _lib = None

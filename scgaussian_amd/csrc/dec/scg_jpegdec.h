@@ -71,19 +71,52 @@
  * MCUs (0: none), quant table id of each of three components, DC table id of each, AC table id of each, 0.
  * The status (the first four uint32 of the workspace; the call's ONE host read): [0] the SCG_JPEGDEC_BAD_* bits, 0 = the pixels are
  * right; [1] sync launches until nothing changed (0: not within those run); [2] blocks counted; [3] 0.
+ *
+ * THE BATCH.  Nothing in the decode of one file depends on another file, so scg_jpegdec_decode_batch puts n images into the SAME
+ * seven steps (two clears, the sync launches, count, scan, write, idct, colour) whatever n is.  The rule above is not restated:
+ * the decode, the idct, the upsampling and the colour conversion are the same device functions over an image view (frame and
+ * pointers), which the single entry fills from its arguments and the batched kernels from the image table.  A workgroup lies
+ * inside ONE image and finds it from its index alone by a search of a prefix table (uniform: scalar loads); thread t of an image's
+ * workgroup g owns subsequence g * SCG_JPEGDEC_THREADS + t of THAT image; subsequence 0 of every image starts from the truth; the
+ * hand-over words, the change counters and the status are per image, and no state crosses from one image into the next.  The scan
+ * runs one workgroup per image.  Idct and colour run flat grids over all images' blocks and (row, chunk of 4 *
+ * SCG_JPEGDEC_THREADS bytes) pairs.  Every offset a kernel takes from the DEVICE table is held to the buffer sizes the call was
+ * passed: a device table that differs from the host copy gives wrong pixels or a status bit (an image whose record cannot be
+ * followed reports SCG_JPEGDEC_BAD_SYNC | SCG_JPEGDEC_BAD_COUNT), never an access outside a buffer.
+ *
+ * The upload (device memory, 16-byte aligned, the caller's ONE copy): header blocks and entropy-coded segments at 16-byte offsets,
+ * anywhere in it; two images may name the same header block.
+ * The table block (n * SCG_JPEGDEC_IMAGE_WORDS + 3 (n + 1) uint32, little-endian; written by scg_jpegdec_batch_plan into host
+ * memory, uploaded by the caller, normally at the front of the upload):
+ *   n image records of SCG_JPEGDEC_IMAGE_WORDS words:
+ *     [0, 16)    the frame
+ *     [16]       bytes of the segment;  [17] 0
+ *     [18, 24)   three uint64 (low word first): offset of the header block and of the segment in the upload, of the pixels in `out`
+ *     [24, 44)   ten uint64: offsets in the workspace of the change counters, entry, exit, bnd, cnt, dcs, coefficients, and the
+ *                planes Y, Cb, Cr (one component: all three name the Y plane)
+ *     [44, 48)   0
+ *   then three prefix tables of n + 1 words: the first workgroup of each image in the entropy grid, the idct grid and the colour
+ *   grid; entry n is the grid's size.
+ * The output: ONE buffer; image i holds its tight H W components bytes at its offset, every offset 16-byte aligned, the images in
+ * input order, so images of one shape lie at a constant stride.
+ * The workspace: 4 n status words first (four per image, as above), then the change counters of every image (one word per sync
+ * launch, max_rounds of them; ONE clear covers both), then per image entry, exit, bnd, cnt, dcs and the planes, then every
+ * coefficient buffer side by side (ONE clear).
  */
 #ifndef SCG_JPEGDEC_H
 #define SCG_JPEGDEC_H
 
 #include "../../../include/scg_raster.h"
 
-#define SCG_JPEGDEC_ABI_VERSION 1
+#define SCG_JPEGDEC_ABI_VERSION 2
 #define SCG_JPEGDEC_SUBSEQ 128            /* bytes of a subsequence: one thread's share of the stream */
 #define SCG_JPEGDEC_THREADS 256           /* threads of a workgroup of the entropy kernels */
 #define SCG_JPEGDEC_MAX_DIM 65535         /* H and W */
 #define SCG_JPEGDEC_MAX_SEGMENT 268435455 /* bytes of the entropy-coded segment: bit positions are 32-bit */
 #define SCG_JPEGDEC_HEADER_BYTES 4096
 #define SCG_JPEGDEC_FRAME_WORDS 16
+#define SCG_JPEGDEC_IMAGE_WORDS 48            /* uint32 of an image record of the batch's table */
+#define SCG_JPEGDEC_MAX_BATCH 65535           /* images of one scg_jpegdec_decode_batch */
 #define SCG_JPEGDEC_BAD_CODE 1            /* a code word no table holds, or a size beyond 11 (DC) / 10 (AC) */
 #define SCG_JPEGDEC_BAD_ZIGZAG 2          /* a run past coefficient 63 */
 #define SCG_JPEGDEC_BAD_COUNT 4           /* the blocks found are not the frame's */
@@ -111,6 +144,24 @@ SCG_API int scg_jpegdec_sizes(const int32_t* frame, uint64_t segment_bytes, uint
 SCG_API int scg_jpegdec_decode(const int32_t* frame, const void* header_dev, const uint8_t* segment_dev, uint64_t segment_bytes,
                                void* out, size_t out_bytes, void* workspace, size_t workspace_bytes, int32_t rounds_done,
                                int32_t rounds, void* stream);
+
+/* Host only.  For n (1..SCG_JPEGDEC_MAX_BATCH) images — frames[n][SCG_JPEGDEC_FRAME_WORDS], segment_bytes[n], and per image the
+ * 16-byte-aligned offset of its header block and of its segment in an upload of upload_bytes — the table block (above) into
+ * table[0, table_words), each image's offset in the output into out_offsets[n], the workspace and output totals, and max_rounds:
+ * the maximum over the images of scg_jpegdec_sizes' max_rounds. */
+SCG_API int scg_jpegdec_batch_plan(int32_t n, const int32_t* frames, const uint64_t* segment_bytes, const uint64_t* header_offsets,
+                                   const uint64_t* segment_offsets, uint64_t upload_bytes, uint32_t* table, uint64_t table_words,
+                                   uint64_t* out_offsets, uint64_t* workspace_bytes, uint64_t* out_bytes, int32_t* max_rounds);
+
+/* frames and table: the HOST copies, validated in full (every record and prefix entry must be what scg_jpegdec_batch_plan gives
+ * for these frames and the offsets the records name, inside upload_bytes) before anything touches a device.  table_dev: the
+ * uploaded table block, 16-byte aligned; upload_dev[0, upload_bytes), out[0, out_bytes) and workspace[0, workspace_bytes), each
+ * 16-byte aligned and at least the plan's totals.  Runs `rounds` sync launches, 1 <= rounds <= max_rounds, then count, scan,
+ * write, idct, colour, once for the whole batch.  There is no continuation: an image whose status carries SCG_JPEGDEC_BAD_SYNC is
+ * the caller's to decode again (scg_jpegdec_decode). */
+SCG_API int scg_jpegdec_decode_batch(int32_t n, const int32_t* frames, const uint32_t* table, const void* table_dev,
+                                     const void* upload_dev, uint64_t upload_bytes, void* out, size_t out_bytes, void* workspace,
+                                     size_t workspace_bytes, int32_t rounds, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,8 @@ are computed where they are needed:
 
     images.install(camera_utils, decode="device")     # ... and a JPEG file is decoded on the GPU too (jpeg_decode.py)
     image = images.load_image(path, (w, h))           # the direct form: file -> float32 (C, h, w), PILtoTorch(Image.open(path), ..)
+    imgs = images.load_images(paths, (w, h))          # the same tensors for a list: ONE jpeg_decode.decode_batch, one resize per group
+    images.install_batched(camera_utils)              # cameraList_from_camInfos loads a scene's JPEG files with one load_images
 
     u8 = images.resize_u8(np.asarray(pil_image), (w, h))          # device uint8 (h, w, 3) == np.asarray(pil_image.resize((w, h)))
     u8, f32 = images.resize_batch(arrays, (w, h), want_float=True)  # one upload and at most two launches per chunk
@@ -396,4 +398,88 @@ def install(module, decode=None):
         module.PILtoTorch = functools.partial(pil_to_torch, decode="device")
     else:
         module.PILtoTorch = pil_to_torch
+    return old
+
+
+@torch.no_grad()
+def load_images(paths, resolutions, device="cuda") -> List[torch.Tensor]:
+    """[load_image(p, r) for p, r in zip(paths, resolutions)], bit for bit, with the JPEG files decoded by ONE
+    jpeg_decode.decode_batch (one upload, one host read for the list) and resized by one resize_batch(..., want_float=True) per
+    group of equal (source shape, target size), read where the decoder left them.  resolutions: one (w, h) or one per path.  A file
+    that is no JPEG, a file the decoder refuses and a reduction beyond the resize kernels take load_image's routes."""
+    from PIL import Image
+    from . import jpeg_decode
+    dev = _device(device)
+    paths = list(paths)
+    if len(resolutions) == 2 and not isinstance(resolutions[0], (tuple, list)):
+        resolutions = [resolutions] * len(paths)
+    resolutions = [(int(r[0]), int(r[1])) for r in resolutions]
+    if len(resolutions) != len(paths):
+        raise _err(f"{len(resolutions)} resolutions for {len(paths)} paths")
+    results: List[Optional[torch.Tensor]] = [None] * len(paths)
+    batch = []                                                                    # (index, expected u8 shape)
+    for i, (path, res) in enumerate(zip(paths, resolutions)):
+        with Image.open(path) as im:
+            if lazily_opened_jpeg(im):
+                Cn = 1 if im.mode == "L" else 3
+                if plan_of((im.size[0], im.size[1]), res, Cn).device_route:
+                    batch.append((i, (im.size[1], im.size[0]) + ((3,) if Cn == 3 else ())))
+    decoded = jpeg_decode.decode_batch([paths[i] for i, _shape in batch], dev) if batch else []
+    groups: Dict[tuple, List[Tuple[int, torch.Tensor]]] = {}
+    for (i, shape), u8 in zip(batch, decoded):
+        if u8.dtype == torch.uint8 and tuple(u8.shape) == shape:
+            groups.setdefault((shape, resolutions[i]), []).append((i, u8))
+    for (shape, res), members in groups.items():
+        H, W, Cn = _hwc(shape, "an image")
+        tensors = [u8 for _i, u8 in members]
+        nbytes = H * W * Cn
+        first = tensors[0]
+        same = all(t.untyped_storage().data_ptr() == first.untyped_storage().data_ptr() and t.is_contiguous()
+                   and t.storage_offset() == first.storage_offset() + k * nbytes for k, t in enumerate(tensors))
+        if same:                                                                  # side by side where the decoder wrote them
+            stacked = torch.as_strided(first, (len(tensors), H, W, Cn), (nbytes, W * Cn, Cn, 1), first.storage_offset())
+        else:
+            stacked = torch.stack([t.reshape(H, W, Cn) for t in tensors])
+        _u8, fl = resize_batch(stacked, res, want_float=True)
+        for k, (i, _t) in enumerate(members):
+            results[i] = fl[k]
+    for i, (path, res) in enumerate(zip(paths, resolutions)):
+        if results[i] is None:
+            results[i] = load_image(path, res, device=dev)
+    return results
+
+
+def install_batched(module):
+    """Rebind `cameraList_from_camInfos` in `module` (utils.camera_utils): the lazily opened JPEG files among cam_infos are loaded
+    with ONE load_images call at the sizes loadCam will ask for (target_resolution), then the module's own loop runs with PILtoTorch
+    bound to a function that serves those tensors by (file name, resolution) and calls pil_to_torch for anything else.  Returns
+    the function that was bound before, as install does."""
+    old = module.cameraList_from_camInfos
+
+    def cameraList_from_camInfos(cam_infos, resolution_scale, args):
+        cam_infos = list(cam_infos)
+        wanted: Dict[tuple, None] = {}
+        for c in cam_infos:
+            im = getattr(c, "image", None)
+            if im is not None and lazily_opened_jpeg(im):
+                res = target_resolution(im.size[0], im.size[1], args.resolution, resolution_scale)
+                wanted[(os.fspath(im.filename), (int(res[0]), int(res[1])))] = None
+        keys = list(wanted)
+        ready = dict(zip(keys, load_images([k[0] for k in keys], [k[1] for k in keys]))) if keys else {}
+
+        def serve(pil_image, resolution):
+            name = getattr(pil_image, "filename", None)
+            key = (os.fspath(name), (int(resolution[0]), int(resolution[1]))) if isinstance(name, (str, os.PathLike)) and name else None
+            if key in ready:
+                return ready[key]
+            return pil_to_torch(pil_image, resolution)
+
+        before = getattr(module, "PILtoTorch", None)
+        module.PILtoTorch = serve
+        try:
+            return old(cam_infos, resolution_scale, args)
+        finally:
+            module.PILtoTorch = before
+
+    module.cameraList_from_camInfos = cameraList_from_camInfos
     return old

@@ -3,6 +3,7 @@
     u8 = jpeg_decode.decode(path_or_bytes)        device uint8 (H, W, 3) or (H, W) == np.asarray(Image.open(path)), ONE host read
     info = jpeg_decode.parse(data)                host only: the frame, the tables, the bounds of the entropy-coded segment, or None
     plan = jpeg_decode.plan_of(info.frame, dev)   the workspace of one frame shape, kept between calls
+    u8s = jpeg_decode.decode_batch(sources)       [decode(s) for s in sources] with ONE upload, ONE launch chain and ONE host read
 
 The reference opens every camera image with Image.open (scene/dataset_readers.py) and loadCam packs and resizes it on one host
 core; here the file's bytes (about a tenth of the pixels) are uploaded and the pixels appear where images.resize_u8 reads them.
@@ -361,3 +362,178 @@ def decode_staged(info: JpegInfo, upload: torch.Tensor, out: Optional[torch.Tens
     LAST.update(status=int(status[0]), rounds=int(status[1]), launched=done, blocks=int(status[2]), segment_bytes=seg_bytes,
                 route="device" if int(status[0]) == 0 else "refused")
     return out, status
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# a batch: a scene's images in one upload, one call, one read
+# --------------------------------------------------------------------------------------------------------------------------------
+IMAGE_WORDS = _lib_jpegdec.JPEGDEC_IMAGE_WORDS
+_ALIGN = 16
+
+
+def _round_up(v: int, to: int) -> int:
+    return (v + to - 1) // to * to
+
+
+def table_words(n: int) -> int:
+    """uint32 words of the table block of n images: the records, then three prefix tables of n + 1 (scg_jpegdec.h)."""
+    return n * IMAGE_WORDS + 3 * (n + 1)
+
+
+class BatchStage:
+    """Where everything lies in the ONE staging buffer of a batch: [table block | distinct header blocks | segments], every part
+    at a 16-byte offset.  Host only.  Header blocks are de-duplicated by content (a video's frames, files written with the
+    standard tables); of a file only its entropy-coded segment is staged."""
+
+    def __init__(self, infos, datas):
+        self.infos, self.datas = list(infos), list(datas)
+        self.n = len(self.infos)
+        self.table_bytes = _round_up(4 * table_words(self.n), _ALIGN)
+        self.headers = []                                        # the distinct blocks, in order of first use
+        seen: Dict[bytes, int] = {}
+        at = self.table_bytes
+        self.header_offsets = []
+        for info in self.infos:
+            block = header_block(info)
+            key = block.tobytes()
+            if key not in seen:
+                seen[key] = self.table_bytes + HEADER_BYTES * len(self.headers)
+                self.headers.append(block)
+            self.header_offsets.append(seen[key])
+        at += HEADER_BYTES * len(self.headers)
+        self.segment_offsets, self.segment_bytes = [], []
+        for info in self.infos:
+            self.segment_offsets.append(at)
+            self.segment_bytes.append(info.segment_end - info.segment_start)
+            at = _round_up(at + self.segment_bytes[-1], _ALIGN)
+        self.nbytes = at
+        self.frames = np.ascontiguousarray(np.stack([np.asarray(i.frame, dtype=np.int32) for i in self.infos])) if self.n else \
+            np.zeros((0, _lib_jpegdec.JPEGDEC_FRAME_WORDS), dtype=np.int32)
+        self.table = np.zeros(table_words(self.n), dtype=np.uint32)
+        self.out_offsets = np.zeros(self.n, dtype=np.uint64)
+        self.workspace_bytes = self.out_bytes = self.max_rounds = 0
+
+    def plan(self) -> "BatchStage":
+        """scg_jpegdec_batch_plan: the table block, each image's place in the output, the totals."""
+        u64 = lambda values: np.ascontiguousarray(values, dtype=np.uint64)                        # noqa: E731
+        seg, hdr, sat = u64(self.segment_bytes), u64(self.header_offsets), u64(self.segment_offsets)
+        ws, ob, mr = C.c_uint64(), C.c_uint64(), C.c_int32()
+        p64 = C.POINTER(C.c_uint64)
+        check(_lib_jpegdec.load().scg_jpegdec_batch_plan(
+            self.n, self.frames.ctypes.data_as(C.POINTER(C.c_int32)), seg.ctypes.data_as(p64), hdr.ctypes.data_as(p64), sat.ctypes.data_as(p64),
+            self.nbytes, self.table.ctypes.data_as(C.POINTER(C.c_uint32)), self.table.size, self.out_offsets.ctypes.data_as(p64),
+            C.byref(ws), C.byref(ob), C.byref(mr)), "scg_jpegdec_batch_plan")
+        self.workspace_bytes, self.out_bytes, self.max_rounds = int(ws.value), int(ob.value), int(mr.value)
+        return self
+
+    def fill(self, view: np.ndarray) -> None:
+        """Write the staged bytes into view[0, nbytes) (uint8): what the ONE upload carries."""
+        view[:4 * self.table.size] = self.table.view(np.uint8)
+        for k, block in enumerate(self.headers):
+            at = self.table_bytes + HEADER_BYTES * k
+            view[at:at + HEADER_BYTES] = block
+        for info, data, at, nb in zip(self.infos, self.datas, self.segment_offsets, self.segment_bytes):
+            view[at:at + nb] = np.frombuffer(data, dtype=np.uint8, count=nb, offset=info.segment_start)
+
+    def shape(self, i: int) -> tuple:
+        info = self.infos[i]
+        return (info.H, info.W) + ((3,) if info.components == 3 else ())
+
+
+_BATCH_BUFFERS: Dict[str, object] = {}
+
+
+def _batch_staging(nbytes: int) -> torch.Tensor:
+    """nbytes of the module's pinned staging buffer (grown with a quarter to spare, then reused; decode_batch reads the status
+    words, which waits for the upload, before the next chunk fills it)."""
+    buf = _BATCH_BUFFERS.get("staging")
+    if buf is None or buf.numel() < nbytes:
+        buf = _BATCH_BUFFERS["staging"] = torch.empty(nbytes * 5 // 4, dtype=torch.uint8, pin_memory=True)
+    return buf[:nbytes]
+
+
+def _batch_workspace(nbytes: int, dev: torch.device) -> torch.Tensor:
+    key = ("workspace", str(dev))
+    buf = _BATCH_BUFFERS.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = _BATCH_BUFFERS[key] = torch.empty(max(nbytes * 5 // 4, _ALIGN), dtype=torch.uint8, device=dev)
+    return buf
+
+
+def launch_batch(stage: BatchStage, upload: torch.Tensor, out: torch.Tensor, workspace: torch.Tensor, rounds: int) -> None:
+    """One scg_jpegdec_decode_batch on the current stream of the upload's device; the table block lies at the upload's front."""
+    dev = upload.device
+    with torch.cuda.device(dev):
+        check(_lib_jpegdec.load().scg_jpegdec_decode_batch(
+            stage.n, stage.frames.ctypes.data_as(C.POINTER(C.c_int32)), stage.table.ctypes.data_as(C.POINTER(C.c_uint32)), upload.data_ptr(),
+            upload.data_ptr(), upload.numel(), out.data_ptr(), out.numel(), workspace.data_ptr(), workspace.numel(), int(rounds),
+            _lib.stream_of(dev, "jpeg_decode.decode_batch")), "scg_jpegdec_decode_batch")
+
+
+def _read(source):
+    if isinstance(source, (str, os.PathLike)):
+        with open(source, "rb") as fh:
+            return fh.read(), source
+    data = bytes(source)
+    return data, data
+
+
+@torch.no_grad()
+def decode_batch(sources, device="cuda", max_workspace_bytes: int = 4 << 30):
+    """What [decode(s) for s in sources] returns or raises (the exception of the first failing source in order), with every file
+    parse() accepts staged into ONE pinned buffer — table block, distinct header blocks, entropy-coded segments — for ONE upload,
+    ONE scg_jpegdec_decode_batch with min(FIRST_ROUNDS, max_rounds) sync launches and ONE host read of the 4 n status words.  A
+    file parse() refuses, and one whose status is not 0 (unsettled, truncated, damaged), goes through decode() afterwards.  A list
+    whose workspace would exceed max_workspace_bytes is split into consecutive chunks, each with its own upload and read.  The
+    outputs of a chunk are views of ONE buffer in input order, 16-byte aligned: images of one shape lie at a constant stride.
+    LAST: uploads, host_reads, headers (distinct header blocks), chunks, and per image status, rounds and route."""
+    dev = _device(device)
+    sources = list(sources)
+    n = len(sources)
+    report = dict(uploads=0, host_reads=0, headers=0, chunks=0, status=[None] * n, rounds=[None] * n, route=[None] * n)
+    LAST.clear()
+    LAST.update(report)
+    if n == 0:
+        return []
+    read = [_read(s) for s in sources]
+    infos = [parse(data) for data, _src in read]
+    results = [None] * n
+    accepted = [i for i in range(n) if infos[i] is not None]
+    at = 0
+    while at < len(accepted):
+        # the longest run of consecutive accepted files whose workspace fits (one file always goes)
+        k = len(accepted) - at
+        while True:
+            members = accepted[at:at + k]
+            stage = BatchStage([infos[i] for i in members], [read[i][0] for i in members]).plan()
+            if stage.workspace_bytes <= max_workspace_bytes or k == 1:
+                break
+            k = max(1, min(k - 1, k * int(max_workspace_bytes) // stage.workspace_bytes))
+        at += k
+        staged = _batch_staging(stage.nbytes)
+        stage.fill(staged.numpy())
+        upload = staged.to(dev, non_blocking=True)                                         # the chunk's ONE upload
+        out = torch.empty(max(stage.out_bytes, _ALIGN), dtype=torch.uint8, device=dev)
+        ws = _batch_workspace(stage.workspace_bytes, dev)
+        launch_batch(stage, upload, out, ws, min(FIRST_ROUNDS, stage.max_rounds))
+        status = ws[:16 * stage.n].view(torch.int32).cpu().numpy().astype(np.int64).reshape(stage.n, 4) & 0xFFFFFFFF      # the ONE read
+        report["uploads"] += 1
+        report["host_reads"] += 1
+        report["chunks"] += 1
+        report["headers"] += len(stage.headers)
+        for j, i in enumerate(members):
+            report["status"][i], report["rounds"][i] = int(status[j, 0]), int(status[j, 1])
+            if int(status[j, 0]) == 0:
+                first = int(stage.out_offsets[j])
+                shape = stage.shape(j)
+                results[i] = out[first:first + int(np.prod(shape))].view(shape)
+                report["route"][i] = "device"
+    for i in range(n):                                                                     # in order: the first failure raises
+        if results[i] is None:
+            results[i] = decode(read[i][1], dev)
+            report["host_reads"] += int(LAST.get("host_reads", 0))
+            report["uploads"] += 1
+            report["route"][i] = "single " + str(LAST.get("route"))
+    LAST.clear()
+    LAST.update(report)
+    return results
