@@ -11,7 +11,8 @@ of SIDE_LIBRARIES, each with a header directory, an ABI version and an error str
     libscg_png.so   include/png   PNG files' zlib streams
     libscg_jpg.so   include/jpg   JPEG files, the frames of a Motion-JPEG video
 
-and, outside the table, libscg_jpegdec.so (csrc/dec: the JPEG decoder, build_decoder below).
+and, outside the table, libscg_jpegdec.so (csrc/dec: the JPEG decoder, build_decoder below) and libscg_camgrad.so (csrc/cam: the
+rasterizer's camera gradients, build_camera_grad below).
 
 hipcc cross-compiles without a GPU; the libraries are git-ignored.  A source whose results are held to another
 implementation's bits is compiled with -ffp-contract=off, one rounding per operation: the comment next to each such source in the
@@ -190,25 +191,50 @@ def decoder_headers():
     return _h(DECODER_DIR) + [os.path.join(CSRC, h) for h in DECODER_INCLUDES] + [os.path.join(INCLUDE, "scg_raster.h")]
 
 
-def build_decoder(force: bool = False, verbose: bool = False) -> str:
-    """libscg_jpegdec.so, with a digest of its own."""
+def _build_own(src: str, obj_name: str, flags, headers, lib_path: str, force: bool, verbose: bool) -> str:
+    """One source -> one library outside the tables, with a digest of its own over `src`, `headers` and the flags."""
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
-    src = os.path.join(DECODER_DIR, DECODER_SOURCE)
-    obj = os.path.join(OBJ_DIR, "dec_" + DECODER_SOURCE.replace(".hip", ".o"))
+    obj = os.path.join(OBJ_DIR, obj_name)
     stamp = obj + ".sha"
-    dig = _digest([src] + decoder_headers(), " ".join(COMMON + DECODER_FLAGS))
+    dig = _digest([src] + headers, " ".join(COMMON + flags))
     fresh = not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == dig
     if not fresh:
-        cmd = [hipcc] + COMMON + DECODER_FLAGS + ["-c", src, "-o", obj]
+        cmd = [hipcc] + COMMON + flags + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
         with open(stamp, "w") as fh:
             fh.write(dig)
-    if not fresh or not os.path.exists(DECODER_LIB):
-        _link(hipcc, DECODER_LIB, [obj], verbose)
-    return DECODER_LIB
+    if not fresh or not os.path.exists(lib_path):
+        _link(hipcc, lib_path, [obj], verbose)
+    return lib_path
+
+
+def build_decoder(force: bool = False, verbose: bool = False) -> str:
+    """libscg_jpegdec.so, with a digest of its own."""
+    return _build_own(os.path.join(DECODER_DIR, DECODER_SOURCE), "dec_" + DECODER_SOURCE.replace(".hip", ".o"), DECODER_FLAGS,
+                      decoder_headers(), DECODER_LIB, force, verbose)
+
+
+# The camera gradients (csrc/cam/camgrad.hip, its C ABI and its rule in csrc/cam/scg_camgrad.h): a library of its own outside the
+# tables, for the decoder's reason.  -ffp-contract=off: it recomputes the forward's colour clamp and must take the forward's
+# decision, i.e. evaluate geometry.hip's chain of single fp32 operations (csrc/geometry_math.h, csrc/sh_eval.h).
+CAMGRAD_DIR = os.path.join(CSRC, "cam")
+CAMGRAD_LIB = os.path.join(HERE, "libscg_camgrad.so")
+CAMGRAD_SOURCE, CAMGRAD_FLAGS = "camgrad.hip", ["-ffp-contract=off"]
+CAMGRAD_INCLUDES = ("geometry_math.h", "host_align.h", "host_error.h", "reduce.h", "scg_common.h", "sh_eval.h")   # the csrc/*.h it includes
+
+
+def camera_grad_headers():
+    """What the camera-gradient library's digest covers besides its source: csrc/cam/*.h, the csrc/*.h it includes, include/scg_raster.h."""
+    return _h(CAMGRAD_DIR) + [os.path.join(CSRC, h) for h in CAMGRAD_INCLUDES] + [os.path.join(INCLUDE, "scg_raster.h")]
+
+
+def build_camera_grad(force: bool = False, verbose: bool = False) -> str:
+    """libscg_camgrad.so, with a digest of its own."""
+    return _build_own(os.path.join(CAMGRAD_DIR, CAMGRAD_SOURCE), "cam_" + CAMGRAD_SOURCE.replace(".hip", ".o"), CAMGRAD_FLAGS,
+                      camera_grad_headers(), CAMGRAD_LIB, force, verbose)
 
 
 def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(), flags=(), only=None) -> str:
@@ -233,6 +259,7 @@ def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(),
         for key in SIDE_LIBRARIES:
             build_side(key, force=force, verbose=verbose)
         build_decoder(force=force, verbose=verbose)
+        build_camera_grad(force=force, verbose=verbose)
     return lib_path
 
 

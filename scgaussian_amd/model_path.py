@@ -213,7 +213,11 @@ def rasterize_model(raster_settings, means2D: torch.Tensor, _args: Optional[_Mod
     (model_for), in place of the keyword arguments."""
     R._require_cuda(means2D)
     ts = _args.tensors if _args is not None else tuple(tensors[n] for n in ARG_NAMES)
-    return _RasterizeModel.apply(means2D, *ts, raster_settings, _args)
+    apply = _RasterizeModel.apply
+    if R._camera_wants_grad((raster_settings,)):
+        from . import camera_grad                            # (it imports this module)
+        apply = camera_grad.apply_model
+    return apply(means2D, *ts, raster_settings, _args)
 
 
 class _RasterizeModelViews(torch.autograd.Function):
@@ -243,7 +247,11 @@ def rasterize_model_views(settings_list, means2D: torch.Tensor, _args: Optional[
     if means2D.dim() != 3 or means2D.shape[0] != K:
         raise ValueError(f"means2D must be ({K}, P, 3): one screen-space gradient slot per view")
     ts = _args.tensors if _args is not None else tuple(tensors[n] for n in ARG_NAMES)
-    flat = _RasterizeModelViews.apply(means2D, *ts, list(settings_list), _args)
+    apply = _RasterizeModelViews.apply
+    if R._camera_wants_grad(settings_list):
+        from . import camera_grad                            # (it imports this module)
+        apply = camera_grad.apply_model_views
+    flat = apply(means2D, *ts, list(settings_list), _args)
     return [tuple(flat[4 * k: 4 * k + 4]) for k in range(K)]
 
 

@@ -15,7 +15,8 @@ computation runs in hand-written HIP kernels behind include/scg_raster.h.  There
 What lives where: this module owns the operator — the forwards and the backward as sequences of library calls (forward_fused: mode,
 capacity look-up, _launch_forward per attempt, overflow retry), the module switches, the K-view core of the four autograd nodes.
 The capacity policy with its tables, pinned partial sums, workspace plans and count words: _counts.py; frames and per-camera launch
-hints: _frames.py; the gradient arena: _grads.py; camera identity: _cameras.py; the stage timer: _timing.py; option and flag bits: _lib.py.
+hints: _frames.py; the gradient arena: _grads.py; camera identity: _cameras.py; the stage timer: _timing.py; option and flag bits: _lib.py;
+the gradients with respect to the camera (sibling nodes of the four, the pass _backward_view calls for them): camera_grad.py.
 
 Concurrency: the operator is re-entrant per device and stream, like the upstream extension — every forward takes its own
 pinned scratch (the partial sums of num_rendered) from a per-device pool, so two threads, each on its own stream, may be
@@ -381,6 +382,11 @@ def _backward_view(state, inputs, radii, dL_dcolor, dL_ddepth, dL_dalpha, timer:
             _grads.invalidate_promise(pa)
             raise
         _grads.commit_promise(pa, n_active, into is not None)
+    camera_pass = state.get("camera_pass")
+    if camera_pass is not None:
+        # a node that also differentiates the camera (camera_grad.py) armed this view: its pass runs here, behind the geometry
+        # backward, while the view's gradient records are in this function's hands
+        camera_pass(state, inputs, radii, records, dev)
     if want_dsplats:
         out["dsplats"] = dsplats
     return out
@@ -652,6 +658,17 @@ def _caller_grads(ctx, g, d_means2D):
             g["colors_precomp"], _shape(g["opacities"], opac_shape), g["scales"], g["rotations"], g["cov3D_precomp"])
 
 
+def _camera_wants_grad(settings_list) -> bool:
+    """A camera tensor of one of these settings requires grad (and grad mode is on): the call goes through camera_grad.py's nodes."""
+    if not torch.is_grad_enabled():
+        return False
+    for st in settings_list:
+        if getattr(st.viewmatrix, "requires_grad", False) or getattr(st.projmatrix, "requires_grad", False) or \
+                getattr(st.campos, "requires_grad", False):
+            return True
+    return False
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
@@ -719,10 +736,14 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                         raster_settings):
     args = (means3D, means2D, _none_if_empty(sh), _none_if_empty(colors_precomp), opacities, _none_if_empty(scales),
             _none_if_empty(rotations), _none_if_empty(cov3Ds_precomp), raster_settings)
+    apply = _RasterizeGaussians.apply
+    if _camera_wants_grad((raster_settings,)):
+        from . import camera_grad                            # (it imports this module)
+        apply = camera_grad.apply_gaussians
     if not raster_settings.debug:
-        return _RasterizeGaussians.apply(*args)
+        return apply(*args)
     try:
-        return _RasterizeGaussians.apply(*args)
+        return apply(*args)
     except Exception:
         _debug_dump(DEBUG_SNAPSHOT_FW, "forward", raster_settings,
                     dict(means3D=means3D, means2D=means2D, sh=args[2], colors_precomp=args[3], opacities=opacities,
@@ -793,6 +814,9 @@ class GaussianRasterizerViews(nn.Module):
         K = len(self.raster_settings_list)
         if means2D.dim() != 3 or means2D.shape[0] != K:
             raise ValueError(f"means2D must be ({K}, P, 3): one screen-space gradient slot per view")
-        flat = _RasterizeViews.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                     self.raster_settings_list)
+        apply = _RasterizeViews.apply
+        if _camera_wants_grad(self.raster_settings_list):
+            from . import camera_grad                        # (it imports this module)
+            apply = camera_grad.apply_views
+        flat = apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, self.raster_settings_list)
         return [tuple(flat[4 * k: 4 * k + 4]) for k in range(K)]
