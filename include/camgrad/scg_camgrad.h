@@ -1,7 +1,7 @@
-/* scg_camgrad.h — C ABI of libscg_camgrad.so: the rasterizer's gradient with respect to the CAMERA (csrc/cam/camgrad.hip, gfx950):
+/* scg_camgrad.h — C ABI of libscg_camgrad.so: the rasterizer's gradient with respect to the CAMERA (camgrad.hip in csrc/, gfx950):
  * dL/dviewmatrix, dL/dprojmatrix and dL/dcampos of one view from the per-Gaussian gradient records its blend backward left.
  *
- * A library of its own OUTSIDE include/ and the build tables (build.build_camera_grad), as libscg_jpegdec.so is.  Conventions as in
+ * A side library (build.SIDE_LIBRARIES "camgrad").  Conventions as in
  * the other libraries: plain C, pointers and scalars only, `void* stream` is a hipStream_t (NULL = the default stream), every launch
  * is asynchronous on it, return value 0 = ok, < 0 = invalid argument (the SCG_E_* codes of scg_raster.h), > 0 = a hipError_t; the
  * message of the last failure of the calling thread is scg_camgrad_last_error().  Every argument is validated before anything touches
@@ -40,9 +40,9 @@
 #ifndef SCG_CAMGRAD_H
 #define SCG_CAMGRAD_H
 
-#include "../../../include/scg_raster.h"
+#include "../scg_raster.h"
 
-#define SCG_CAMGRAD_ABI_VERSION 1
+#define SCG_CAMGRAD_ABI_VERSION 2
 #define SCG_CAMGRAD_BLOCK 256             /* Gaussians (threads) of a workgroup of the first launch */
 #define SCG_CAMGRAD_SUMS 27               /* live sums: floats of one workgroup's partial record */
 #define SCG_CAMGRAD_OUT_FLOATS 35         /* dV (16) | dPM (16) | dcampos (3) */
@@ -54,7 +54,7 @@ extern "C" {
 #endif
 
 SCG_API const char* scg_camgrad_last_error(void);
-SCG_API int32_t scg_camgrad_version(void);
+SCG_API int32_t scg_camgrad_abi_version(void);
 
 /* Host only.  The workgroups of the first launch for P >= 0 Gaussians and the bytes of `partials` (0 for P = 0). */
 SCG_API int scg_camgrad_sizes(int32_t P, int32_t* n_blocks, uint64_t* partial_bytes);

@@ -1,9 +1,8 @@
-/* scg_jpegdec.h — C ABI of libscg_jpegdec.so: baseline JPEG files decoded on the GPU (csrc/dec/jpegunpack.hip, gfx950).  The reading
+/* scg_jpegdec.h — C ABI of libscg_jpegdec.so: baseline JPEG files decoded on the GPU (csrc/jpegunpack.hip, gfx950).  The reading
  * direction of include/jpg/scg_jpeg.h: the file's bytes are uploaded, the tight uint8 (H, W, 3) or (H, W) pixels appear on the
  * device, the pixels np.asarray(Image.open(path)) gives (Pillow on libjpeg-turbo), byte for byte.
  *
- * A library of its own OUTSIDE include/ and the build tables (build.build_decoder; it joins SIDE_LIBRARIES when the tests that
- * pin the tables may next be edited).  Conventions as in the other libraries: plain C, pointers and scalars only, `void* stream`
+ * A side library (build.SIDE_LIBRARIES "jpegdec").  Conventions as in the other libraries: plain C, pointers and scalars only, `void* stream`
  * is a hipStream_t (NULL = the default stream), every launch is asynchronous on it, return value 0 = ok, < 0 = invalid argument
  * (the SCG_E_* codes of scg_raster.h), > 0 = a hipError_t; the message of the last failure of the calling thread is
  * scg_jpegdec_last_error().  Every argument is validated before anything touches a device.  The caller owns all buffers: nothing
@@ -106,7 +105,7 @@
 #ifndef SCG_JPEGDEC_H
 #define SCG_JPEGDEC_H
 
-#include "../../../include/scg_raster.h"
+#include "../scg_raster.h"
 
 #define SCG_JPEGDEC_ABI_VERSION 2
 #define SCG_JPEGDEC_SUBSEQ 128            /* bytes of a subsequence: one thread's share of the stream */

@@ -1,8 +1,8 @@
-"""ctypes binding of libscg_jpegdec.so (csrc/dec/scg_jpegdec.h): baseline JPEG files decoded on the GPU.
+"""ctypes binding of libscg_jpegdec.so (include/jpegdec/scg_jpegdec.h): baseline JPEG files decoded on the GPU.
 
-A library of its own with a version and an error string of its own, built by build.build_decoder (it is not an entry of
-build.SIDE_LIBRARIES yet: see there).  As for the others: a missing library raises, there is no quiet stand-in for a kernel.
-tests/test_jpegdec_cpu.py holds SYMBOLS and the constants to the header's text.
+A library next to libscg_raster.so with a version and an error string of its own (build.SIDE_LIBRARIES["jpegdec"]).  As there: a
+missing library raises, there is no quiet stand-in for a kernel.  tests/test_jpegdec_cpu.py holds SYMBOLS and the constants to
+the header's text.
 """
 from __future__ import annotations
 
@@ -15,7 +15,6 @@ from ._lib import open_library, raise_last_error
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libscg_jpegdec.so")
-HEADER_PATH = os.path.join(_HERE, "csrc", "dec", "scg_jpegdec.h")
 
 # the header's integer #defines under their own names minus "SCG_"
 JPEGDEC_ABI_VERSION = ABI_VERSION = 2

@@ -10,9 +10,8 @@ of SIDE_LIBRARIES, each with a header directory, an ABI version and an error str
     libscg_lp.so    include/lp    the LPIPS metric (VGG16 on the fp32 matrix pipe)
     libscg_png.so   include/png   PNG files' zlib streams
     libscg_jpg.so   include/jpg   JPEG files, the frames of a Motion-JPEG video
-
-and, outside the table, libscg_jpegdec.so (csrc/dec: the JPEG decoder, build_decoder below) and libscg_camgrad.so (csrc/cam: the
-rasterizer's camera gradients, build_camera_grad below).
+    libscg_jpegdec.so  include/jpegdec  baseline JPEG files decoded (Pillow's pixels)
+    libscg_camgrad.so  include/camgrad  the rasterizer's camera gradients (view, projection, centre)
 
 hipcc cross-compiles without a GPU; the libraries are git-ignored.  A source whose results are held to another
 implementation's bits is compiled with -ffp-contract=off, one rounding per operation: the comment next to each such source in the
@@ -83,6 +82,14 @@ SIDE_LIBRARIES = {
     }),
     "jpg": ("jpg", {    # include/jpg/scg_jpeg.h
         "jpegpack.hip": ["-ffp-contract=off"],    # integer arithmetic only; the flag says that the bytes are held to libjpeg's
+    }),
+    "jpegdec": ("jpegdec", {    # include/jpegdec/scg_jpegdec.h
+        "jpegunpack.hip": ["-ffp-contract=off"],  # integer arithmetic only; the flag says, as for the packer, that the bytes are held to another implementation's (Pillow's pixels)
+    }),
+    "camgrad": ("camgrad", {    # include/camgrad/scg_camgrad.h
+        # it recomputes the forward's colour clamp and must take the forward's decision, i.e. evaluate geometry.hip's chain of
+        # single fp32 operations (csrc/geometry_math.h, csrc/sh_eval.h)
+        "camgrad.hip": ["-ffp-contract=off"],
     }),
 }
 
@@ -176,67 +183,6 @@ def build_side(key: str, force: bool = False, verbose: bool = False) -> str:
     return lib_path
 
 
-# The JPEG decoder (csrc/dec/jpegunpack.hip, its C ABI in csrc/dec/scg_jpegdec.h): a library of its own that is NOT an entry of
-# SIDE_LIBRARIES and has no header under include/ — the tests that pin the table's keys and demand a guard-band case per prototype
-# under include/ are fixed, so it joins the table (key "jpegdec", include/jpegdec/) when those tests may next be edited.  Integer
-# arithmetic only; -ffp-contract=off says, as for the packer, that the bytes are held to another implementation's (Pillow's pixels).
-DECODER_DIR = os.path.join(CSRC, "dec")
-DECODER_LIB = os.path.join(HERE, "libscg_jpegdec.so")
-DECODER_SOURCE, DECODER_FLAGS = "jpegunpack.hip", ["-ffp-contract=off"]
-DECODER_INCLUDES = ("compact.h", "host_align.h", "host_error.h", "scg_common.h")      # the csrc/*.h it includes
-
-
-def decoder_headers():
-    """What the decoder's digest covers besides its source: csrc/dec/*.h, the csrc/*.h it includes, include/scg_raster.h."""
-    return _h(DECODER_DIR) + [os.path.join(CSRC, h) for h in DECODER_INCLUDES] + [os.path.join(INCLUDE, "scg_raster.h")]
-
-
-def _build_own(src: str, obj_name: str, flags, headers, lib_path: str, force: bool, verbose: bool) -> str:
-    """One source -> one library outside the tables, with a digest of its own over `src`, `headers` and the flags."""
-    os.makedirs(OBJ_DIR, exist_ok=True)
-    hipcc = _hipcc()
-    obj = os.path.join(OBJ_DIR, obj_name)
-    stamp = obj + ".sha"
-    dig = _digest([src] + headers, " ".join(COMMON + flags))
-    fresh = not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == dig
-    if not fresh:
-        cmd = [hipcc] + COMMON + flags + ["-c", src, "-o", obj]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
-        with open(stamp, "w") as fh:
-            fh.write(dig)
-    if not fresh or not os.path.exists(lib_path):
-        _link(hipcc, lib_path, [obj], verbose)
-    return lib_path
-
-
-def build_decoder(force: bool = False, verbose: bool = False) -> str:
-    """libscg_jpegdec.so, with a digest of its own."""
-    return _build_own(os.path.join(DECODER_DIR, DECODER_SOURCE), "dec_" + DECODER_SOURCE.replace(".hip", ".o"), DECODER_FLAGS,
-                      decoder_headers(), DECODER_LIB, force, verbose)
-
-
-# The camera gradients (csrc/cam/camgrad.hip, its C ABI and its rule in csrc/cam/scg_camgrad.h): a library of its own outside the
-# tables, for the decoder's reason.  -ffp-contract=off: it recomputes the forward's colour clamp and must take the forward's
-# decision, i.e. evaluate geometry.hip's chain of single fp32 operations (csrc/geometry_math.h, csrc/sh_eval.h).
-CAMGRAD_DIR = os.path.join(CSRC, "cam")
-CAMGRAD_LIB = os.path.join(HERE, "libscg_camgrad.so")
-CAMGRAD_SOURCE, CAMGRAD_FLAGS = "camgrad.hip", ["-ffp-contract=off"]
-CAMGRAD_INCLUDES = ("geometry_math.h", "host_align.h", "host_error.h", "reduce.h", "scg_common.h", "sh_eval.h")   # the csrc/*.h it includes
-
-
-def camera_grad_headers():
-    """What the camera-gradient library's digest covers besides its source: csrc/cam/*.h, the csrc/*.h it includes, include/scg_raster.h."""
-    return _h(CAMGRAD_DIR) + [os.path.join(CSRC, h) for h in CAMGRAD_INCLUDES] + [os.path.join(INCLUDE, "scg_raster.h")]
-
-
-def build_camera_grad(force: bool = False, verbose: bool = False) -> str:
-    """libscg_camgrad.so, with a digest of its own."""
-    return _build_own(os.path.join(CAMGRAD_DIR, CAMGRAD_SOURCE), "cam_" + CAMGRAD_SOURCE.replace(".hip", ".o"), CAMGRAD_FLAGS,
-                      camera_grad_headers(), CAMGRAD_LIB, force, verbose)
-
-
 def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(), flags=(), only=None) -> str:
     """tag/defines build a VARIANT libscg_raster_<tag>.so (selected at run time with SCG_LIB_PATH); the default build has
     neither and builds every side library behind the main one.  `only`: the sources the defines / flags apply to — the others
@@ -258,8 +204,6 @@ def build(force: bool = False, verbose: bool = False, tag: str = "", defines=(),
     if not tag:
         for key in SIDE_LIBRARIES:
             build_side(key, force=force, verbose=verbose)
-        build_decoder(force=force, verbose=verbose)
-        build_camera_grad(force=force, verbose=verbose)
     return lib_path
 
 

@@ -1,5 +1,5 @@
 """The rasterizer's gradient with respect to the camera: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos (libscg_camgrad.so,
-csrc/cam/scg_camgrad.h states the rule).
+include/camgrad/scg_camgrad.h states the rule).
 
     dV, dPM, dcampos = camera_backward(settings, inputs, radii, dsplats)        # the plain call, on one view's gradient records
 

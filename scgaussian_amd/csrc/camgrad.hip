@@ -9,16 +9,16 @@
 // partials[block][27].  camgrad_finish_kernel: one workgroup folds the partials in fp64 in block order and writes the 35 floats.
 // No atomics, no host read, nothing allocated: bitwise reproducible and capturable.
 //
-// Compiled with -ffp-contract=off (build.build_camera_grad): the colour clamp is RECOMPUTED here and must take the forward's
+// Compiled with -ffp-contract=off (build.SIDE_LIBRARIES): the colour clamp is RECOMPUTED here and must take the forward's
 // decision, i.e. evaluate the forward's chain of single fp32 operations (csrc/sh_eval.h at the direction geometry_forward_one forms).
-#include "scg_camgrad.h"
+#include "../../include/camgrad/scg_camgrad.h"
 
-#include "../scg_common.h"
-#include "../host_align.h"
-#include "../host_error.h"
-#include "../reduce.h"
-#include "../sh_eval.h"
-#include "../geometry_math.h"
+#include "scg_common.h"
+#include "host_align.h"
+#include "host_error.h"
+#include "reduce.h"
+#include "sh_eval.h"
+#include "geometry_math.h"
 
 #pragma clang fp contract(off)
 
@@ -304,7 +304,7 @@ using namespace scg;
 extern "C" {
 
 const char* scg_camgrad_last_error(void) { return g_err.text; }
-int32_t scg_camgrad_version(void) { return SCG_CAMGRAD_ABI_VERSION; }
+int32_t scg_camgrad_abi_version(void) { return SCG_CAMGRAD_ABI_VERSION; }
 
 int scg_camgrad_sizes(int32_t P, int32_t* n_blocks, uint64_t* partial_bytes) {
     const char* who = "scg_camgrad_sizes";

@@ -1,4 +1,4 @@
-// jpegunpack.hip — libscg_jpegdec.so: baseline JPEG files decoded on the GPU (csrc/dec/scg_jpegdec.h states the rule and the call; it
+// jpegunpack.hip — libscg_jpegdec.so: baseline JPEG files decoded on the GPU (include/jpegdec/scg_jpegdec.h states the rule and the call; it
 // is the contract, and tests/jpegdec_refs.py restates it in numpy).
 //
 // The entropy-coded segment is one serial bit stream.  It is decoded in parallel and exactly by the self-synchronising scheme: a
@@ -17,13 +17,13 @@
 // jpegdec_batch_* kernel from the image table of scg_jpegdec_decode_batch, where a workgroup finds its image from blockIdx.x alone.
 // One decode function (run<kMode>) serves sync, count and write, so the three cannot disagree about a state.  No workgroup waits
 // for another, nothing is allocated, no float atomics; the same input gives the same bytes.
-#include "scg_jpegdec.h"
+#include "../../include/jpegdec/scg_jpegdec.h"
 
 #include <string.h>
 
-#include "../compact.h"
-#include "../host_align.h"
-#include "../host_error.h"
+#include "compact.h"
+#include "host_align.h"
+#include "host_error.h"
 
 namespace scg {
 namespace {

@@ -1,4 +1,4 @@
-"""JPEG files decoded on the GPU, host side (libscg_jpegdec.so; csrc/dec/scg_jpegdec.h states the rule and the call).
+"""JPEG files decoded on the GPU, host side (libscg_jpegdec.so; include/jpegdec/scg_jpegdec.h states the rule and the call).
 
     u8 = jpeg_decode.decode(path_or_bytes)        device uint8 (H, W, 3) or (H, W) == np.asarray(Image.open(path)), ONE host read
     info = jpeg_decode.parse(data)                host only: the frame, the tables, the bounds of the entropy-coded segment, or None

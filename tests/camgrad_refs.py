@@ -1,4 +1,4 @@
-"""fp64 numpy restatement of the camera-gradient rule (scgaussian_amd/csrc/cam/scg_camgrad.h): from (inputs, camera, gradient
+"""fp64 numpy restatement of the camera-gradient rule (include/camgrad/scg_camgrad.h): from (inputs, camera, gradient
 records, radii) to the 35 numbers dL/dviewmatrix (16) | dL/dprojmatrix (16) | dL/dcampos (3).
 
 Written from the header in MATRIX form (T = J W, cov2D = T Sigma T^T + 0.3 I, conic = cov2D^-1, dL/dcov2D = -Q G Q), not from the

@@ -1,4 +1,4 @@
-"""The JPEG decoder's rule restated in numpy (scgaussian_amd/csrc/dec/scg_jpegdec.h states it; the kernels of csrc/dec/jpegunpack.hip
+"""The JPEG decoder's rule restated in numpy (include/jpegdec/scg_jpegdec.h states it; the kernels of csrc/jpegunpack.hip
 are held to this file byte for byte, and this file to np.asarray(Image.open(...)) of Pillow on libjpeg-turbo).
 
     decode(data, mutant=None)          the pixels of a baseline file: uint8 (H, W, 3) or (H, W)

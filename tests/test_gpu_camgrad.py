@@ -117,8 +117,10 @@ def test_views_rasterizer_returns_per_view_camera_gradients():
     pu.assert_close(pairs[1][1][2].grad, torch.from_numpy(_oracle(1)[0][32:].copy()).float(), ("views", "campos alone"))
 
 
-def _raw_model(ray_fraction=0.6):
-    model = syn.make_raw_model(_scene(), ray_fraction=ray_fraction, seed=7)
+def _raw_model(ray_fraction=0.6, n=None):
+    """The raw model of the small scene, or of its first n Gaussians."""
+    sc = _scene() if n is None else syn.Scene(*[t[:n].contiguous() for t in _scene()])
+    model = syn.make_raw_model(sc, ray_fraction=ray_fraction, seed=7)
     model.active_sh_degree = DEG
     md = model.to(DEV)
     md.requires_grad_()
@@ -155,10 +157,12 @@ def _seven(inputs):
     return tuple(None if inputs.get(n) is None else inputs[n].detach().to(DEV).contiguous() for n in NAMES7)
 
 
-def _kernel(inputs, cam, deg, mod, records, radii, want_campos=True, seven=None, **kw):
-    st = pu.hip_settings(cam, deg, (0.0, 0.0, 0.0), mod)
-    out = camera_grad.camera_backward(st, _seven(inputs) if seven is None else seven, radii.to(DEV).contiguous(),
-                                      records.to(DEV).contiguous(), want_campos, **kw)
+def _kernel(inputs, cam, deg, mod, records, radii, want_campos=True, seven=None, home=lambda x: x, **kw):
+    """home: what every device tensor handed to the call goes through first (tests/test_gpu_guard_bands.py moves them into guarded
+    buffers with it; here the identity)."""
+    st = home(pu.hip_settings(cam, deg, (0.0, 0.0, 0.0), mod))
+    out = camera_grad.camera_backward(st, home(_seven(inputs)) if seven is None else seven, home(radii.to(DEV).contiguous()),
+                                      home(records.to(DEV).contiguous()), want_campos, **kw)
     torch.cuda.synchronize()
     assert [tuple(o.shape) for o in out] == [(4, 4), (4, 4), (3,)]
     return torch.cat([o.reshape(-1) for o in out]).cpu().double().numpy()

@@ -32,7 +32,14 @@ pngpack.hip checks a chunk's image index against the image count; jpegpack.hip t
 [0, images) and its row in [0, the image's segments) and names this very workgroup (segment_of), clamps every pixel index to the
 image, and reads a header template at the offset the entry point checked against the templates' size; resample.hip clamps the column index to wout - 1 and a bound to
 [0, win - 1]; the geocheck pair table is written by scg_geocheck_setup itself; scg_sort_pairs and scg_inclusive_scan_u32 take
-their integers as values, never as addresses; scg_densify_stats compares radii with 0.
+their integers as values, never as addresses; scg_densify_stats compares radii with 0; jpegunpack.hip: a batched workgroup finds
+its image by a search of the prefix table inside [0, n - 1] and goes on only when first[image] <= its index < first[image] + the
+image's own group count; a record of the device table is followed only when frame_from accepts its frame and the header block, the
+segment, the pixels and each of the ten workspace regions lie, offset and size, inside upload_bytes, out_bytes and workspace_bytes as
+the call was passed them (view_of_image), every index into the header block is masked (look[peek >> 8], vals[.. & 255], table id & 1,
+quant id & 3), a stream read stops at the segment's bytes and a coefficient is stored only for a block below the frame's count;
+camgrad.hip reads radii, inputs and records at min(i, P - 1), compares radii with 0 and splits i at model.ray.count, which the entry
+point held to P.
 
 Scratch words, audited by reading before the first poisoned run — per family: the words a kernel reads or updates atomically, and
 who wrote or cleared them earlier in the same call (K: the kernel itself or an earlier launch of the call; M: a hipMemsetAsync on
@@ -80,10 +87,21 @@ on this reading and on the cases below, not on a proof.
                       last one before the encode kernel reads flag, offset and base[s], base[s + 1]; the window, the code tables and
                       the DC history are LDS, cleared behind a barrier; the image table is uploaded by _bind, the segment and header
                       tables by the plan; a flagged file's capacity and the gaps between the files in `out` belong to nobody
+  jpegunpack.hip      the status words and the change counters (all images' in the batch): M, one clear; the coefficient buffers: M,
+                      the second clear; entry, exit: K, sync launch 0 stores every subsequence's before a later launch or the
+                      count reads them; bnd: K, every workgroup stores its word in every launch, launch k + 1 reads what launch k
+                      stored and launch 0 reads none; cnt, dcs: K, the count stores every subsequence's before the scan and the
+                      write read them; the planes: K, the idct stores every block of the padded planes before the colour kernel
+                      reads inside them; out: K, every byte of H W components; the alignment gaps between regions and between
+                      the batch's images belong to nobody
+  camgrad.hip         partials: K, every workgroup stores its 27 words (a wave without a visible Gaussian adds zeros) before the
+                      one finishing workgroup reads [0, blocks) x 27; out35: K, all 35 words, the twelve dead ones as 0, also at
+                      P = 0 and with everything culled
   plypack.hip, mono.hip: no scratch; every byte of the buffer / arena region an entry owns is written by it; the tables the mono
                       kernels index are uploaded from the host copy
 """
 import contextlib
+import functools
 import glob
 import math
 import os
@@ -139,8 +157,8 @@ def _name_of(entry, path):
 # ---- the binding's libraries, traced ---------------------------------------------------------------------------------------------
 
 def _lib_modules():
-    from scgaussian_amd import _lib, _lib_img, _lib_io, _lib_jpg, _lib_lp, _lib_mp, _lib_png, _lib_vw
-    return (_lib, _lib_io, _lib_img, _lib_mp, _lib_vw, _lib_lp, _lib_png, _lib_jpg)
+    from scgaussian_amd import _lib, _lib_camgrad, _lib_img, _lib_io, _lib_jpegdec, _lib_jpg, _lib_lp, _lib_mp, _lib_png, _lib_vw
+    return (_lib, _lib_io, _lib_img, _lib_mp, _lib_vw, _lib_lp, _lib_png, _lib_jpg, _lib_jpegdec, _lib_camgrad)
 
 
 @contextlib.contextmanager
@@ -161,13 +179,15 @@ def tracing():
 def _clear_caches():
     """The binding's process-global caches hold device buffers of earlier tests: emptied here, in place (other modules hold the same
     dictionaries by name), so that every buffer of a case is allocated inside its own guarded run (condition 2 fails otherwise)."""
-    from scgaussian_amd import _counts, _grads, model_path, rasterizer
+    from scgaussian_amd import _counts, _grads, jpeg_decode, model_path, rasterizer
     rasterizer._FRAME_CACHE.clear()
     rasterizer._CAM_HINTS.clear()
     _grads._ARENA_POOLS.clear()
     _grads._LAYOUTS.clear()
     model_path._ACCEPTS.clear()
     _counts._SPEC_STATE.clear()
+    jpeg_decode._PLANS.clear()                                    # (images.py keeps no decode plan of its own: it calls jpeg_decode)
+    jpeg_decode._BATCH_BUFFERS.clear()
 
 
 # ---- a case --------------------------------------------------------------------------------------------------------------------------
@@ -1137,6 +1157,158 @@ def _model_path(nr, nb, deg, scene="random"):
                 fields={"scg_backward_model": fields + ["frame.bwd_cost_out"], "scg_forward_model": ["frame.tile_cost_out"]})
 
 
+# ---- the JPEG decoder (jpegdec/scg_jpegdec.h) --------------------------------------------------------------------------------------
+
+UPLOADED = "the file's bytes and its header block, uploaded by the wrapper with .to(device) from pinned memory"
+JPEGDEC_LONG = (88, 96)                                           # noise at quality 100, 4:4:4: a segment of two workgroups
+
+
+@functools.lru_cache(maxsize=None)
+def _jpegdec_small():
+    """[(name, file, the restatement's pixels)]: the smallest sizes of test_gpu_jpegdec.SIZES at each sampling, one component, a
+    restart interval, and a segment of one subsequence and a byte.  Computed once."""
+    import jpegdec_refs as R
+    files = [(f"{H}x{W}-{sampling}", R.pillow_file(R.image(H, W, 3, "noise"), 90, sampling))
+             for (H, W) in ((1, 1), (7, 9), (17, 33), (3, 50)) for sampling in R.SAMPLINGS]
+    files.append(("7x9-one-component", R.pillow_file(R.image(7, 9, 1, "noise"), 90)))
+    files.append(("17x33-restart", R.pillow_file(R.image(17, 33, 3, "noise"), 90, "4:2:0", restart_blocks=1)))
+    files.append(("subsequence+1", R.segment_of_length(R.SUBSEQ + 1)))
+    assert b"\xff\xd0" in files[-2][1] and R.segment_bytes(files[-1][1]) == R.SUBSEQ + 1
+    return [(name, data, R.decode(data)) for name, data in files]
+
+
+@functools.lru_cache(maxsize=None)
+def _jpegdec_long():
+    import jpegdec_refs as R
+    data = R.pillow_file(R.image(*JPEGDEC_LONG, 3, "noise"), 100, "4:4:4")
+    assert R.segment_bytes(data) >= R.SUBSEQ * R.THREADS + 1 and b"\xff\xd0" not in data      # more than one workgroup, no marker
+    return "long", data, R.decode(data)
+
+
+def _jpegdec_single():
+    def run(home):
+        from scgaussian_amd import jpeg_decode
+        out = {}
+        for name, data, want in _jpegdec_small() + [_jpegdec_long()]:
+            got = jpeg_decode.decode(data, DEV)
+            last = dict(jpeg_decode.LAST)
+            assert last["route"] == "device" and last["status"] == 0, (name, last)      # (never through Pillow on the host)
+            assert np.array_equal(got.cpu().numpy(), want), name
+            if name == "long":                                    # hand-over words across workgroups, more than one sync launch
+                assert last["launched"] > 1 and 1 < last["rounds"] <= last["launched"], last
+            out[name] = got
+        return out
+    return Case("jpegdec-single", run, ["scg_jpegdec_decode"],
+                excused={"scg_jpegdec_decode": {"header_dev": UPLOADED, "segment_dev": UPLOADED}})
+
+
+def _jpegdec_batch():
+    """The small files in one list: several share a header block (one quality, the standard tables), two have one shape, and a
+    progressive file in the middle is refused by parse() and decoded alone afterwards; then the list again in two chunks."""
+    def run(home):
+        import jpegdec_refs as R
+        from scgaussian_amd import jpeg_decode
+        small = _jpegdec_small()
+        twin = R.pillow_file(R.image(7, 9, 3, "noise", seed=1), 90, "4:4:4")
+        refused = R.pillow_file(R.image(24, 40, 3, "noise"), 90, "4:2:0", progressive=True)
+        assert jpeg_decode.parse(refused) is None and small[3][0] == "7x9-4:4:4"
+        files = [d for _n, d, _w in small[:4]] + [twin] + [d for _n, d, _w in small[4:8]] + [refused] + [d for _n, d, _w in small[8:]]
+        want = [w for _n, _d, w in small[:4]] + [R.pillow_pixels(twin)] + [w for _n, _d, w in small[4:8]] + [R.pillow_pixels(refused)] + \
+            [w for _n, _d, w in small[8:]]
+        at = files.index(refused)
+        accepted = [f for f in files if f is not refused]
+        whole = jpeg_decode.BatchStage([jpeg_decode.parse(f) for f in accepted], accepted).plan().workspace_bytes
+        out = {}
+        for tag, kw, chunks in (("one", {}, 1), ("two", dict(max_workspace_bytes=whole - 1), 2)):
+            got = jpeg_decode.decode_batch(files, DEV, **kw)
+            last = dict(jpeg_decode.LAST)
+            assert last["chunks"] == chunks and last["headers"] < chunks * len(accepted), last
+            assert [r for i, r in enumerate(last["route"]) if i != at] == ["device"] * len(accepted), last
+            assert last["route"][at] == "single host" and last["status"][at] is None, last
+            for i, (g, w) in enumerate(zip(got, want)):
+                assert np.array_equal(g.cpu().numpy(), w), (tag, i)
+            if chunks == 1:                                       # images of one shape side by side: 189 bytes padded to 192
+                assert got[3].untyped_storage().data_ptr() == got[4].untyped_storage().data_ptr()
+                assert got[4].storage_offset() - got[3].storage_offset() == 192
+            out[tag] = list(got)
+        return out
+    return Case("jpegdec-batch", run, ["scg_jpegdec_decode_batch"],
+                excused={"scg_jpegdec_decode_batch": {"table_dev": UPLOADED, "upload_dev": UPLOADED}})
+
+
+# ---- the camera gradients (camgrad/scg_camgrad.h) ----------------------------------------------------------------------------------
+
+def _camgrad_alone(n, mode, want_campos=True, culled=False):
+    """The kernel alone on planted records (test_gpu_camgrad._sized, _kernel), held to the fp64 restatement at the module's own
+    bar; culled: every radius 0, where the 35 outputs must still be written — exact zeros."""
+    def run(home):
+        import test_gpu_camgrad as T
+        inputs, cam, records, radii = T._sized(n, 3, mode)
+        if culled:
+            radii = torch.zeros_like(radii)
+        got = T._kernel(inputs, cam, 3, 1.0, records, radii, want_campos=want_campos, home=home)
+        if culled:
+            assert not got.any() and not np.signbit(got).any()
+        else:
+            T._held(got, inputs, cam, 3, 1.0, records, radii, ("guarded", n, mode, want_campos), want_campos=want_campos)
+        return dict(out35=torch.from_numpy(got))
+    return Case(f"camgrad-alone-{n}-{mode}" + ("" if want_campos else "-no-campos") + ("-culled" if culled else ""), run,
+                ["scg_camgrad_backward"])
+
+
+def _camgrad_model(nr, nb):
+    def run(home):
+        import geometry_refs as G
+        import test_gpu_camgrad as T
+        from scgaussian_amd import model_path as mp
+        n = nr + nb
+        model, md = T._raw_model(ray_fraction=nr / n, n=n)
+        md = home(md)
+        t = mp.tensors_of(md)
+        assert mp.supported(t) and (md.zval.shape[0], md.bg_xyz.shape[0]) == (nr, nb)
+        inputs = T._activated_inputs(model, md)
+        cam = T._cam(1)
+        radii = G.oracle_preprocess({k: v for k, v in inputs.items()}, cam, 3, 1.0)["radii"]
+        records = G.make_records(n, 43)
+        got = T._kernel(inputs, cam, 3, 1.0, records, radii, seven=mp._ModelArgs(t), home=home)
+        T._held(got, inputs, cam, 3, 1.0, records, radii, ("guarded", "model", nr, nb))
+        return dict(out35=torch.from_numpy(got))
+    return Case(f"camgrad-model-{nr}+{nb}", run, ["scg_camgrad_backward_model"])
+
+
+def _camgrad_routed(P):
+    """GaussianRasterizer with viewmatrix, projmatrix and campos requiring grad, two steps of one camera: the staged path, whose
+    gradient records are a tensor, then the one-call path, whose records are a raw pointer into the forward's workspace."""
+    def run(home):
+        import parity_utils as pu
+        from scgaussian_amd import rasterizer as R
+        from scgaussian_amd import synthetic as syn
+        W, H = W_RASTER, H_RASTER
+        sc, cam = _sparse_scene("random", P, P)
+        st = pu.hip_settings(cam, 3, BG_RASTER)
+        st = home(st._replace(**{k: getattr(st, k).detach().clone().requires_grad_(True) for k in ("viewmatrix", "projmatrix", "campos")}))
+        camera = {k: getattr(st, k) for k in ("viewmatrix", "projmatrix", "campos")}
+        leaves = {k: home(v.detach().to(DEV).contiguous().requires_grad_(True)) for k, v in pu.run_oracle_inputs(sc, cam, 3, 1.0, "sh_sr").items()}
+        ups = [home(g.to(DEV)) for g in syn.make_upstream_grads(W, H, seed=P + 50)]
+        kw = {k: v for k, v in leaves.items() if k not in ("means3D", "means2D", "opacities")}
+        out = {}
+        for step in ("staged", "one_call"):
+            for t in (*leaves.values(), *camera.values()):
+                t.grad = None
+            c, radii, d, a = R.GaussianRasterizer(st)(means3D=leaves["means3D"], means2D=leaves["means2D"], opacities=leaves["opacities"], **kw)
+            torch.autograd.backward([c, d, a], ups)
+            out.update({f"{step}_color": c, f"{step}_depth": d, f"{step}_alpha": a, f"{step}_radii": radii})
+            for k, v in (*leaves.items(), *camera.items()):
+                assert v.grad is not None, (step, k)
+                out[f"grad_{step}_{k}"] = v.grad.clone()
+        return out
+    absent = _absent_gradients("sh_sr")
+    return Case(f"camgrad-routed-P{P}", run, ["scg_camgrad_backward", "scg_forward", "scg_backward"], excused=RASTER_EXCUSED,
+                not_passed={"scg_geometry_backward": absent, "scg_backward": absent, "scg_binning": {"keys_sorted"}},
+                fields={"scg_forward": ["frame.tile_cost_out"], "scg_backward": ["frame.bwd_cost_out"]},
+                close=lambda name: _atomics if name.startswith("grad_") else None)
+
+
 CASES = (
     [_image_loss(s, lam) for s, lam in (((3, 1, 1), 0.2), ((3, 5, 7), 0.2), ((3, 33, 65), 1.0))]
     + [_image_loss_pair(s) for s in ((3, 1, 1), (3, 33, 65))] + [_image_loss_pair((3, 33, 65), same=True)]
@@ -1167,6 +1339,10 @@ CASES = (
        _raster("col_cov", 3, 65, "one_tile")]
     + [_model_path(1, 0, 0), _model_path(0, 1, 3), _model_path(61, 59, 3), _model_path(64, 65, 0)]
     + [_model_path(33, 32, 3, "culled"), _model_path(33, 32, 3, "one_tile")]
+    + [_jpegdec_single(), _jpegdec_batch()]
+    + [_camgrad_alone(n, mode) for n in (1, 257, 2 * 256 + 1) for mode in ("sh_sr", "col_cov")]
+    + [_camgrad_alone(257, "sh_sr", want_campos=False), _camgrad_alone(257, "sh_sr", culled=True)]
+    + [_camgrad_model(61, 59), _camgrad_routed(65)]
 )
 
 
@@ -1220,7 +1396,8 @@ QUERIES = {
     "scg_mp_last_error", "scg_mp_abi_version", "scg_mp_struct_bytes", "scg_mp_layout", "scg_mp_workspace_bytes", "scg_png_last_error",
     "scg_png_abi_version", "scg_png_struct_bytes", "scg_png_layout", "scg_jpg_last_error", "scg_jpg_abi_version", "scg_jpg_struct_bytes",
     "scg_jpeg_layout", "scg_vw_last_error", "scg_vw_abi_version", "scg_vw_warp_scratch_bytes",
-    "scg_vw_smooth_scratch_bytes",
+    "scg_vw_smooth_scratch_bytes", "scg_jpegdec_last_error", "scg_jpegdec_abi_version", "scg_jpegdec_sizes", "scg_jpegdec_batch_plan",
+    "scg_camgrad_last_error", "scg_camgrad_abi_version", "scg_camgrad_sizes",
 }
 
 

@@ -1,4 +1,4 @@
-"""The JPEG decoder on the GPU (csrc/dec/jpegunpack.hip through scgaussian_amd.jpeg_decode), held for EQUALITY OF BYTES to the numpy
+"""The JPEG decoder on the GPU (csrc/jpegunpack.hip through scgaussian_amd.jpeg_decode), held for EQUALITY OF BYTES to the numpy
 restatement of its rule (tests/jpegdec_refs.py), to Pillow's pixels where Pillow reads JPEG, and to the recorded pixels of
 tests/golden/ref_jpegdec.npz.  No tolerance exists in this file."""
 import contextlib

@@ -1,8 +1,7 @@
 """The JPEG decoder without a GPU: the numpy restatement of its rule (tests/jpegdec_refs.py) against Pillow's pixels and a mutant of
 each rule, jpeg_decode.parse, the header's text against the library's exports and the binding, every argument code, read_avi, and
-the build tables that the decoder must leave as they are."""
+the decoder's entry of the build table."""
 import ctypes as C
-import glob
 import io
 import os
 
@@ -10,7 +9,6 @@ import numpy as np
 import pytest
 
 import abi_compare
-import abi_text
 import jpegdec_refs as R
 from scgaussian_amd import _lib, _lib_jpegdec, build, jpeg, jpeg_decode
 
@@ -170,28 +168,9 @@ def test_huffman_table_is_the_header_blocks_and_refuses_a_full_code():
 
 # ---- the ABI -----------------------------------------------------------------------------------------------------------------------
 def test_header_text_exports_and_binding_agree():
-    abi = abi_text.read([_lib_jpegdec.HEADER_PATH])
-    where = abi_text.declared_in(abi)
-    assert all(n.startswith("scg_jpegdec_") for n in where) and not abi.structs
-    assert abi_compare.exported_names(_lib_jpegdec.LIB_PATH) == sorted(where) == sorted(_lib_jpegdec.SYMBOLS)
-    diffs = [d for fn in abi.functions for d in abi_compare.prototype_differences(fn, *_lib_jpegdec.SYMBOLS[fn.name], {}, abi_compare.ANY)]
-    assert not diffs, "\n".join(diffs)
-    defined = {n[4:]: v for n, v in abi.defines.items()}
-    assert {n: getattr(_lib_jpegdec, n, None) for n in defined} == defined
-    assert {n for n in vars(_lib_jpegdec) if n.startswith("JPEGDEC_")} <= set(defined)
-    assert _lib_jpegdec.load().scg_jpegdec_abi_version() == _lib_jpegdec.ABI_VERSION == abi.defines["SCG_JPEGDEC_ABI_VERSION"]
+    abi = abi_compare.check_side_library(_lib_jpegdec, "jpegdec", "scg_jpegdec.h", abi_compare.ANY)
+    assert not abi.structs
     assert R.SUBSEQ == _lib_jpegdec.JPEGDEC_SUBSEQ and R.THREADS == _lib_jpegdec.JPEGDEC_THREADS
-
-
-def test_no_other_library_declares_or_exports_the_decoders_names():
-    headers = sorted(glob.glob(os.path.join(build.INCLUDE, "**", "*.h"), recursive=True))
-    assert headers and _lib_jpegdec.HEADER_PATH not in headers
-    for h in headers:
-        assert "scg_jpegdec" not in open(h).read(), h
-    libs = [build.LIB_PATH] + [build.side_library(k)[0] for k in build.SIDE_LIBRARIES]
-    for lib in libs:
-        assert not [n for n in abi_compare.exported_names(lib) if n.startswith("scg_jpegdec")], lib
-    assert not set(_lib_jpegdec.SYMBOLS) & set(_lib.SYMBOLS)
 
 
 def _frame(**kw):
@@ -271,17 +250,10 @@ def test_read_avi_returns_what_write_avi_wrote(tmp_path):
 
 
 # ---- the build ---------------------------------------------------------------------------------------------------------------------
-def test_the_build_tables_are_unchanged_and_the_decoder_stands_beside_them():
-    assert list(build.SIDE_LIBRARIES) == ["io", "img", "mp", "vw", "lp", "png", "jpg"]
-    assert {k: list(v[1]) for k, v in build.SIDE_LIBRARIES.items()} == {
-        "io": ["plypack.hip"], "img": ["resample.hip"], "mp": ["matchpoint.hip"], "vw": ["virtualwarp.hip"], "lp": ["lpips.hip"],
-        "png": ["pngpack.hip"], "jpg": ["jpegpack.hip"]}
+def test_the_decoder_is_one_entry_of_the_side_library_table():
     assert len(build.SOURCES) == 17 and "jpegunpack.hip" not in build.SOURCES
-    assert not [h for h in build.HEADERS if os.sep + "dec" + os.sep in h]
-    assert not glob.glob(os.path.join(build.INCLUDE, "**", "*jpegdec*"), recursive=True)
-    covered = build.decoder_headers()
-    assert _lib_jpegdec.HEADER_PATH in covered and all(os.path.exists(h) for h in covered)
-    src = open(os.path.join(build.DECODER_DIR, build.DECODER_SOURCE)).read()
+    assert abi_compare.side_header("jpegdec", "scg_jpegdec.h") in build.HEADERS
+    assert build.SIDE_LIBRARIES["jpegdec"] == ("jpegdec", {"jpegunpack.hip": ["-ffp-contract=off"]})
+    src = open(os.path.join(build.CSRC, "jpegunpack.hip")).read()
     included = {line.split('"')[1] for line in src.splitlines() if line.startswith('#include "')}
-    assert included == {"scg_jpegdec.h"} | {"../" + h for h in build.DECODER_INCLUDES if h != "scg_common.h"}
-    assert build.DECODER_FLAGS == ["-ffp-contract=off"] and _lib_jpegdec.LIB_PATH == build.DECODER_LIB
+    assert included == {"../../include/jpegdec/scg_jpegdec.h", "compact.h", "host_align.h", "host_error.h"}

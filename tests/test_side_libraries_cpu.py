@@ -21,6 +21,8 @@ EXPECTED = {
     "lp": ("scg_lpips.h", {"lpips.hip": []}),
     "png": ("scg_png.h", {"pngpack.hip": []}),
     "jpg": ("scg_jpeg.h", {"jpegpack.hip": ["-ffp-contract=off"]}),
+    "jpegdec": ("scg_jpegdec.h", {"jpegunpack.hip": ["-ffp-contract=off"]}),
+    "camgrad": ("scg_camgrad.h", {"camgrad.hip": ["-ffp-contract=off"]}),
 }
 CONTRACT_OFF = {"geometry.hip", "evalview.hip", "optim.hip", "initstage.hip", "densify.hip", "seed.hip", "geocheck.hip", "mono.hip",
                 "depthviz.hip"}
@@ -35,8 +37,8 @@ def _header_names(key):
     return set(abi_text.declared_in(abi_text.read(paths)))
 
 
-def test_the_table_names_the_seven_libraries_in_order():
-    assert list(build.SIDE_LIBRARIES) == list(EXPECTED) == ["io", "img", "mp", "vw", "lp", "png", "jpg"]
+def test_the_table_names_the_nine_libraries_in_order():
+    assert list(build.SIDE_LIBRARIES) == list(EXPECTED) == ["io", "img", "mp", "vw", "lp", "png", "jpg", "jpegdec", "camgrad"]
     assert not any("jpeg" in s or "jpg" in s for s in build.SOURCES)     # the JPEG packer is a side library's, not the main one's
     assert {s for s, flags in build.SOURCES.items() if flags == ["-ffp-contract=off"]} == CONTRACT_OFF
     assert build.SOURCES["blend.hip"] == ["-fno-slp-vectorize"]
@@ -59,7 +61,7 @@ def test_build_table_entry(key):
 
 def test_headers_are_the_same_files_as_the_hand_written_list():
     want = sorted(glob.glob(os.path.join(build.CSRC, "*.h"))) + sorted(glob.glob(os.path.join(build.INCLUDE, "*.h")))
-    for d in ("io", "img", "mp", "vw", "lp", "png", "jpg"):
+    for d in ("io", "img", "mp", "vw", "lp", "png", "jpg", "jpegdec", "camgrad"):
         want += sorted(glob.glob(os.path.join(build.INCLUDE, d, "*.h")))
     assert build.HEADERS == want and len(set(want)) == len(want)
     # ... and no header under include/ or csrc/ is outside it
@@ -71,7 +73,7 @@ def test_headers_are_the_same_files_as_the_hand_written_list():
 def test_all_pairs_share_no_source_path_or_symbol():
     tables = dict({"main": build.SOURCES}, **{k: build.side_library(k)[1] for k in build.SIDE_LIBRARIES})
     paths = [build.LIB_PATH] + [build.side_library(k)[0] for k in build.SIDE_LIBRARIES]
-    assert len(tables) == 8 and len(set(paths)) == 8
+    assert len(tables) == 10 and len(set(paths)) == 10
     everything = [s for t in tables.values() for s in t]
     assert len(set(everything)) == len(everything)                       # every source belongs to exactly one library
     assert sorted(everything) == sorted(os.path.basename(p) for p in glob.glob(os.path.join(build.CSRC, "*.hip")))
